@@ -14,6 +14,11 @@ graphs shard with no data-path collective) and the step ends with ONE RCCL all-r
 The step — including the all-reduce — is captured once into a hipGraph (launch-bound regime: 8 kernels
 of 5-17 us) and replayed; ``--no-graph`` times eager launches instead.
 
+``--dump-outputs DIR`` writes what the last timed step computed (rank 0) as float32 ``DIR/<name>.npy``: ``out`` (the layer's
+output), ``d_x`` and ``grad.<parameter>`` (the gradient bucket, after the all-reduce when N > 1).  The inputs are seeded, so
+two builds given the same arguments can be compared output for output; beyond 64 MB in all, a fixed seeded sample of the node
+rows is written instead of all of them.
+
 Prints ONE JSON line (rank 0).  Extra objects:
   roofline          the scatter-aggregate kernel THE TIMED STEP LAUNCHES (gather + segment softmax + scatter-add with
                     the update GEMM fused in): algorithmic bytes / its average duration vs the HBM peak
@@ -44,7 +49,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-# /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s HBM3E spec, ~6.29 TB/s measured-achievable; 157.3 TF dense fp32 MFMA
+# MI355X: 8 TB/s HBM3E spec, ~6.29 TB/s measured-achievable; 157.3 TF dense fp32 MFMA
 HBM_PEAK_GBS = 8000.0
 HBM_ACHIEVABLE_GBS = 6290.0
 MFMA_F32_PEAK_TFLOPS = 157.3
@@ -225,6 +230,34 @@ def cpu_baseline(batch_cpu, conv_cpu, x_cpu, cot_cpu, budget_s):
             "ms_per_step_by_threads": {str(c): runs[c][1] / runs[c][0] * 1e3 for c in counts}}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, last, params, names, limit=DUMP_LIMIT_BYTES):
+    """``--dump-outputs``: the output, d_x and the per-parameter gradients of one step as float32 ``dirname/<name>.npy``.  The
+    parameter gradients are cut from the bucket the step returns (the reduced values when N > 1).  Past ``limit`` bytes in all,
+    out and d_x keep the same fixed seeded sample of node rows (sorted), the gradients stay whole."""
+    import numpy as np
+    arrays = {"out": last["out"], "d_x": last["d_x"]}
+    bucket, off = last["bucket"], 0
+    for n, p in zip(names, params):
+        arrays["grad." + n] = bucket[off:off + p.numel()].view(p.shape)
+        off += p.numel()
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    total = sum(v.numel() * 4 for v in arrays.values())
+    limit -= 4096                               # room for the .npy headers
+    if total > limit:
+        rows = arrays["out"].size(0)
+        fixed = total - (arrays["out"].numel() + arrays["d_x"].numel()) * 4
+        row_bytes = (arrays["out"][0].numel() + arrays["d_x"][0].numel()) * 4
+        keep = max(1, min(rows, (limit - fixed) // row_bytes))
+        idx = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        arrays["out"], arrays["d_x"] = arrays["out"][idx], arrays["d_x"][idx]
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v.numpy())
+
+
 def spawn_ranks(n):
     """``python bench.py --gpus N`` run as written: start the N ranks ourselves.  This process has made no GPU call yet
     (``device_count`` does not initialise the runtime) and never will: it only waits for its children — fresh interpreters,
@@ -267,7 +300,11 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline time budget (0 = skip)")
     ap.add_argument("--large-batch", type=int, default=16384, help="extra roofline point beyond the LLC (0 = skip)")
     ap.add_argument("--prof-reps", type=int, default=30, help="eager profiled steps behind roofline_kernels")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output and gradients as float32 DIR/<name>.npy (rank 0, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -343,6 +380,8 @@ def main():
         if bucket is None:
             bucket = torch.cat([g_.reshape(-1) for g_ in grads[:-1]], out=flat)
         live["bucket"], live["d_x"] = bucket, grads[-1]
+        if args.dump_outputs:
+            live["out"] = out                   # kept only when dumping: the timed graphs' memory stays as it is otherwise
         return bucket
 
     def compute_and_reduce():
@@ -381,6 +420,7 @@ def main():
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 compute()
+    live_single = dict(live)     # the tensors a replay of `graph` writes (a capture allocates them once, every replay refills them)
 
     # ---- several consecutive steps per graph launch: the same kernels, the same work per step, fewer launch bubbles.  Only when the
     #      whole step (collective included) is inside the graph; an eager all-reduce between steps keeps one step per launch ----
@@ -405,6 +445,7 @@ def main():
             dist.all_reduce(flag, op=dist.ReduceOp.MIN)
             if int(flag.item()) == 0:
                 graph_multi = None
+    live_multi = dict(live)      # ... and those of the last step inside `graph_multi`
 
     def step():
         if graph is not None:
@@ -473,6 +514,17 @@ def main():
     ms = dt / args.steps * 1e3
     value = B * world * args.steps / dt
     leg("warm-up steps + timed steps")
+    if args.dump_outputs and rank == 0:
+        # the last timed step ran in: the multi-step graph when run_steps ended on a whole launch of it, else the single-step graph,
+        # else (eager) the step itself
+        if graph is None:
+            last = live
+        elif graph_multi is not None and args.steps % S == 0:
+            last = live_multi
+        else:
+            last = live_single
+        dump_outputs(args.dump_outputs, last, params, [n for n, _ in conv.named_parameters()])
+        leg("dump outputs")
 
     # ---- the other staging mode, timed the same way: with the default (cached images) the headline step starts at the node
     #      GEMM; a training step re-lays the parameters out after every optimizer write, i.e. k_stage_params inside every step ----

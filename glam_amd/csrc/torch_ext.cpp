@@ -8,6 +8,7 @@
 //
 // Host-only C++ (no device code): built by csrc/Makefile with the system compiler against torch's headers.
 #include <ATen/ATen.h>
+#include <algorithm>
 #include <c10/hip/HIPStream.h>
 #include <torch/csrc/autograd/custom_function.h>
 #include <torch/library.h>
@@ -320,6 +321,59 @@ struct Pool5Fn : public torch::autograd::Function<Pool5Fn> {
 Tensor global_pool5(const Tensor& x, const Tensor& ptr, int64_t k) { return Pool5Fn::apply(x, ptr, k); }
 Tensor sort_pool_topk_last(const Tensor& x, const Tensor& ptr, int64_t k) { return Pool5Fn::apply(x, ptr, k).slice(1, 2 * x.size(1)); }
 
+// ---- NNConv over continuous edge features (glam_nnconv_ec_*): nn = Linear(De, 32) -> ReLU -> Linear(32, Cin*Cout) ----------------
+// The stacked weight is built inside the node (one launch) and its gradient scattered back to nn.2 / root in the backward.
+struct NNConvECFn : public torch::autograd::Function<NNConvECFn> {
+    static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& edge_attr, const Tensor& w0, const Tensor& b0, const Tensor& w1,
+                          const Tensor& b1, const Tensor& root, const c10::optional<Tensor>& bias_opt, const Tensor& rowptr, const Tensor& src,
+                          const Tensor& eid, const Tensor& colptr, const Tensor& dst, const Tensor& eid_t, bool mean) {
+        const Tensor bias = bias_opt.has_value() ? *bias_opt : Tensor();
+        want(x, at::kFloat, "x"); want(edge_attr, at::kFloat, "edge_attr"); want(w0, at::kFloat, "w0"); want(b0, at::kFloat, "b0");
+        want(w1, at::kFloat, "w1"); want(b1, at::kFloat, "b1"); want(root, at::kFloat, "root");
+        if (bias.defined()) want(bias, at::kFloat, "bias");
+        want(rowptr, at::kInt, "rowptr"); want(src, at::kInt, "src"); want(eid, at::kInt, "eid");
+        TORCH_CHECK(x.dim() == 2 && edge_attr.dim() == 2 && root.dim() == 2, "nnconv_ec: x [N, Cin], edge_attr [E, De], root [Cin, Cout]");
+        const int64_t N = x.size(0), E = edge_attr.size(0), De = edge_attr.size(1), Cin = x.size(1), Cout = root.size(1);
+        TORCH_CHECK(root.size(0) == Cin && w0.sizes() == at::IntArrayRef({32, De}) && b0.numel() == 32 &&
+                        w1.sizes() == at::IntArrayRef({Cin * Cout, 32}) && b1.numel() == Cin * Cout && (!bias.defined() || bias.numel() == Cout) &&
+                        rowptr.numel() == N + 1 && src.numel() == E && eid.numel() == E, "nnconv_ec: shape mismatch");
+        TORCH_CHECK(glam_nnconv_ec_supported((int)De, 32, (int)Cin, (int)Cout) == 1, "nnconv_ec: unsupported shape De=", De, " Cin=", Cin,
+                    " Cout=", Cout);
+        Tensor wstack = at::empty({34 * Cin, Cout}, x.options()), h = at::empty({E, 32}, x.options()), out = at::empty({N, Cout}, x.options());
+        check_rc(glam_nnconv_ec_stack(fp(w1), fp(b1), fp(root), (int)Cin, (int)Cout, fpm(wstack), cur_stream()), "glam_nnconv_ec_stack");
+        const size_t nws = glam_nnconv_ec_workspace_bytes(N, E, (int)De, (int)Cin, (int)Cout, 0);
+        Tensor ws = at::empty({(int64_t)std::max<size_t>(nws, 16)}, x.options().dtype(at::kByte));
+        check_rc(glam_nnconv_ec_fwd(fp(x), fp(edge_attr), ip(rowptr), ip(src), ip(eid), N, E, (int)De, (int)Cin, (int)Cout, fp(w0), fp(b0),
+                                    fp(wstack), fp(bias), mean ? 1 : 0, fpm(h), ws.data_ptr(), (size_t)ws.numel(), fpm(out), cur_stream()),
+                 "glam_nnconv_ec_fwd");
+        ctx->save_for_backward({x, edge_attr, wstack, h, rowptr, src, eid, colptr, dst, eid_t});
+        ctx->saved_data["mean"] = mean;
+        ctx->saved_data["bias"] = bias.defined();
+        return out;
+    }
+    static variable_list backward(AutogradContext* ctx, variable_list grads) {
+        auto s = ctx->get_saved_variables();
+        const Tensor &x = s[0], &ea = s[1], &wstack = s[2], &h = s[3];
+        const bool mean = ctx->saved_data["mean"].toBool(), has_bias = ctx->saved_data["bias"].toBool();
+        Tensor d_out = grads[0].contiguous();
+        const int64_t N = x.size(0), E = ea.size(0), De = ea.size(1), Cin = x.size(1), Cout = wstack.size(1);
+        auto o = x.options();
+        Tensor dx = at::empty({N, Cin}, o), dw0 = at::empty({32, De}, o), db0 = at::empty({32}, o), dws = at::empty({34 * Cin, Cout}, o),
+               dbias = at::empty({Cout}, o), dw1 = at::empty({Cin * Cout, 32}, o), db1 = at::empty({Cin * Cout}, o), droot = at::empty({Cin, Cout}, o);
+        Tensor ws = at::empty({(int64_t)std::max<size_t>(glam_nnconv_ec_workspace_bytes(N, E, (int)De, (int)Cin, (int)Cout, 1), 16)}, o.dtype(at::kByte));
+        check_rc(glam_nnconv_ec_bwd(fp(d_out), fp(x), fp(ea), ip(s[4]), ip(s[5]), ip(s[6]), ip(s[7]), ip(s[8]), ip(s[9]), N, E, (int)De, (int)Cin,
+                                    (int)Cout, fp(wstack), fp(h), mean ? 1 : 0, nullptr, fpm(dx), fpm(dw0), fpm(db0), fpm(dws), fpm(dbias), ws.data_ptr(),
+                                    (size_t)ws.numel(), cur_stream()), "glam_nnconv_ec_bwd");
+        check_rc(glam_nnconv_ec_unstack(fp(dws), (int)Cin, (int)Cout, fpm(dw1), fpm(db1), fpm(droot), cur_stream()), "glam_nnconv_ec_unstack");
+        return {dx, Tensor(), dw0, db0, dw1, db1, droot, has_bias ? dbias : Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+Tensor nnconv_ec(const Tensor& x, const Tensor& edge_attr, const Tensor& w0, const Tensor& b0, const Tensor& w1, const Tensor& b1, const Tensor& root,
+                 const c10::optional<Tensor>& bias, const Tensor& rowptr, const Tensor& src, const Tensor& eid, const Tensor& colptr, const Tensor& dst,
+                 const Tensor& eid_t, bool mean) {
+    return NNConvECFn::apply(x, edge_attr, w0, b0, w1, b1, root, bias, rowptr, src, eid, colptr, dst, eid_t, mean);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(glam, m) {
@@ -338,4 +392,6 @@ TORCH_LIBRARY(glam, m) {
     m.def("segment_softmax_aggregate(Tensor gate, Tensor v, Tensor ptr) -> Tensor", &segment_softmax_aggregate);
     m.def("global_pool5(Tensor x, Tensor ptr, int k=3) -> Tensor", &global_pool5);
     m.def("sort_pool_topk_last(Tensor x, Tensor ptr, int k=3) -> Tensor", &sort_pool_topk_last);
+    m.def("nnconv_ec(Tensor x, Tensor edge_attr, Tensor w0, Tensor b0, Tensor w1, Tensor b1, Tensor root, Tensor? bias, Tensor rowptr, "
+          "Tensor src, Tensor eid, Tensor colptr, Tensor dst, Tensor eid_t, bool mean=True) -> Tensor", &nnconv_ec);
 }

@@ -410,6 +410,20 @@ class NNConv(MessagePassing):
             return out if isinstance(out, tuple) else (out, x)
         return out
 
+    def _edge_conditioned_route(self, x, edge_attr):
+        """The general (continuous edge feature) branch runs on ``ops.nnconv_edge_conditioned`` when the edge network is the
+        reference's ``Linear(De, 32) -> ReLU -> Linear(32, in*out)``, the edge features carry no gradient, aggr is mean or add, the
+        tensors are CUDA fp32 and the kernels cover the shape; every other case keeps the per-edge weight tensor."""
+        if edge_attr.requires_grad or self.aggr not in ("mean", "add") or self.root is None or edge_attr.dim() != 2 or x.dim() != 2:
+            return False
+        De = edge_attr.size(1)
+        if not _is_edge_mlp(self.nn, De, self.in_channels * self.out_channels) or x.size(1) != self.in_channels:
+            return False
+        ts = [x, edge_attr, self.root] + ([] if self.bias is None else [self.bias]) + [p for m in (self.nn[0], self.nn[2]) for p in (m.weight, m.bias)]
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in ts):
+            return False
+        return ops.nnconv_ec_supported(De, 32, self.in_channels, self.out_channels)
+
     def _forward(self, x, edge_index, edge_attr, with_identity):
         gi = ops.graph_index(edge_index, x.size(0))
         De = edge_attr.size(1)
@@ -441,6 +455,13 @@ class NNConv(MessagePassing):
                 return ops.matmul_tall(S.view(x.size(0), (Dp + 1) * C), w_all, self.bias)
             S = ops.edge_weighted_sum(x, ea, gi, mean=(self.aggr == "mean"))           # [N, Dp, in]
             out = ops.matmul_tall(S[:, :De].reshape(x.size(0), De * self.in_channels), w_rel)
+        elif self._edge_conditioned_route(x, edge_attr):
+            # continuous edge features (the protein tower's contact maps): h_e = relu(nn.0(e)) per edge, then ONE product
+            # [S | x] @ Wstack + bias with S the h-weighted neighbour sums (csrc/nnconv_ec.hip) — no [E, C*C] weight tensor
+            lin0, lin2 = self.nn[0], self.nn[2]
+            w_ec = ops.scoped_weights(("nnconv-ec", id(self)), self, lambda: ops.nnconv_ec_stack(lin2.weight, lin2.bias, self.root))
+            return ops.nnconv_edge_conditioned(x, edge_attr, gi, lin0.weight, lin0.bias, lin2.weight, lin2.bias, self.root, self.bias,
+                                               mean=(self.aggr == "mean"), with_identity=with_identity, wstack=w_ec)
         else:
             weight = self.nn(edge_attr).view(-1, self.in_channels, self.out_channels)
             msg = torch.bmm(x.index_select(0, edge_index[0]).unsqueeze(1), weight).squeeze(1)
@@ -450,6 +471,13 @@ class NNConv(MessagePassing):
         if self.bias is not None:
             out = out + self.bias
         return out
+
+
+def _is_edge_mlp(nn, De, M):
+    """``nn`` is exactly ``Sequential(Linear(De, 32), ReLU(), Linear(32, M))`` with biases (the reference's edge network)."""
+    return (type(nn) is Sequential and len(nn) == 3 and type(nn[0]) is Linear and type(nn[1]) is ReLU and type(nn[2]) is Linear
+            and nn[0].in_features == De and nn[0].out_features == 32 and nn[2].in_features == 32 and nn[2].out_features == M
+            and nn[0].bias is not None and nn[2].bias is not None)
 
 
 def _glorot(t):

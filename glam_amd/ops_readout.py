@@ -440,6 +440,110 @@ def self_slot_supported(K, D):
     return K in (4, 8) and D % 4 == 0
 
 
+# --------------------------------------------------------------------------------------
+# NNConv over continuous edge features (csrc/nnconv_ec.hip): no per-edge weight tensor
+# --------------------------------------------------------------------------------------
+class _NNConvECStack(torch.autograd.Function):
+    """``Wstack`` f32[34 Cin, Cout] = [A_0; ...; A_31; b1; root] from ``nn.2.weight``, ``nn.2.bias`` and ``root`` (one launch each way)."""
+
+    @staticmethod
+    def forward(ctx, w1, b1, root):
+        require_device(w1, b1, root)
+        w1, b1, root = f32c(w1, "nn.2.weight"), f32c(b1, "nn.2.bias"), f32c(root, "root")
+        Cin, Cout = root.shape
+        out = torch.empty(34 * Cin, Cout, dtype=torch.float32, device=w1.device)
+        check(_lib.load().glam_nnconv_ec_stack(ptr(w1), ptr(b1), ptr(root), Cin, Cout, ptr(out), stream()), "glam_nnconv_ec_stack")
+        ctx.dims = (Cin, Cout)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_ws):
+        Cin, Cout = ctx.dims
+        d_ws = f32c(d_ws, "d_wstack")
+        dw1 = torch.empty(Cin * Cout, 32, dtype=torch.float32, device=d_ws.device)
+        db1 = torch.empty(Cin * Cout, dtype=torch.float32, device=d_ws.device)
+        droot = torch.empty(Cin, Cout, dtype=torch.float32, device=d_ws.device)
+        check(_lib.load().glam_nnconv_ec_unstack(ptr(d_ws), Cin, Cout, ptr(dw1), ptr(db1), ptr(droot), stream()), "glam_nnconv_ec_unstack")
+        return dw1, db1, droot
+
+
+def nnconv_ec_stack(w1, b1, root):
+    """The stacked weight of ``nnconv_edge_conditioned`` (build it once per model forward: ``ops.scoped_weights``)."""
+    return _NNConvECStack.apply(w1, b1, root)
+
+
+class _NNConvEC(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, edge_attr, gi, w0, b0, wstack, bias, mean, with_identity=False):
+        require_device(x, edge_attr, w0, b0, wstack)
+        x_in = x
+        x, ea = f32c(x, "x"), f32c(edge_attr, "edge_attr")
+        w0, b0, wstack = f32c(w0, "nn.0.weight"), f32c(b0, "nn.0.bias"), f32c(wstack, "wstack")
+        bias = None if bias is None else f32c(bias, "bias")
+        N, Cin = x.shape
+        E, De = ea.shape
+        Cout = wstack.size(1)
+        if N != gi.N or E != gi.E or wstack.size(0) != 34 * Cin or tuple(w0.shape) != (32, De):
+            raise GlamHipError("nnconv_edge_conditioned: x / edge_attr / weights disagree with the edge list")
+        lib = _lib.load()
+        h = torch.empty(E, 32, dtype=torch.float32, device=x.device)
+        out = torch.empty(N, Cout, dtype=torch.float32, device=x.device)
+        nws = lib.glam_nnconv_ec_workspace_bytes(N, E, De, Cin, Cout, 0)
+        ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=x.device)
+        check(lib.glam_nnconv_ec_fwd(ptr(x), ptr(ea), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), N, E, De, Cin, Cout, ptr(w0), ptr(b0),
+                                     ptr(wstack), ptr(bias), int(mean), ptr(h), ptr(ws), ws.numel(), ptr(out), stream()), "glam_nnconv_ec_fwd")
+        del ws
+        ctx.save_for_backward(x, ea, wstack, h)
+        ctx.gi, ctx.dims, ctx.has_bias = gi, (N, E, De, Cin, Cout, int(mean)), bias is not None
+        ctx.aliased = bool(with_identity)
+        if ctx.aliased:
+            ctx.set_materialize_grads(False)
+            return out, x_in.view_as(x_in)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, d_alias=None):
+        x, ea, wstack, h = ctx.saved_tensors
+        gi = ctx.gi
+        N, E, De, Cin, Cout, mean = ctx.dims
+        if d_out is None:                    # (only with the alias: the layer's output itself was not used)
+            return d_alias, None, None, None, None, None, None, None, None
+        d_out = f32c(d_out, "d_out")
+        d_alias = None if d_alias is None else f32c(d_alias, "d_identity")
+        colptr, dst, eid_t = gi.transpose()
+        dev = d_out.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        dx, dw0, db0 = torch.empty(N, Cin, **f32), torch.empty(32, De, **f32), torch.empty(32, **f32)
+        dws, dbias = torch.empty(34 * Cin, Cout, **f32), torch.empty(Cout, **f32)
+        lib = _lib.load()
+        ws = torch.empty(max(lib.glam_nnconv_ec_workspace_bytes(N, E, De, Cin, Cout, 1), 16), dtype=torch.uint8, device=dev)
+        check(lib.glam_nnconv_ec_bwd(ptr(d_out), ptr(x), ptr(ea), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t),
+                                     N, E, De, Cin, Cout, ptr(wstack), ptr(h), mean, ptr(d_alias), ptr(dx), ptr(dw0), ptr(db0), ptr(dws),
+                                     ptr(dbias), ptr(ws), ws.numel(), stream()), "glam_nnconv_ec_bwd")
+        return dx, None, None, dw0, db0, dws, (dbias if ctx.has_bias else None), None, None
+
+
+def nnconv_ec_supported(De, hidden, Cin, Cout):
+    return _lib.load().glam_nnconv_ec_supported(De, hidden, Cin, Cout) == 1
+
+
+def nnconv_edge_conditioned(x, edge_attr, gi, w0, b0, w1, b1, root, bias, mean=True, with_identity=False, wstack=None):
+    """PyG ``NNConv(Cin, Cout, Linear(De, 32) -> ReLU -> Linear(32, Cin*Cout), aggr='mean' | 'add')`` on continuous edge features
+    without the per-edge weight tensor: ``out = [S | x] @ Wstack + bias`` (csrc/nnconv_ec.hip; the algebra is in its header).
+    ``w0, b0, w1, b1``: ``nn.0.weight``, ``nn.0.bias``, ``nn.2.weight``, ``nn.2.bias``; ``bias`` may be None; ``wstack``: a prebuilt
+    ``nnconv_ec_stack(w1, b1, root)`` (shared by the applications of one forward), else built here.  No gradient w.r.t.
+    ``edge_attr`` (edge data).  ``with_identity``: returns ``(out, identity)`` as ``edge_weighted_sum`` does."""
+    if wstack is None:
+        wstack = nnconv_ec_stack(w1, b1, root)
+    if with_identity:
+        if torch.is_grad_enabled() and x.requires_grad:
+            return _NNConvEC.apply(x, edge_attr, gi, w0, b0, wstack, bias, mean, True)
+        return _NNConvEC.apply(x, edge_attr, gi, w0, b0, wstack, bias, mean), x
+    return _NNConvEC.apply(x, edge_attr, gi, w0, b0, wstack, bias, mean)
+
+
 _ONEHOT_CACHE: dict = {}
 
 

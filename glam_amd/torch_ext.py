@@ -8,6 +8,7 @@ forwarding to the C ABI of ``include/glam_hip.h``.  This is the boundary SURVEY.
     triplet_aggregate(xw, a_ij, edge_attr, w_edge?, M, rowptr, src, eid, colptr, dst, eid_t, heads, slope=0.2) -> aggr
     triplet_layer(x, edge_attr, weight_node, weight_edge, weight_triplet_att, weight_scale, bias, <6 CSR tensors>, heads, slope=0.2) -> out
     segment_pool(x, ptr, mode)  segment_softmax_aggregate(gate, v, ptr)  global_pool5(x, ptr, k=3)  sort_pool_topk_last(x, ptr, k=3)
+    nnconv_ec(x, edge_attr, w0, b0, w1, b1, root, bias?, rowptr, src, eid, colptr, dst, eid_t, mean=True) -> out
 
 ``load()`` registers the library with torch's dispatcher; there is no fallback: a missing ``.so`` raises."""
 from __future__ import annotations
@@ -35,4 +36,4 @@ def load():
 
 
 OPS = ("csr_from_edge_index", "batch_ptr", "triplet_aggregate", "triplet_layer", "segment_pool", "segment_softmax_aggregate",
-       "global_pool5", "sort_pool_topk_last")
+       "global_pool5", "sort_pool_topk_last", "nnconv_ec")

@@ -531,6 +531,34 @@ int glam_edge_wsum_bwd_add(const float* d_out, const float* w, const int32_t* co
 /* self_slot = 1 (K in {4, 8}, D % 4 == 0): out is f32[N, K+1, D] and slot K of node n is x[n] itself — NNConv's root term
  * x_i @ root (src_1gp/layer.py:119) as one more relation, so that the layer is ONE GEMM [N, (K+1) D] x [(K+1) D, out]. */
 
+/* NNConv over continuous edge features (the protein tower of src_2gi_dti_scr/glam.py: NNConv(Cin, Cout, Linear(De, 32) -> ReLU ->
+ * Linear(32, Cin*Cout), aggr in {mean, add}) with 8 contact features per residue edge) without the per-edge weight tensor [E, Cin*Cout].
+ * With h_e = relu(W0 e_e + b0) (f32[E, 32]) the layer is out = [S | x] @ Wstack + bias, where [S | x] = f32[N, 34, Cin] holds
+ * S[n, k, :] = (mean ? 1/deg_n : 1) * sum_{e -> n} h_e[k] x[src e] for k < 32, the same with h = 1 for k = 32, and x[n] for k = 33;
+ * Wstack = f32[34*Cin, Cout] with rows k*Cin + ci = W1[ci*Cout + co, k] (k < 32), b1[ci*Cout + co] (k = 32), root[ci, co] (k = 33).
+ * W0 f32[32, De], b0 f32[32], W1 f32[Cin*Cout, 32], b1 f32[Cin*Cout], root f32[Cin, Cout] are the torch layouts of nn.0 / nn.2 / root.
+ * glam_nnconv_ec_supported: 1 for hidden = 32, 1 <= De <= 16, 1 <= Cin, Cout <= 96, else 0 (the entry points return
+ * GLAM_E_UNSUPPORTED).  glam_nnconv_ec_stack builds Wstack (one launch); glam_nnconv_ec_unstack scatters d_Wstack back into
+ * d_W1, d_b1, d_root (one launch).
+ * glam_nnconv_ec_fwd: h f32[E, 32] (16-byte aligned) is written for the backward; bias may be NULL; workspace >=
+ * glam_nnconv_ec_workspace_bytes(..., backward = 0) holds [S | x].
+ * glam_nnconv_ec_bwd (d_out f32[N, Cout]; CSR by target and its transpose, as glam_edge_wsum_bwd): recomputes [S | x] from h,
+ * writes dx f32[N, Cin] (+ addend f32[N, Cin], may be NULL: the skip connection's gradient, as glam_edge_wsum_bwd_add), d_w0, d_b0,
+ * d_wstack f32[34*Cin, Cout], d_bias f32[Cout]; workspace >= glam_nnconv_ec_workspace_bytes(..., backward = 1).  No gradient
+ * reaches edge_attr (edge data).  Exact fp32 MFMA products; the weight gradients are two-stage fixed-order sums (no atomics:
+ * bit-identical from run to run).  No host synchronisation: hipGraph-capturable. */
+int glam_nnconv_ec_supported(int De, int hidden, int Cin, int Cout);
+size_t glam_nnconv_ec_workspace_bytes(int64_t N, int64_t E, int De, int Cin, int Cout, int backward);
+int glam_nnconv_ec_stack(const float* w1, const float* b1, const float* root, int Cin, int Cout, float* wstack, void* stream);
+int glam_nnconv_ec_unstack(const float* d_wstack, int Cin, int Cout, float* d_w1, float* d_b1, float* d_root, void* stream);
+int glam_nnconv_ec_fwd(const float* x, const float* edge_attr, const int32_t* rowptr, const int32_t* src, const int32_t* eid,
+                       int64_t N, int64_t E, int De, int Cin, int Cout, const float* w0, const float* b0, const float* wstack,
+                       const float* bias, int mean, float* h, void* workspace, size_t workspace_bytes, float* out, void* stream);
+int glam_nnconv_ec_bwd(const float* d_out, const float* x, const float* edge_attr, const int32_t* rowptr, const int32_t* src,
+                       const int32_t* eid, const int32_t* colptr, const int32_t* dst, const int32_t* eid_t, int64_t N, int64_t E,
+                       int De, int Cin, int Cout, const float* wstack, const float* h, int mean, const float* addend, float* dx,
+                       float* d_w0, float* d_b0, float* d_wstack, float* d_bias, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Per-pair fusion of the two-tower models: out f32[P,2] = [max, mean] of mol[seg_i] @ pro[seg_i]^T for every pair i
  * (segments mol_ptr / pro_ptr int32[P+1]; empty segment -> 0); argmax int32[P,2] = (ligand row, residue row) of the max;

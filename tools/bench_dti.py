@@ -5,12 +5,23 @@ import torch
 from glam_amd import model, optim
 from glam_amd.data import synth_batch, synth_protein_batch
 
-_pos = [a for a in sys.argv[1:] if not a.startswith("--")]
+# --pro-block NAME: the protein tower's conv (default _GCNConv; _NNConv = the continuous-edge-feature NNConv route);
+# --alpha A: hid_dim_alpha (hidden width 15 * A; default 4, the reference's)
+_opts = {"--pro-block": "_GCNConv", "--alpha": "4"}
+_args, _pos = sys.argv[1:], []
+while _args:
+    a = _args.pop(0)
+    if a in _opts:
+        _opts[a] = _args.pop(0)
+    elif not a.startswith("--"):
+        _pos.append(a)
 B = int(_pos[0]) if len(_pos) > 0 else 32
 NORM = _pos[1] if len(_pos) > 1 else "_None"
+PRO_BLOCK, ALPHA = _opts["--pro-block"], int(_opts["--alpha"])
 dev = torch.device("cuda")
 torch.manual_seed(0)
-net = model.ArchitectureDTI(graph_norm=NORM, graph_do="_None()", end_do="_None()", pre_act="ReLU", graph_act="ReLU", flat_act="ReLU", end_act="ReLU").to(dev)
+net = model.ArchitectureDTI(graph_norm=NORM, graph_do="_None()", end_do="_None()", pre_act="ReLU", graph_act="ReLU", flat_act="ReLU", end_act="ReLU",
+                            pro_block=PRO_BLOCK, hid_dim_alpha=ALPHA).to(dev)
 mol, pro = synth_batch(B, seed=0).to(dev), synth_protein_batch(B, seed=1, n_min=200, n_max=800).to(dev)
 y = torch.randn(B, device=dev)
 opt = (optim.Adam(net.parameters(), lr=1e-3) if os.environ.get("GLAM_ADAM", "glam") == "glam"
@@ -62,5 +73,6 @@ for mode in ("eager", "hipGraph"):
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(50): step()
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / 50
-    print(json.dumps({"workload": f"ArchitectureDTI defaults (_NNConv ligand, _GCNConv protein, norm={NORM}), B={B} pairs, protein nodes={pro.x.size(0)}",
-                      "launch": mode, "ms_per_step": dt * 1e3, "pairs_per_s": B / dt}), flush=True)
+    print(json.dumps({"workload": f"ArchitectureDTI (_NNConv ligand, {PRO_BLOCK} protein, alpha={ALPHA}, norm={NORM}), B={B} pairs, protein nodes={pro.x.size(0)}",
+                      "launch": mode, "ms_per_step": dt * 1e3, "pairs_per_s": B / dt,
+                      "peak_mem_mib": torch.cuda.max_memory_allocated() / 2**20}), flush=True)

@@ -118,6 +118,8 @@ SIGNATURES = {
     "glam_loss_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "glam_adam_max_tensors": (_i32, []),
     "glam_adam_step": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp] + [ctypes.c_double] * 5 + [_vp]),
+    "glam_ranger_max_tensors": (_i32, []),
+    "glam_ranger_step": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp] + [ctypes.c_double] * 6 + [_i32, ctypes.c_double, _i32, _vp]),
     "glam_linear_narrow_supported": (_i32, [_i32, _i32]),
     "glam_linear_narrow_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "glam_linear_narrow_bwd_workspace_bytes": (_sz, [_i32, _i32]),

@@ -18,17 +18,33 @@ step sums the weight gradients of all applications of a block in one product (``
 per application: equal within fp32 rounding.  ``GraphedTrainStep.run(batches)`` goes one step further for the epoch loop: up to
 ``steps_per_graph`` CONSECUTIVE steps (one per batch, in order) are captured into one graph — every ``hipGraphLaunch`` carries a
 bubble of ≈7 µs on this stack (a 99 µs step replays in 92 µs at eight steps per launch, bench.py), and an ESOL epoch at the reference's
-batch size is 36 launches otherwise.  Requirements: an optimizer created with ``capturable=True`` (Adam/AdamW), a
+batch size is 36 launches otherwise.  Requirements: an optimizer created with ``capturable=True`` (Adam/AdamW, ``glam_amd.optim.Adam`` / ``Ranger``), a
 loss function of ``(output, batch)`` that stays on the device, and no data-dependent Python control flow in the model.
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes
+import gc
 import os
 import weakref
 
 import torch
+
+
+@contextlib.contextmanager
+def _gc_paused():
+    """No cyclic garbage collection while a stream captures.  The graph caches below sit in reference cycles (a weakref's callback
+    holds the dictionary that holds the weakref), so a dropped stepper or model frees its graphs only when the collector runs — and
+    this torch no longer collects before a capture begins.  A ``CUDAGraph`` destroyed during a capture fails in its destructor and
+    aborts the process; the collection simply waits until the capture has ended."""
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if enabled:
+            gc.enable()
 
 
 class GraphedTrainStep:
@@ -56,7 +72,11 @@ class GraphedTrainStep:
         self._lr = [None] * len(optimizer.param_groups)
         self._hyper = None
 
-    _BAKED = ("betas", "eps", "weight_decay", "amsgrad", "maximize", "momentum", "dampening", "nesterov", "alpha", "centered")
+    _BAKED = ("betas", "eps", "weight_decay", "amsgrad", "maximize", "momentum", "dampening", "nesterov", "alpha", "centered", "k",
+              "N_sma_threshhold")
+    # hyper-parameters some optimizers keep on the optimizer object rather than in the groups (glam_amd.optim.Ranger, as the
+    # reference's ranger.py reads them: Lookahead's alpha, the rectification threshold, the gradient-centralisation switches)
+    _BAKED_ATTRS = ("alpha", "k", "N_sma_threshhold", "use_gc", "gc_conv_only", "gc_loc")
 
     def _sync_hyper(self):
         for i, g in enumerate(self.optimizer.param_groups):
@@ -73,10 +93,12 @@ class GraphedTrainStep:
                     t.fill_(float(lr))
                 g["lr"] = t
         snap = tuple(tuple((k, g[k]) for k in self._BAKED if k in g) for g in self.optimizer.param_groups)
+        snap += tuple((a, getattr(self.optimizer, a)) for a in self._BAKED_ATTRS if hasattr(self.optimizer, a))
         if self._hyper is not None and snap != self._hyper:
             for st in self._state.values():   # constants of the captured optimizer launches changed: capture again
                 st[2] = st[3] = None
             self._multi.clear()
+            self._pool = None                 # (its last graph is gone with them: the allocator no longer knows the handle)
         self._hyper = snap
 
     def _step(self, batch):
@@ -112,7 +134,7 @@ class GraphedTrainStep:
         if st[2] is None:                                 # second visit: capture, then fall through to the replay
             graph = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
-            with torch.cuda.graph(graph, pool=self._pool):
+            with _gc_paused(), torch.cuda.graph(graph, pool=self._pool):
                 st[3] = self._step(batch)
             if self._pool is None:
                 self._pool = graph.pool()                 # all graphs share one memory pool: they never run concurrently
@@ -143,7 +165,7 @@ class GraphedTrainStep:
             refs = [weakref.ref(b, lambda _r, k=key, d=self._multi: d.pop(k, None)) for b in chunk]
             graph = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
-            with torch.cuda.graph(graph, pool=self._pool):
+            with _gc_paused(), torch.cuda.graph(graph, pool=self._pool):
                 outs = [self._step(b) for b in chunk]
             if self._pool is None:
                 self._pool = graph.pool()
@@ -182,7 +204,7 @@ class GraphedForward:
         if st[1] is None:
             graph = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
-            with torch.cuda.graph(graph, pool=self._pool), no_graphed_call():
+            with _gc_paused(), torch.cuda.graph(graph, pool=self._pool), no_graphed_call():
                 st[2] = self.model(*batches)
             if self._pool is None:
                 self._pool = graph.pool()
@@ -448,7 +470,7 @@ class GraphedCallable:
         torch.cuda.synchronize()
         fwd = torch.cuda.CUDAGraph()
         if not grad:
-            with torch.cuda.graph(fwd), no_graphed_call():
+            with _gc_paused(), torch.cuda.graph(fwd), no_graphed_call():
                 st.out = eager_forward(*st.static)
             st.fwd = fwd
             return
@@ -459,13 +481,13 @@ class GraphedCallable:
         # join that stream, and the runtime crashes at capture end (tools/repro_graphed_call.py, V=4 / V=5).
         names = [n for n, p in module.named_parameters() if p.requires_grad]
         proxies = tuple(p.detach().requires_grad_() for p in params)
-        with torch.cuda.graph(fwd), no_graphed_call():
+        with _gc_paused(), torch.cuda.graph(fwd), no_graphed_call():
             out = torch.func.functional_call(module, dict(zip(names, proxies)), tuple(st.static))
         st.fwd, st.out = fwd, out
         if out.requires_grad:
             st.gout = torch.zeros_like(out)
             bwd = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(bwd, pool=fwd.pool()):
+            with _gc_paused(), torch.cuda.graph(bwd, pool=fwd.pool()):
                 grads = torch.autograd.grad(out, proxies, st.gout, allow_unused=True)
             st.bwd, st.params, st.grads = bwd, params, tuple(grads)
 

@@ -868,6 +868,20 @@ int glam_adam_max_tensors(void);
 int glam_adam_step(const uint64_t* table, const int64_t* numel, int n, float* step, unsigned* ticket, const float* lr_dev, double lr,
                    double beta1, double beta2, double eps, double weight_decay, void* stream);
 
+/* One Ranger step (RAdam + Lookahead + gradient centralisation; reference src_1gp/ranger.py:117-205, the other optimizer of the
+ * reference's search, trainer.py:45-48) over n parameter tensors in one launch per 40 tensors.  table: HOST array [n][5] of device
+ * addresses {param, grad, exp_avg, exp_avg_sq, slow_buffer} (f32, numel[i] elements each, contiguous); row[i]: the row length
+ * numel / size(0) of a tensor whose gradient is centralised (a mean over dimensions 1..n per index of dimension 0), 0 for one that is
+ * not.  step / ticket / lr_dev as for glam_adam_step (the step count of the launch is *step + 1, read on the device, and decides the
+ * rectification branch and the Lookahead sync `s % k == 0`).  gc_loc != 0 centralises the gradient before the moments and writes it
+ * back to grad (as the reference leaves p.grad); gc_loc == 0 centralises the update direction instead.  In the un-rectified branch
+ * the direction is exp_avg itself, so weight decay and late centralisation also land in exp_avg (as in the reference).  In place:
+ * param, exp_avg, exp_avg_sq, slow_buffer, and grad when it is centralised with gc_loc != 0. */
+int glam_ranger_max_tensors(void);
+int glam_ranger_step(const uint64_t* table, const int64_t* numel, const int64_t* row, int n, float* step, unsigned* ticket,
+                     const float* lr_dev, double lr, double beta1, double beta2, double eps, double weight_decay, double alpha, int k,
+                     double n_sma_threshold, int gc_loc, void* stream);
+
 /* The training step's loss, value and gradient in one launch (mean reduction):
  *   kind 0  squared error          — `self.criterion(output, y_true)` with nn.MSELoss, src_1gp/trainer.py:296 / loss.py:42
  *   kind 1  BCE with logits        — nn.BCEWithLogitsLoss, loss.py:48

@@ -1,4 +1,5 @@
-"""Epoch time of the reference-style training loop (fixed batch order, Adam, MSE; src_1gp/trainer.py:286-304):
+"""Epoch time of the reference-style training loop (fixed batch order, Adam — or Ranger with GLAM_OPTIM=ranger — MSE;
+src_1gp/trainer.py:286-304):
   eager      the loop as written, the model's graphed-callable route switched off (model.graphed_call = False)
   unchanged  the loop as written — ``model(batch)`` replays hipGraphs by itself (glam_amd.graphs.GraphedCallable), cached batch objects
   unch+fresh the loop as written on a FRESH device copy of every batch in every epoch (what trainer.py:294 hands the model: recognised
@@ -30,7 +31,8 @@ def fresh(b):
 for graphed in (False, "unchanged", "unch+fresh", True, "run"):
     net = copy.deepcopy(net0)
     net.graphed_call = graphed in ("unchanged", "unch+fresh")
-    opt = (optim.Adam(net.parameters(), lr=1e-3) if os.environ.get("GLAM_ADAM", "glam") == "glam"
+    opt = (optim.Ranger(net.parameters(), lr=1e-3) if os.environ.get("GLAM_OPTIM") == "ranger"
+           else optim.Adam(net.parameters(), lr=1e-3) if os.environ.get("GLAM_ADAM", "glam") == "glam"
            else torch.optim.Adam(net.parameters(), lr=1e-3, capturable=True, fused=True))
     loader = DataLoader(mols, batch_size=B, device=dev)
     stepper = GraphedTrainStep(net, opt, loss_fn)

@@ -1031,7 +1031,7 @@ extern "C" int glam_edge_wsum_fwd(const float* x, const float* w, const int32_t*
     GLAM_REQUIRE(x && rowptr && out && (E == 0 || (w && src && eid)), "glam_edge_wsum_fwd: null pointer");
     const dim3 grid(grid_for(N * D, kBlock)), block(kBlock);
     hipStream_t s = (hipStream_t)stream;
-    if (K == 1 && (D & 3) == 0)
+    if (K == 1 && (D & 3) == 0 && aligned16(x) && aligned16(out))
         hipLaunchKernelGGL(k_edge_wsum1_fwd_v4, dim3(grid_for(N * (D / 4), kBlock)), block, 0, s, x, w, rowptr, src, eid, (int)N, D, mean, out);
     else if (K == 1) hipLaunchKernelGGL(k_edge_wsum_fwd<1>, grid, block, 0, s, x, w, rowptr, src, eid, (int)N, D, mean, out);
     else if ((D & 3) == 0 && aligned16(x) && aligned16(w) && aligned16(out)) {
@@ -1055,7 +1055,7 @@ extern "C" int glam_edge_wsum_bwd(const float* d_out, const float* w, const int3
     GLAM_REQUIRE(d_out && colptr && rowptr && dx && (E == 0 || (w && dst && eid_t)), "glam_edge_wsum_bwd: null pointer");
     const dim3 grid(grid_for(N * D, kBlock)), block(kBlock);
     hipStream_t s = (hipStream_t)stream;
-    if (K == 1 && (D & 3) == 0)
+    if (K == 1 && (D & 3) == 0 && aligned16(d_out) && aligned16(dx))
         hipLaunchKernelGGL(k_edge_wsum1_bwd_v4, dim3(grid_for(N * (D / 4), kBlock)), block, 0, s, d_out, w, colptr, dst, eid_t, rowptr, (int)N, D, mean, dx);
     else if (K == 1) hipLaunchKernelGGL(k_edge_wsum_bwd<1>, grid, block, 0, s, d_out, w, colptr, dst, eid_t, rowptr, (int)N, D, mean, dx);
     else if ((D & 3) == 0 && aligned16(d_out) && aligned16(w) && aligned16(dx)) {

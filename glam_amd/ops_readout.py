@@ -413,9 +413,10 @@ class _EdgeWeightedSum(torch.autograd.Function):
         colptr, dst, eid_t = gi.transpose()
         dx = torch.empty(N, D, dtype=torch.float32, device=d_out.device)
         lib = _lib.load()
-        if d_alias is not None and K in (4, 8) and D % 4 == 0:
-            # the skip connection's gradient joins the sums in this launch (no add launch of the autograd engine)
-            d_alias = f32c(d_alias, "d_identity")
+        d_alias = None if d_alias is None else f32c(d_alias, "d_identity")
+        if d_alias is not None and K in (4, 8) and D % 4 == 0 and all(t.data_ptr() % 16 == 0 for t in (d_out, w, d_alias)):
+            # the skip connection's gradient joins the sums in this launch (no add launch of the autograd engine); the launch
+            # exists for 16-byte aligned operands only (glam_edge_wsum_bwd_add refuses the rest)
             check(lib.glam_edge_wsum_bwd_add(ptr(d_out), ptr(w), ptr(colptr), ptr(dst), ptr(eid_t), ptr(gi.rowptr), N, E, D, K, mean, self_slot,
                                              ptr(d_alias), ptr(dx), stream()), "glam_edge_wsum_bwd_add")
             return dx, None, None, None, None, None

@@ -38,8 +38,20 @@ def scatter(src, index, dim_size, reduce="sum"):
         cnt = src.new_zeros(dim_size).scatter_add_(0, index, src.new_ones(index.shape)).clamp_(min=1)
         return tot / cnt.view((-1,) + (1,) * (src.dim() - 1))
     if reduce == "max":
-        return src.new_zeros(shape).scatter_reduce(0, idx, src, reduce="amax", include_self=False)
+        return _scatter_max(src, index, idx, shape)
     raise ValueError(reduce)
+
+
+def _scatter_max(src, index, idx, shape):
+    """``torch_scatter.scatter_max(...)[0]``: the forward of ``scatter_reduce("amax")``, but the gradient of each output goes to ONE
+    row, the lowest-index maximal one (``scatter_max``'s arg row), not split evenly over tied rows as ``amax``'s gradient is."""
+    with torch.no_grad():
+        m = src.new_zeros(shape).scatter_reduce(0, idx, src, reduce="amax", include_self=False)
+        rows = torch.arange(src.size(0), device=src.device).view((-1,) + (1,) * (src.dim() - 1)).expand_as(src)
+        cand = torch.where(src == m.index_select(0, index), rows, src.size(0))
+        arg = torch.full(shape, src.size(0), dtype=torch.long, device=src.device).scatter_reduce(0, idx, cand, reduce="amin")
+    # row N is a zero row: an empty segment reads it (-> 0, torch_scatter convention) and sends its gradient nowhere
+    return torch.cat([src, src.new_zeros((1,) + tuple(src.shape[1:]))]).gather(0, arg)
 
 
 def segment_softmax(src, index, num_segments):

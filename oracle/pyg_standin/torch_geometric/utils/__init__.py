@@ -19,8 +19,15 @@ def scatter(src, index, dim=0, dim_size=None, reduce="sum"):
         cnt = cnt.clamp_(min=1).view((-1,) + (1,) * (src.dim() - 1))
         return tot / cnt
     if reduce == "max":
-        out = src.new_zeros(out_shape)
-        return out.scatter_reduce(0, idx, src, reduce="amax", include_self=False)
+        # torch_scatter.scatter_max: the gradient goes to the lowest-index maximal row only (scatter_reduce("amax") would split
+        # it evenly over tied rows); row N is a zero row that empty segments read
+        with torch.no_grad():
+            m = src.new_zeros(out_shape).scatter_reduce(0, idx, src, reduce="amax", include_self=False)
+            rows = torch.arange(src.size(0), device=src.device).view((-1,) + (1,) * (src.dim() - 1)).expand_as(src)
+            cand = torch.where(src == m.index_select(0, index), rows, src.size(0))
+            arg = torch.full(out_shape, src.size(0), dtype=torch.long, device=src.device)
+            arg = arg.scatter_reduce(0, idx, cand, reduce="amin")
+        return torch.cat([src, src.new_zeros((1,) + tuple(src.shape[1:]))]).gather(0, arg)
     if reduce == "min":
         out = src.new_zeros(out_shape)
         return out.scatter_reduce(0, idx, src, reduce="amin", include_self=False)

@@ -1437,18 +1437,27 @@ def test_triplet_message_more_than_four_heads(device, C, H):
                        ["x"] + [n for n, _ in conv.named_parameters()])
 
 
-@pytest.mark.parametrize("alpha,act,block", [(1, "ReLU", "_TripletMessage"), (2, "ReLU", "_TripletMessage"), (3, "CELU", "_TripletMessage"),
-                                             (6, "ReLU", "_TripletMessage"), (3, "ReLU", "_NNConv"), (2, "LeakyReLU", "_TripletMessageLight")])
-def test_architecture_odd_widths_vs_oracle(device, alpha, act, block):
+_ODD_WIDTH_CASES = [
+    (1, "ReLU", "_TripletMessage", "GlobalPool5"), (2, "ReLU", "_TripletMessage", "GlobalPool5"), (3, "CELU", "_TripletMessage", "GlobalPool5"),
+    (6, "ReLU", "_TripletMessage", "GlobalPool5"), (3, "ReLU", "_NNConv", "GlobalPool5"), (2, "LeakyReLU", "_TripletMessageLight", "GlobalPool5"),
+    (1, "ReLU", "_TripletMessage", "GlobalLAPool"), (3, "CELU", "_TripletMessage", "GlobalLAPool"), (6, "ReLU", "_NNConv", "GlobalLAPool"),
+    (1, "ReLU", "_GCNConv", "GlobalPool5"), (6, "CELU", "_GCNConv", "GlobalPool5"),
+    (1, "LeakyReLU", "_GATConv", "GlobalPool5"), (6, "ReLU", "_GATConv", "GlobalPool5")]
+
+
+# (the GlobalPool5 cases keep their ids: alpha-act-block)
+@pytest.mark.parametrize("alpha,act,block,readout", [pytest.param(*c, id="-".join(map(str, c[:3] if c[3] == "GlobalPool5" else c)))
+                                                     for c in _ODD_WIDTH_CASES])
+def test_architecture_odd_widths_vs_oracle(device, alpha, act, block, readout):
     """hid_dim_alpha of the search space (glam.py:60) whose hidden width is not a multiple of 4: features travel between the
     conv and the GRU step as zero-padded rows handed on by reference (ops.pad_cols / slice_cols); outputs and every parameter
     gradient against the oracle's full model."""
     torch.manual_seed(40 + alpha)
     b = synth_batch(24, seed=alpha)
-    net = model.Architecture(hid_dim_alpha=alpha, e_dim=64, out_dim=2, message_steps=3, mol_block=block, mol_readout="GlobalPool5",
+    net = model.Architecture(hid_dim_alpha=alpha, e_dim=64, out_dim=2, message_steps=3, mol_block=block, mol_readout=readout,
                              graph_norm="_None", pre_act=act, graph_act=act, flat_act=act, graph_do="_None()", end_do="_None()").eval()
     sd = {k: v.detach().clone().requires_grad_(True) for k, v in net.state_dict().items()}
-    ref = O.architecture(sd, b, b.num_graphs, message_steps=3, mol_block=block, mol_readout="GlobalPool5", graph_norm="_None",
+    ref = O.architecture(sd, b, b.num_graphs, message_steps=3, mol_block=block, mol_readout=readout, graph_norm="_None",
                          pre_act=act, graph_act=act, flat_act=act)
     cot = torch.randn(ref.shape)
     names = [n for n, _ in net.named_parameters()]
@@ -1460,10 +1469,10 @@ def test_architecture_odd_widths_vs_oracle(device, alpha, act, block):
     def run(dt):
         sd_ = {k: v.to(dt).clone().requires_grad_(True) for k, v in net_cpu_sd.items()}
         bb = type(b)(b.x.to(dt), b.edge_index, b.edge_attr.to(dt), batch=b.batch)
-        o = O.architecture(sd_, bb, b.num_graphs, message_steps=3, mol_block=block, mol_readout="GlobalPool5", graph_norm="_None",
+        o = O.architecture(sd_, bb, b.num_graphs, message_steps=3, mol_block=block, mol_readout=readout, graph_norm="_None",
                            pre_act=act, graph_act=act, flat_act=act)
         return o.detach(), _grads(o, cot.to(dt), [sd_[n] for n in names])
-    assert_twin_parity(run, out, _grads(out, cot.to(device), [p for _, p in net.named_parameters()]), "odd width", names)
+    assert_twin_parity(run, out, _grads(out, cot.to(device), [p for _, p in net.named_parameters()]), f"odd width {readout}", names)
 
 
 def test_padded_views_are_not_trusted_after_inplace_writes(device):

@@ -116,6 +116,11 @@ SIGNATURES = {
     "glam_loss_workspace_bytes": (_sz, []),
     "glam_loss_fwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "glam_loss_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "glam_metrics_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "glam_metrics_binary": (_i32, [_vp, _vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, ctypes.c_double, ctypes.c_double,
+                                   ctypes.POINTER(ctypes.c_double), _i32, _vp, _sz, _vp, _vp]),
+    "glam_metrics_regression": (_i32, [_vp, _vp, _i32, _i64, _vp, _sz, _vp, _vp]),
+    "glam_metrics_multiclass": (_i32, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp, _sz, _vp, _vp]),
     "glam_adam_max_tensors": (_i32, []),
     "glam_adam_step": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp] + [ctypes.c_double] * 5 + [_vp]),
     "glam_ranger_max_tensors": (_i32, []),

@@ -896,6 +896,39 @@ int glam_loss_fwd(const float* pred, const float* target, int64_t n, int kind, i
                   void* ws, size_t ws_bytes, unsigned* ticket, void* stream);
 int glam_loss_bwd(const float* grad, const float* inv_count, const float* g_up, int64_t n, float* d_pred, void* stream);
 
+/* Evaluation metrics of the reference's trainers, scored on the device (reference src_1gp/metrics.py, src_2gi_ddi/utils.py; the
+ * trainers call them on the validation split after every epoch, trainer.py:79-98).  Every order-based metric comes from per-sample
+ * counts over the samples of the same task (O(n^2) pair steps per task, no sort); integer counts and fp64 sums in a fixed order, so a
+ * call is bit-identical run to run.  Inputs are device arrays; key_dtype / dtype: 0 = f32, 1 = f64 keys (scores, targets);
+ * label_dtype: 0 = f32, 1 = f64 labels and predictions.  n < GLAM_METRICS_MAX_N per task (int32 counts).  ws >=
+ * glam_metrics_workspace_bytes(n, tasks, n_class) (n_class = 0 for the binary / regression forms; 0 = arguments out of range);
+ * record: device buffer of GLAM_METRICS_RECORD_BYTES = int64 i[16] then f64 d[16], written by the call's last launch.  Two launches
+ * per call.  The bad flag reports a label outside the allowed set or a non-finite key (the reference's ValueError).
+ *
+ * glam_metrics_binary — roc_auc_score / precision_recall_curve + auc / accuracy / precision / recall / f1 of binary_metrics
+ * (metrics.py:16-29), binary_metrics_multi_target_nan (metrics.py:32-56; masked = 1: label -1 = missing), screening_metrics,
+ * bedroc_score and enrichment_factor_single (metrics.py:102-167).  score, label, pred: [n, tasks] row-major; pred_mode 0: pred holds
+ * 0/1 predictions, 1: score >= threshold, 2: score > threshold (pred unused); alpha: BEDROC's; pct_host: HOST array of n_pct <= 5
+ * EF fractions.  Ties of equal scores rank in index order (the reference's unstable argsort leaves that order undefined).
+ * Record: i = {kept tasks, skipped tasks (one class only), bad, P, N, tp, fp, tn, fn (task 0), EF hits [5] (task 0),
+ * 2 x AUC numerator (task 0), -}, d = {sum over kept tasks of auc, acc, precision, recall (binary averaging), PR-AUC (task 0),
+ * sum of exp(-alpha rank / n) over the positives (task 0)}.
+ * glam_metrics_regression — cal_ci + mean_squared_error + r2_score of regression_metrics (metrics.py:59-90, and
+ * src_2gi_dti_scr/utils.py:109-141).  y, f: [n].  Record: i = {pairs (y_j < y_i), of those f_j < f_i, of those f_j == f_i, bad},
+ * d = {sum (y - f)^2, sum (y - mean y)^2, sum y}.
+ * glam_metrics_multiclass — multi_class_metrics (src_2gi_ddi/utils.py:138-151): pred = the first argmax of score [n, n_class] (score
+ * may be null when pred is given), label / pred integral in [0, n_class), n_class <= 4096.  Record: i = {correct rows, classes seen
+ * (in labels or predictions), bad, n}, d = {sums over the classes seen of precision, recall, F1}. */
+#define GLAM_METRICS_RECORD_BYTES 256
+#define GLAM_METRICS_MAX_N 2147483647LL
+size_t glam_metrics_workspace_bytes(int64_t n, int64_t tasks, int n_class);
+int glam_metrics_binary(const void* score, const void* label, const void* pred, int key_dtype, int label_dtype, int64_t n, int64_t tasks,
+                        int masked, int pred_mode, double threshold, double alpha, const double* pct_host, int n_pct, void* ws,
+                        size_t ws_bytes, void* record, void* stream);
+int glam_metrics_regression(const void* y, const void* f, int dtype, int64_t n, void* ws, size_t ws_bytes, void* record, void* stream);
+int glam_metrics_multiclass(const void* score, const void* label, const void* pred, int key_dtype, int label_dtype, int64_t n,
+                            int n_class, void* ws, size_t ws_bytes, void* record, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

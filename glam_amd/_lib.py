@@ -116,6 +116,8 @@ SIGNATURES = {
     "glam_loss_workspace_bytes": (_sz, []),
     "glam_loss_fwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "glam_loss_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "glam_ce_loss_max_classes": (_i32, []),
+    "glam_ce_loss_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "glam_metrics_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "glam_metrics_binary": (_i32, [_vp, _vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, ctypes.c_double, ctypes.c_double,
                                    ctypes.POINTER(ctypes.c_double), _i32, _vp, _sz, _vp, _vp]),

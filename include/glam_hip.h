@@ -885,6 +885,9 @@ int glam_ranger_step(const uint64_t* table, const int64_t* numel, const int64_t*
 /* The training step's loss, value and gradient in one launch (mean reduction):
  *   kind 0  squared error          — `self.criterion(output, y_true)` with nn.MSELoss, src_1gp/trainer.py:296 / loss.py:42
  *   kind 1  BCE with logits        — nn.BCEWithLogitsLoss, loss.py:48
+ *   kind 2  absolute error         — nn.L1Loss ('mae'), gradient sign(d) with sign(0) = 0
+ *   kind 3  smooth L1, beta = 1    — nn.SmoothL1Loss ('huber', 'smae')
+ *   kind 4  BCE on probabilities   — nn.BCELoss ('bce'): logs clamped at -100, gradient (x - y) / max(x (1 - x), 1e-12)
  *   masked != 0: the mean runs over the elements with target >= 0 only — `criterion(y_score[y_true >= 0], y_true[y_true >= 0])`,
  *   trainer.py:244-245 (labels of -1 are missing, dataset.py:138), without the boolean indexing (not capturable in a hipGraph).
  * pred, target: f32[n]; loss, inv_count: f32[1] (the mean and 1 / count; count = 0 gives nan like the reference's empty mean);
@@ -895,6 +898,21 @@ size_t glam_loss_workspace_bytes(void);
 int glam_loss_fwd(const float* pred, const float* target, int64_t n, int kind, int masked, float* loss, float* inv_count, float* grad,
                   void* ws, size_t ws_bytes, unsigned* ticket, void* stream);
 int glam_loss_bwd(const float* grad, const float* inv_count, const float* g_up, int64_t n, float* d_pred, void* stream);
+
+/* The cross-entropy family in one launch: logits x: f32[B, C] (contiguous), labels y: int64[B], weight: f32[C] or NULL.
+ *   focal 0  nn.CrossEntropyLoss(weight, ignore_index): mean of w[y_i] ce_i over the rows with y_i != ignore_index, divided by the
+ *            sum of their w[y_i] (nan when every row is ignored, as in torch; inv_count is then 0, torch's zero gradient)
+ *   focal 1  the reference's FocalLoss(alpha, gamma) (src_1gp/loss.py:3-16): mean over all B rows of alpha (1 - pt)^gamma ce_i,
+ *            pt = exp(-ce_i), ignored rows 0; gamma = 0 or gamma >= 1 only (other exponents make torch's own gradient 0 * inf on
+ *            ignored rows), no weight.
+ * A label outside [0, C) that is not ignore_index is never used as an index: the loss and that row's gradient are nan (torch raises
+ * a device-side assert instead).  loss, inv_count, grad [B, C], ws and ticket as for glam_loss_fwd (ws / ticket are needed once
+ * B exceeds one block's rows); the backward is glam_loss_bwd with n = B * C.  1 <= C <= glam_ce_loss_max_classes().  Fixed
+ * summation order (per row thread-sequential, then a lane butterfly; over rows as glam_loss_fwd): bit-reproducible. */
+int glam_ce_loss_max_classes(void);
+int glam_ce_loss_fwd(const float* x, const int64_t* y, const float* weight, int64_t B, int C, int64_t ignore_index, int focal,
+                     float alpha, float gamma, float* loss, float* inv_count, float* grad, void* ws, size_t ws_bytes, unsigned* ticket,
+                     void* stream);
 
 /* Evaluation metrics of the reference's trainers, scored on the device (reference src_1gp/metrics.py, src_2gi_ddi/utils.py; the
  * trainers call them on the validation split after every epoch, trainer.py:79-98).  Every order-based metric comes from per-sample

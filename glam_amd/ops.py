@@ -13,6 +13,7 @@ from __future__ import annotations
 import collections
 import contextlib
 import ctypes
+import math
 import os
 import weakref
 
@@ -563,6 +564,12 @@ def light_aggregate(xw, a_ij, edge_attr, M, gi, Cp, slope=0.2):
     return _TripletAggregate.apply(xw, a_ij, edge_attr, None, M, gi, 1, Cp, edge_attr.size(1), False, slope)
 
 
+def _triplet_shapes(wn, we, att, H):
+    """The layout of a TripletMessage's flat parameter gradients: its five parameters in parameter order."""
+    C = wn.size(0)
+    return (wn.shape, we.shape, att.shape, (H * C, C), (C,))
+
+
 def fused_layer_supported(C, heads, De):
     """Shapes covered by the dense MFMA kernels behind ``glam_triplet_layer_*`` (C <= 60 at 3 heads)."""
     Cp = (C + 3) // 4 * 4
@@ -580,33 +587,88 @@ def fused_layer_supported(C, heads, De):
 GRAD_CARRY = True            # (module switches like this one are attributes, not environment variables: the tests flip them in place)
 
 
+def _flat_views(flat, shapes):
+    """Consecutive views of ``flat`` with the given shapes: the pieces of a flat gradient buffer, in memory order."""
+    return [t.view(s) for t, s in zip(flat.split([math.prod(s) for s in shapes]), shapes)]
+
+
+def _flat_grads(shapes, device):
+    """An uninitialised flat fp32 gradient buffer laid out as ``shapes`` and its views (``_flat_views``)."""
+    flat = torch.empty(sum(math.prod(s) for s in shapes), dtype=torch.float32, device=device)
+    return flat, _flat_views(flat, shapes)
+
+
 class _ParamBundle(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, split, total, *params):
-        ctx.split = split
-        return torch.empty(total, dtype=torch.float32, device=params[0].device)
+    def forward(ctx, shapes, order, *params):
+        ctx.shapes, ctx.order = shapes, order
+        return torch.empty(sum(math.prod(s) for s in shapes), dtype=torch.float32, device=params[0].device)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_flat):
-        return (None, None) + tuple(ctx.split(d_flat))
+        views = _flat_views(d_flat, ctx.shapes)
+        return (None, None) + tuple(views[i] for i in ctx.order)
 
 
-def _carry_for(key, params, total, split):
-    """The scope's carry tensor for this parameter set (created on the block's first application of the pass), or None
-    when gradients are off / there is no scope."""
-    scope = _SCOPE
-    if scope is None or not GRAD_CARRY or not torch.is_grad_enabled() or not any(p.requires_grad for p in params):
+class _Carry:
+    """One application's end of the gradient carry of a block's parameters ``params`` under the scope key ``key``.  ``shapes``: the
+    pieces of the flat gradient buffer in memory order; ``order[i]``: the piece that holds the gradient of ``params[i]`` (default:
+    parameter order).  ``tensor`` is the carry to hand to the node, None when there is no scope, gradients are off or no parameter
+    requires one; ``first`` marks the block's first application of the pass, whose backward runs LAST."""
+
+    def __init__(self, key, params, shapes, order=None):
+        self.key, self.owner, self.scope = key, params[0], _SCOPE
+        hit = self.scope.fwd.get(key) if self.scope is not None else None
+        self.first = not (hit is not None and hit[0] is self.owner)
+        self.tensor = None
+        if self.scope is not None and GRAD_CARRY and torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            order = tuple(range(len(params))) if order is None else order
+            self.tensor = _ParamBundle.apply(shapes, order, *params) if self.first else hit[1]
+
+    def store(self, carry):
+        """The node's carry output, for the block's next application."""
+        if carry is not None:
+            self.scope.fwd[self.key] = (self.owner, carry)
+
+
+def _carried(flat, d_carry, summed=False):
+    """What a node hands back through the carry: its flat parameter gradients plus those of the later applications (``d_carry``),
+    unless the reduction of its weight-gradient product already added them (``summed``)."""
+    return flat if (summed or d_carry is None) else flat.add_(d_carry)
+
+
+# ---- parked weight-gradient operand sets ---------------------------------------------------------------------------------
+# With GRU_WGRAD_BATCH the weight gradients of ALL applications of a block come from one product over their operands: every
+# application but the first parks its operand set in the scope and hands the carry on untouched; the first one (its backward runs
+# last: everything later in the forward depends on its outputs) multiplies the parked sets together, three per launch, chaining each
+# launch's result into the next as its addend.  3 weight-gradient launches + 3 reductions -> 1 + 1 per training step at message_steps = 3.
+_WGRAD_BATCH_MIN_ROWS = 512     # (a wave's row range must fit into one operand set: glam_wgrad_gemm_pair_split_seg)
+
+
+def _parks(scope, N):
+    """True when a carried node of ``N`` rows parks its weight-gradient operands (``_park``) instead of multiplying them itself."""
+    return scope is not None and GRU_WGRAD_BATCH and N >= _WGRAD_BATCH_MIN_ROWS
+
+
+def _park(scope, kind, owner, first, operands, compat=None):
+    """Parks ``operands`` (unless None) with the sets of the block's other applications.  Returns None on every application but the
+    first: the caller returns its pass-through gradients.  On the first one it returns all parked sets as the groups to launch: at
+    most three sets each, of one ``compat`` key, in parking order.  The list is emptied before anything is launched: a set left
+    behind by an interrupted backward would be counted again by a retried one (``retain_graph=True``)."""
+    parked = scope.bwd.setdefault(("parked", kind, id(owner)), (owner, []))[1]
+    if operands is not None:
+        parked.append((compat, operands))
+    if not first:
         return None
-    hit = scope.fwd.get(key)
-    if hit is not None and hit[0] is params[0]:
-        return hit[1]
-    return _ParamBundle.apply(split, total, *params)
-
-
-def _carry_store(key, owner, carry):
-    if _SCOPE is not None and carry is not None:
-        _SCOPE.fwd[key] = (owner, carry)
+    sets = list(parked)
+    parked.clear()
+    groups = []
+    while sets:
+        grp = [s for s in sets if s[0] == sets[0][0]][:3]
+        sets = [s for s in sets if all(s is not g for g in grp)]
+        groups.append([s[1] for s in grp])
+    return groups
 
 
 # ---- staged parameter images across passes -------------------------------------------------------------------------------
@@ -731,91 +793,75 @@ class _TripletLayer(torch.autograd.Function):
         return res if len(res) > 1 else out
 
     @staticmethod
-    def _flush_parked(parked, N, C, H, De, Cp, Dp, wn, we, att, carry_in):
-        """Both weight-gradient products + k_param_grads over the parked operand sets (three per launch pair), chained through the
-        gradient carry.  The list is emptied whatever happens: a set left behind by an interrupted backward would be counted again by
-        a retried one (``retain_graph=True``)."""
-        lib, dev = _lib.load(), wn.device
-        sizes = [wn.numel(), we.numel(), att.numel(), H * C * C, C]
-        sets = list(parked)
-        parked.clear()
-        vp = ctypes.c_void_p
-        while sets:
-            grp, sets = sets[:3], sets[3:]
-            n = len(grp)
-            out = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-            o = [t.view(sh) for t, sh in zip(out.split(sizes), (wn.shape, we.shape, att.shape, (H * C, C), (C,)))]
-            c = carry_in.split(sizes) if carry_in is not None else (None,) * 5
-            ws2 = torch.empty(2 * lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
-            infos = (ctypes.c_int64 * (4 * n))(*[v for t in grp for v in t[1]])
-            arr = lambda i: (vp * n)(*[t[i].data_ptr() for t in grp])
-            check(lib.glam_triplet_layer_param_grads_sets(n, arr(0), infos, arr(2), arr(3), arr(4), N, C, H, De, Cp, Dp, ptr(wn), ptr(we),
-                                                          ptr(att), ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(o[3]), ptr(o[4]), ptr(c[0]), ptr(c[1]),
-                                                          ptr(c[2]), ptr(c[3]), ptr(c[4]), ptr(ws2), ws2.numel(), stream()),
-                  "glam_triplet_layer_param_grads_sets")
-            carry_in = out
-        return carry_in
-
-    @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_out, *more):
         d_alias = more[0] if ctx.aliased else None
         d_carry = more[-1] if ctx.carried else None
-        if d_out is None:                    # the layer's output was not used: only the skip connection / the carry pass through
-            scope = getattr(ctx, "scope", None)
-            parked = scope.bwd.get(("triplet-parked", id(ctx.saved_tensors[2]))) if (scope is not None and ctx.first_app) else None
-            if parked and parked[1]:         # later applications parked their operand sets for this one to multiply: do it without a set of our own
-                x_p, ea_p, wn, we, att = ctx.saved_tensors[:5]
-                C, H, De, Cp, Dp, _slope = ctx.dims
-                d_carry = _TripletLayer._flush_parked(parked[1], ctx.gi.N, C, H, De, Cp, Dp, wn, we, att,
-                                                      f32c(d_carry, "d_carry") if d_carry is not None else None)
-            return (d_alias,) + (None,) * 9 + (d_carry, None, None, None)
         x_p, ea_p, wn, we, att, staged, xw, a_ij, aggr, stats = ctx.saved_tensors
         C, H, De, Cp, Dp, slope = ctx.dims
-        gi = ctx.gi
+        gi, scope = ctx.gi, ctx.scope
         N, E = gi.N, gi.E
         lib, dev = _lib.load(), x_p.device
-        d_out = f32c(d_out, "d_out")
-        colptr, dst, eid_t = gi.transpose()
-        f = dict(dtype=torch.float32, device=dev)
-        d_x = torch.empty_like(x_p)
-        d_ea = torch.zeros_like(ea_p) if ctx.needs_input_grad[1] else None
-        ws = torch.empty(lib.glam_triplet_layer_bwd_workspace_bytes(N, E, H, Cp, Dp), dtype=torch.uint8, device=dev)
+        groups = None
+        if d_out is None:
+            # the layer's output was not used: only the skip connection / the carry pass through — on the first application together
+            # with the parameter gradients of the sets that the later applications parked (below: without a set of its own)
+            groups = _park(scope, "triplet", wn, True, None) if (scope is not None and ctx.first_app) else None
+            if not groups:
+                return (d_alias,) + (None,) * 9 + (d_carry, None, None, None)
+            d_x, d_ea = d_alias, None
+        else:
+            d_out = f32c(d_out, "d_out")
+            colptr, dst, eid_t = gi.transpose()
+            d_x = torch.empty_like(x_p)
+            d_ea = torch.zeros_like(ea_p) if ctx.needs_input_grad[1] else None
+            ws = torch.empty(lib.glam_triplet_layer_bwd_workspace_bytes(N, E, H, Cp, Dp), dtype=torch.uint8, device=dev)
+            # molecular graphs with one-hot bond features: B1 and B2 + d_x warp-specialised over the ELL records of both directions
+            ell_t = gi.ell_t() if (d_ea is None and _ws_route(lib, N, H, Cp, Dp, ea_p)) else None
+            ell_f = gi.ell() if ell_t is not None else None          # (by target: what the forward used)
+            if ctx.carried and d_ea is None and _parks(scope, N):
+                # The parameter gradients of ALL applications of the layer from one launch pair (see _park): every application runs the
+                # DATA half of its backward (d_x) and parks its operands — its workspace holds d_xw, d_a and the block partials of
+                # d_W_edge / d_M —; the first application runs both weight-gradient products over the parked sets and k_param_grads ONCE
+                # (glam_triplet_layer_param_grads_sets).  3 x (k_wgrad + k_param_grads) -> 1 + 1 per training step at message_steps = 3.
+                in_kernel = d_alias is not None and ell_t is not None and _lib.route_enabled("x3")   # (warp-specialised route only)
+                addend = f32c(d_alias, "d_identity") if in_kernel else None
+                info = (ctypes.c_int64 * 4)()
+                check(lib.glam_triplet_layer_bwd_data_ell(ptr(x_p), ptr(ea_p), ptr(staged), ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats), ptr(d_out),
+                                                          ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t), N, E, C, H, De,
+                                                          Cp, Dp, slope, ptr(d_x), ptr(ell_f[0]) if ell_f else None, ptr(ell_f[1]) if ell_f else None,
+                                                          ptr(ell_t[0]) if ell_t else None, ptr(ell_t[1]) if ell_t else None, 1 if ell_t else 0,
+                                                          None, ptr(ws), ws.numel(), ptr(addend), info, stream()), "glam_triplet_layer_bwd_data_ell")
+                if d_alias is not None and not in_kernel:
+                    d_x = d_x.add_(d_alias)
+                groups = _park(scope, "triplet", wn, ctx.first_app, (ws, tuple(info), x_p, aggr, d_out))
+                if groups is None:
+                    return d_x, d_ea, None, None, None, None, None, None, None, None, d_carry, None, None, None
+        shapes = _triplet_shapes(wn, we, att, H)
+        if groups is not None:
+            # both weight-gradient products + k_param_grads over each group of parked operand sets, chained through the gradient carry
+            carry = f32c(d_carry, "d_carry") if d_carry is not None else None
+            vp = ctypes.c_void_p
+            for grp in groups:
+                n = len(grp)
+                out, o = _flat_grads(shapes, dev)
+                c = _flat_views(carry, shapes) if carry is not None else (None,) * 5
+                ws2 = torch.empty(2 * lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
+                infos = (ctypes.c_int64 * (4 * n))(*[v for t in grp for v in t[1]])
+                arr = lambda i: (vp * n)(*[t[i].data_ptr() for t in grp])
+                check(lib.glam_triplet_layer_param_grads_sets(n, arr(0), infos, arr(2), arr(3), arr(4), N, C, H, De, Cp, Dp, ptr(wn), ptr(we),
+                                                              ptr(att), ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(o[3]), ptr(o[4]), ptr(c[0]), ptr(c[1]),
+                                                              ptr(c[2]), ptr(c[3]), ptr(c[4]), ptr(ws2), ws2.numel(), stream()),
+                      "glam_triplet_layer_param_grads_sets")
+                carry = out
+            return d_x, d_ea, None, None, None, None, None, None, None, None, carry, None, None, None
         # the five parameter gradients are consecutive views of ONE buffer (parameter order), so a data-parallel
         # step can all-reduce them as a single bucket without a gather copy (parallel.flat_view)
-        sizes = [wn.numel(), we.numel(), att.numel(), H * C * C, C]
-        flatg = torch.empty(sum(sizes), **f)
-        d_wn, d_we, d_att, d_wsc, d_bias = (t.view(s) for t, s in zip(flatg.split(sizes), (wn.shape, we.shape, att.shape, (H * C, C), (C,))))
-        # molecular graphs with one-hot bond features: B1 and B2 + d_x warp-specialised over the ELL records of both directions
-        ell_t = gi.ell_t() if (d_ea is None and _ws_route(lib, N, H, Cp, Dp, ea_p)) else None
+        flatg, (d_wn, d_we, d_att, d_wsc, d_bias) = _flat_grads(shapes, dev)
         have_carry = ctx.carried and d_carry is not None and N > 0
-        ell_f = gi.ell() if ell_t is not None else None          # (by target: what the forward used)
-        scope = ctx.scope
-        if ctx.carried and d_ea is None and scope is not None and GRU_WGRAD_BATCH and N >= 512:
-            # The parameter gradients of ALL applications of the layer from one launch pair: every application runs the DATA half of its
-            # backward (d_x) and parks its operands — its workspace holds d_xw, d_a and the block partials of d_W_edge / d_M —; the first
-            # application (its backward runs last) runs both weight-gradient products over the parked sets and k_param_grads ONCE
-            # (glam_triplet_layer_param_grads_sets).  3 x (k_wgrad + k_param_grads) -> 1 + 1 per training step at message_steps = 3.
-            in_kernel = d_alias is not None and ell_t is not None and _lib.route_enabled("x3")   # (warp-specialised route only)
-            addend = f32c(d_alias, "d_identity") if in_kernel else None
-            info = (ctypes.c_int64 * 4)()
-            check(lib.glam_triplet_layer_bwd_data_ell(ptr(x_p), ptr(ea_p), ptr(staged), ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats), ptr(d_out),
-                                                      ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t), N, E, C, H, De,
-                                                      Cp, Dp, slope, ptr(d_x), ptr(ell_f[0]) if ell_f else None, ptr(ell_f[1]) if ell_f else None,
-                                                      ptr(ell_t[0]) if ell_t else None, ptr(ell_t[1]) if ell_t else None, 1 if ell_t else 0,
-                                                      None, ptr(ws), ws.numel(), ptr(addend), info, stream()), "glam_triplet_layer_bwd_data_ell")
-            if d_alias is not None and not in_kernel:
-                d_x = d_x.add_(d_alias)
-            parked = scope.bwd.setdefault(("triplet-parked", id(wn)), (wn, []))[1]
-            parked.append((ws, tuple(info), x_p, aggr, d_out))
-            if not ctx.first_app:
-                return d_x, d_ea, None, None, None, None, None, None, None, None, d_carry, None, None, None
-            carry_in = _TripletLayer._flush_parked(parked, N, C, H, De, Cp, Dp, wn, we, att, f32c(d_carry, "d_carry") if d_carry is not None else None)
-            return d_x, d_ea, None, None, None, None, None, None, None, None, carry_in, None, None, None
         if have_carry or ell_t is not None:
             # the gradient accumulated by the later applications of the block is summed by k_param_grads itself
-            c_parts = f32c(d_carry, "d_carry").split(sizes) if have_carry else (None,) * 5
-            c_wn, c_we, c_att, c_wsc, c_bias = c_parts
+            c_wn, c_we, c_att, c_wsc, c_bias = _flat_views(f32c(d_carry, "d_carry"), shapes) if have_carry else (None,) * 5
             # the skip connection's gradient joins d_x in the epilogue of the d_x product (warp-specialised route)
             in_kernel = d_alias is not None and ell_t is not None and _lib.route_enabled("x3")     # (a 3 x bf16 consumer option)
             addend = f32c(d_alias, "d_identity") if in_kernel else None
@@ -831,7 +877,7 @@ class _TripletLayer(torch.autograd.Function):
             if d_alias is not None and not in_kernel:
                 d_x = d_x.add_(d_alias)
             if ctx.carried:
-                return d_x, d_ea, None, None, None, None, None, None, None, None, (flatg if (have_carry or d_carry is None) else flatg.add_(d_carry)), None, None, None
+                return d_x, d_ea, None, None, None, None, None, None, None, None, _carried(flatg, d_carry, have_carry), None, None, None
             return d_x, d_ea, d_wn, d_we, d_att, d_wsc, d_bias, None, None, None, None, None, None, None
         check(lib.glam_triplet_layer_bwd_params(ptr(x_p), ptr(ea_p), ptr(staged), ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats),
                                                 ptr(d_out), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst),
@@ -841,7 +887,7 @@ class _TripletLayer(torch.autograd.Function):
         if d_alias is not None:
             d_x = d_x.add_(d_alias)
         if ctx.carried:
-            return d_x, d_ea, None, None, None, None, None, None, None, None, (flatg if d_carry is None else flatg.add_(d_carry)), None, None, None
+            return d_x, d_ea, None, None, None, None, None, None, None, None, _carried(flatg, d_carry), None, None, None
         return d_x, d_ea, d_wn, d_we, d_att, d_wsc, d_bias, None, None, None, None, None, None, None
 
 
@@ -905,21 +951,15 @@ def triplet_layer(x_p, ea_p, weight_node, weight_edge, att, weight_scale, bias, 
                                               ell_f[0] if ell_f else None, ell_f[1] if ell_f else None,
                                               ell_b[0] if ell_b else None, ell_b[1] if ell_b else None, onehot)
     params = (weight_node, weight_edge, att, weight_scale, bias)
-    C = weight_node.size(0)
-    sizes = [weight_node.numel(), weight_edge.numel(), att.numel(), heads * C * C, C]
-    shapes = (weight_node.shape, weight_edge.shape, att.shape, (heads * C, C), (C,))
-    key = ("carry-triplet", id(weight_node))
-    hit = _SCOPE.fwd.get(key) if _SCOPE is not None else None
-    first = not (hit is not None and hit[0] is weight_node)      # the layer's first application of this pass: its backward runs LAST
-    carry = _carry_for(key, params, sum(sizes), lambda flat: [t.view(sh) for t, sh in zip(flat.split(sizes), shapes)])
-    if carry is None:
+    carry = _Carry(("carry-triplet", id(weight_node)), params, _triplet_shapes(weight_node, weight_edge, att, heads))
+    if carry.tensor is None:
         # no backward can follow (torch.no_grad(), or nothing that requires a gradient): the inference forward
         no_backward = not (torch.is_grad_enabled() and any(t.requires_grad for t in (x_p, ea_p) + params))
         return _TripletLayer.apply(x_p, ea_p, weight_node, weight_edge, att, weight_scale, bias, gi, heads, slope, None, with_identity, True, no_backward)
     # the parameters still enter as inputs (the kernels read them, and the scope's staging cache is keyed on them), but this
     # node returns no gradient for them: it flows through `carry`
-    res = _TripletLayer.apply(x_p, ea_p, weight_node, weight_edge, att, weight_scale, bias, gi, heads, slope, carry, with_identity, first)
-    _carry_store(key, weight_node, res[-1])
+    res = _TripletLayer.apply(x_p, ea_p, weight_node, weight_edge, att, weight_scale, bias, gi, heads, slope, carry.tensor, with_identity, carry.first)
+    carry.store(res[-1])
     return (res[0], res[1]) if with_identity else res[0]
 
 
@@ -942,7 +982,7 @@ class _TripletLayerWide(torch.autograd.Function):
         HC = H * Cp
         if gi.N != N or ea_p.size(0) != gi.E or wn.shape != (C, H * C) or wsc.shape != (H * C, C) or Cp != (C + 3) // 4 * 4:
             raise GlamHipError("triplet_layer_wide: shape mismatch")
-        ctx.carried = carry is not None      # gradient carry of the block's parameters (see _ParamBundle)
+        ctx.carried = carry is not None      # gradient carry of the block's parameters (see _Carry)
         if ctx.carried:
             ctx.set_materialize_grads(False)
         lib, dev = _lib.load(), x_p.device
@@ -1036,53 +1076,40 @@ class _TripletLayerWide(torch.autograd.Function):
         else:
             d_x = torch.matmul(d_xw, Wcat[:, :HC].t())
             d_x.addmm_(d_a, Wcat[:, HC:].t())
-        sizes = [wn.numel(), we.numel(), att.numel(), H * C * C, C]
-        shapes = (wn.shape, we.shape, att.shape, (H * C, C), (C,))
-        if ctx.carried and scope is not None and GRU_WGRAD_BATCH and N >= 512 and Cp <= 128:
-            # the parameter gradients of ALL applications of the layer from one set of launches (see _TripletLayer.backward): every
-            # application parks its operands (and its small d_W_edge / d_M sums); the first one — its backward runs last — runs both N-deep
-            # products over the parked sets (glam_wgrad_gemm_sets2) and the chain rule (k_stage_params_bwd is linear in dstaged) ONCE
-            parked = scope.bwd.setdefault(("wide-parked", id(wn)), (wn, []))[1]
-            parked.append((aggr, d_out, d_xw, d_a, x_p, dstaged))
-            if not ctx.first_app:
+        if ctx.carried and Cp <= 128 and _parks(scope, N):
+            # the parameter gradients of ALL applications of the layer from one set of launches (see _park): every application parks
+            # its operands (and its small d_W_edge / d_M sums); the first one runs both N-deep products over the parked sets
+            # (glam_wgrad_gemm_sets2) and the chain rule (k_stage_params_bwd is linear in dstaged) ONCE
+            groups = _park(scope, "wide", wn, ctx.first_app, (aggr, d_out, d_xw, d_a, x_p, dstaged))
+            if groups is None:
                 return d_x, d_ea, None, None, None, None, None, None, None, None, d_carry, None
-            sets = list(parked)
-            parked.clear()
             vp = ctypes.c_void_p
-            small = dstaged[o_we:]                       # d_We_p | d_M: sums over the applications
-            for t in sets[:-1]:
+            small = dstaged[o_we:]                       # d_We_p | d_M: sums over the applications (its own set is parked last)
+            for t in [t for grp in groups for t in grp][:-1]:
                 small.add_(t[5][o_we:])
-            first_group = True
-            while sets:
-                grp, sets = sets[:3], sets[3:]
+            for g, grp in enumerate(groups):
                 n = len(grp)
                 arr = lambda i: (vp * n)(*[t[i].data_ptr() for t in grp])
                 wws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
                 check(lib.glam_wgrad_gemm_sets2(n, arr(0), HC, HC, None, 0, 0, 1, arr(1), Cp, Cp, N, ptr(dstaged[o_wsb:]), Cp, 1,
-                                                None if first_group else ptr(dstaged[o_wsb:]), ptr(wws), wws.numel(), stream()),
+                                                None if g == 0 else ptr(dstaged[o_wsb:]), ptr(wws), wws.numel(), stream()),
                       "glam_wgrad_gemm_sets2")
                 wws2 = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
                 check(lib.glam_wgrad_gemm_sets2(n, arr(2), HC, HC, arr(3), 8, 8, 0, arr(4), Cp, Cp, N, ptr(dstaged), 1, HC + 8,
-                                                None if first_group else ptr(dstaged), ptr(wws2), wws2.numel(), stream()),
+                                                None if g == 0 else ptr(dstaged), ptr(wws2), wws2.numel(), stream()),
                       "glam_wgrad_gemm_sets2")
-                first_group = False
-            flatg = torch.empty(sum(sizes), **f)
-            d_wn, d_we, d_att, d_wsc, d_bias = (t.view(sh) for t, sh in zip(flatg.split(sizes), shapes))
-            check(lib.glam_triplet_stage_params_bwd(ptr(wn), ptr(we), ptr(att), ptr(dstaged), C, H, De, Cp, Dp, ptr(d_wn), ptr(d_we),
-                                                    ptr(d_att), ptr(d_wsc), ptr(d_bias), stream()), "glam_triplet_stage_params_bwd")
-            return d_x, d_ea, None, None, None, None, None, None, None, None, (flatg if d_carry is None else flatg.add_(d_carry)), None
-        wws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
-        # d_WsB = [aggr | 1]^T d_out ;  d_Wcat = x^T [d_xw | d_a], computed as ([d_xw | d_a]^T x)^T
-        check(lib.glam_wgrad_gemm(ptr(aggr), HC, HC, None, 0, 0, 1, ptr(d_out), Cp, Cp, 0, N, ptr(dstaged[o_wsb:]), Cp, 1,
-                                  ptr(wws), wws.numel(), stream()), "glam_wgrad_gemm")
-        check(lib.glam_wgrad_gemm(ptr(d_xw), HC, HC, ptr(d_a), 8, 8, 0, ptr(x_p), Cp, Cp, 0, N, ptr(dstaged), 1, HC + 8,
-                                  ptr(wws), wws.numel(), stream()), "glam_wgrad_gemm")
-        flatg = torch.empty(sum(sizes), **f)
-        d_wn, d_we, d_att, d_wsc, d_bias = (t.view(s) for t, s in zip(flatg.split(sizes), shapes))
+        else:
+            wws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
+            # d_WsB = [aggr | 1]^T d_out ;  d_Wcat = x^T [d_xw | d_a], computed as ([d_xw | d_a]^T x)^T
+            check(lib.glam_wgrad_gemm(ptr(aggr), HC, HC, None, 0, 0, 1, ptr(d_out), Cp, Cp, 0, N, ptr(dstaged[o_wsb:]), Cp, 1,
+                                      ptr(wws), wws.numel(), stream()), "glam_wgrad_gemm")
+            check(lib.glam_wgrad_gemm(ptr(d_xw), HC, HC, ptr(d_a), 8, 8, 0, ptr(x_p), Cp, Cp, 0, N, ptr(dstaged), 1, HC + 8,
+                                      ptr(wws), wws.numel(), stream()), "glam_wgrad_gemm")
+        flatg, (d_wn, d_we, d_att, d_wsc, d_bias) = _flat_grads(_triplet_shapes(wn, we, att, H), dev)
         check(lib.glam_triplet_stage_params_bwd(ptr(wn), ptr(we), ptr(att), ptr(dstaged), C, H, De, Cp, Dp, ptr(d_wn), ptr(d_we),
                                                 ptr(d_att), ptr(d_wsc), ptr(d_bias), stream()), "glam_triplet_stage_params_bwd")
         if ctx.carried:       # one add of the flat buffer per application instead of five per-parameter accumulations
-            return d_x, d_ea, None, None, None, None, None, None, None, None, (flatg if d_carry is None else flatg.add_(d_carry)), None
+            return d_x, d_ea, None, None, None, None, None, None, None, None, _carried(flatg, d_carry), None
         return d_x, d_ea, d_wn, d_we, d_att, d_wsc, d_bias, None, None, None, None, None
 
 
@@ -1118,17 +1145,11 @@ def wide_layer_supported(C, heads, De):
 
 def triplet_layer_wide(x_p, ea_p, weight_node, weight_edge, att, weight_scale, bias, gi, heads, slope=0.2):
     params = (weight_node, weight_edge, att, weight_scale, bias)
-    C = weight_node.size(0)
-    sizes = [weight_node.numel(), weight_edge.numel(), att.numel(), heads * C * C, C]
-    shapes = (weight_node.shape, weight_edge.shape, att.shape, (heads * C, C), (C,))
-    key = ("carry-triplet-wide", id(weight_node))
-    hit = _SCOPE.fwd.get(key) if _SCOPE is not None else None
-    first = not (hit is not None and hit[0] is weight_node)      # the layer's first application of this pass: its backward runs LAST
-    carry = _carry_for(key, params, sum(sizes), lambda flat: [t.view(sh) for t, sh in zip(flat.split(sizes), shapes)])
-    if carry is None:
+    carry = _Carry(("carry-triplet-wide", id(weight_node)), params, _triplet_shapes(weight_node, weight_edge, att, heads))
+    if carry.tensor is None:
         return _TripletLayerWide.apply(x_p, ea_p, weight_node, weight_edge, att, weight_scale, bias, gi, heads, slope)
-    out, carry = _TripletLayerWide.apply(x_p, ea_p, weight_node, weight_edge, att, weight_scale, bias, gi, heads, slope, carry, first)
-    _carry_store(key, weight_node, carry)
+    out, carry_out = _TripletLayerWide.apply(x_p, ea_p, weight_node, weight_edge, att, weight_scale, bias, gi, heads, slope, carry.tensor, carry.first)
+    carry.store(carry_out)
     return out
 
 
@@ -1217,7 +1238,7 @@ GRU_FUSED_MIN_NODES = 16384
 GRU_WS = "1"
 # MessageBlock's skip connection handed through the conv's autograd node (the d_x product's epilogue sums both gradient paths): A/B switch
 SKIP_THROUGH_CONV = True
-# the GRU's weight gradients of all applications of a block in one launch pair (glam_wgrad_gemm_pair_split_seg): A/B switch
+# the weight gradients of all applications of a block from one product over their parked operand sets (see _park): A/B switch
 GRU_WGRAD_BATCH = True
 # the warp-specialised GRU step on pre-split operand fragments of its gate matrices (glam_gru_ws_make_pre) instead of splitting the plain
 # images in every block's prologue: A/B switch (GLAM_GRU_PRE=0)

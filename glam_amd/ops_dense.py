@@ -206,7 +206,7 @@ class _MatmulTall(torch.autograd.Function):
     data-side products stay on the library GEMM, but the WEIGHT gradient ``A^T @ dY`` — a reduction over the N rows for
     which the library's heuristics pick 32x32 tiles (77 us at N = 20 k, K = 240, M = 60) — runs on ``k_wgrad`` (≈12 us),
     the bias gradient riding on its ones column.  ``carry``: the gradient carry of (w, bias) when a block applies them several
-    times per forward (see _ParamBundle): [d_w | d_bias] flat, summed by the reduction of the weight-gradient product."""
+    times per forward (see ops._Carry): [d_w | d_bias] flat, summed by the reduction of the weight-gradient product."""
 
     @staticmethod
     def forward(ctx, a, w, bias, carry=None, first_app=True, with_identity=False):
@@ -286,21 +286,17 @@ class _MatmulTall(torch.autograd.Function):
             da = d_alias
         dw = db = None
         scope = ctx.scope
-        if ctx.carried and ctx.has_bias and M <= 64 and scope is not None and _o.GRU_WGRAD_BATCH and N >= _GRU_BATCH_MIN_ROWS:
-            # the weight gradient of ALL applications of the block in one launch (see _GruBlock.backward): every application but the first
-            # parks (a, dy); the first one — its backward runs last — multiplies the parked sets together, three per launch
-            lib = _lib.load()
-            parked = scope.bwd.setdefault(("tall-parked", id(w)), (w, []))[1]
-            parked.append((a, dy))
-            if not ctx.first_app:
+        if ctx.carried and ctx.has_bias and M <= 64 and _o._parks(scope, N):
+            # the weight gradient of ALL applications of the block in one launch (see ops._park): every application but the first
+            # parks (a, dy); the first one multiplies the parked sets together, three per launch
+            groups = _o._park(scope, "tall", w, ctx.first_app, (a, dy))
+            if groups is None:
                 return da, None, None, d_carry, None
-            sets = list(parked)
-            parked.clear()
+            lib = _lib.load()
             dwb = torch.empty(K + 1, M, dtype=torch.float32, device=a.device)
             add = None if d_carry is None else f32c(d_carry, "d_carry")
             vp = ctypes.c_void_p
-            while sets:
-                grp, sets = sets[:3], sets[3:]
+            for grp in groups:
                 n = len(grp)
                 ws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=a.device)
                 check(lib.glam_wgrad_gemm_sets(n, (vp * n)(*[t[0].data_ptr() for t in grp]), K, K, 1, (vp * n)(*[t[1].data_ptr() for t in grp]),
@@ -325,8 +321,7 @@ class _MatmulTall(torch.autograd.Function):
                 dwb = torch.empty(K + 1, M, dtype=torch.float32, device=a.device)
                 product(a, K, K, 1, dy, M, M, dwb, M, 1)
                 if ctx.carried:
-                    flat = dwb.view(-1)
-                    return da, None, None, (flat if (add is not None or d_carry is None) else flat.add_(d_carry)), None
+                    return da, None, None, _o._carried(dwb.view(-1), d_carry, add is not None), None
                 return da, dwb[:K], dwb[K], None, None
             dw = torch.empty(K, M, dtype=torch.float32, device=a.device)
             if M <= 128:      # dw = a^T dy: P = a (up to 320 columns), Q = dy (two 64-column chunks beyond 64)
@@ -334,27 +329,20 @@ class _MatmulTall(torch.autograd.Function):
             else:             # wide output: dw^T = dy^T a, written through transposed strides
                 product(dy, M, M, 0, a, K, K, dw, 1, M)
             if ctx.carried:
-                flat = dw.view(-1)
-                return da, None, None, (flat if (add is not None or d_carry is None) else flat.add_(d_carry)), None
+                return da, None, None, _o._carried(dw.view(-1), d_carry, add is not None), None
         return da, dw, db, None, None
 
 
 def _matmul_tall_node(a, w, bias, with_identity=False):
     """``_MatmulTall`` with the gradients of (w, bias) carried across the applications of a block inside a weight_scope."""
     K, M = w.shape
-    total = K * M + (M if bias is not None else 0)
-    params = (w,) if bias is None else (w, bias)
-
-    def split(flat):     # [d_w (K x M) | d_bias (M)]: the layout of the [a | 1]^T dy product
-        return (flat[:K * M].view(K, M),) if bias is None else (flat[:K * M].view(K, M), flat[K * M:])
-    key = ("carry-tall", id(w), id(bias))
-    hit = _o._SCOPE.fwd.get(key) if _o._SCOPE is not None else None
-    first = not (hit is not None and hit[0] is w)          # the block's first application of this pass: its backward runs LAST
-    carry = _o._carry_for(key, params, total, split) if (w.requires_grad or (bias is not None and bias.requires_grad)) else None
-    if carry is None:
+    # [d_w (K x M) | d_bias (M)]: the layout of the [a | 1]^T dy product
+    params, shapes = ((w,), ((K, M),)) if bias is None else ((w, bias), ((K, M), (M,)))
+    carry = _o._Carry(("carry-tall", id(w), id(bias)), params, shapes)
+    if carry.tensor is None:
         return _MatmulTall.apply(a, w, bias, None, True, with_identity)
-    res = _MatmulTall.apply(a, w, bias, carry, first, with_identity)
-    _o._carry_store(key, w, res[-1])
+    res = _MatmulTall.apply(a, w, bias, carry.tensor, carry.first, with_identity)
+    carry.store(res[-1])
     return (res[0], res[1]) if with_identity else res[0]
 
 
@@ -385,7 +373,7 @@ class _LinearTall(torch.autograd.Function):
     on ``k_wgrad`` as two contiguous tensors (``glam_wgrad_gemm_linear``: no strided views for autograd to copy).  ``celu_in``: act = the
     CELU MessageBlock applies in front of its GRU (src_1gp/layer.py:261), folded into the operand loads of all three products instead
     of a launch each way.  ``carry``: the gradient carry of (w, b) when a block applies them several times per forward (see
-    _ParamBundle): ``[d_w | d_b]`` flat, summed by the reduction of the weight-gradient product."""
+    ops._Carry): ``[d_w | d_b]`` flat, summed by the reduction of the weight-gradient product."""
 
     @staticmethod
     def forward(ctx, x, w, b, carry=None, celu_in=False, first_app=True):
@@ -438,20 +426,15 @@ class _LinearTall(torch.autograd.Function):
             dx = torch.matmul(dy, w)
         ws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=x.device)
         scope = ctx.scope
-        if (ctx.carried and scope is not None and _o.GRU_WGRAD_BATCH and N >= _GRU_BATCH_MIN_ROWS and K % 4 == 0 and K + 1 <= 128 and M <= 320):
-            # the weight gradient of ALL applications of the block in one launch (see _GruBlock.backward): every application but the first
-            # parks (dy, x); the first one — its backward runs last — multiplies the parked sets together, three per launch
-            parked = scope.bwd.setdefault(("lintall-parked", id(w)), (w, []))[1]
-            parked.append((dy, x, bool(ctx.fold)))
-            if not ctx.first_app:
+        if ctx.carried and K % 4 == 0 and K + 1 <= 128 and M <= 320 and _o._parks(scope, N):
+            # the weight gradient of ALL applications of the block in one launch (see ops._park): every application but the first
+            # parks (dy, x); the first one multiplies the parked sets together, three per launch, one CELU fold per launch
+            groups = _o._park(scope, "lintall", w, ctx.first_app, (dy, x, bool(ctx.fold)), bool(ctx.fold))
+            if groups is None:
                 return dx, None, None, d_carry, None, None
-            sets = list(parked)
-            parked.clear()
             addf = None if d_carry is None else f32c(d_carry, "d_carry")
             vp = ctypes.c_void_p
-            while sets:
-                grp = [t for t in sets if t[2] == sets[0][2]][:3]
-                sets = [t for t in sets if all(t is not u for u in grp)]
+            for grp in groups:
                 n = len(grp)
                 flat = torch.empty(M * (K + 1), **f)
                 aw, ab = (addf[:M * K], addf[M * K:]) if addf is not None else (None, None)
@@ -470,31 +453,25 @@ class _LinearTall(torch.autograd.Function):
             check(lib.glam_wgrad_gemm_linear(ptr(dy), M, M, ptr(x), K, K, int(ctx.fold), ptr(dw), ptr(db), ptr(aw), ptr(ab), N, ptr(ws),
                                              ws.numel(), stream()), "glam_wgrad_gemm_linear")
             if ctx.carried:
-                return dx, None, None, (flat if (add is not None or d_carry is None) else flat.add_(d_carry)), None, None
+                return dx, None, None, _o._carried(flat, d_carry, add is not None), None, None
             return dx, dw, db, None, None, None
         dwb = torch.empty(M, K + 1, **f)
         check(lib.glam_wgrad_gemm(ptr(dy), M, M, None, 0, 0, 0, ptr(x), K, K, 1, N, ptr(dwb), K + 1, 1, ptr(ws), ws.numel(), stream()),
               "glam_wgrad_gemm")
         if ctx.carried:      # (layout of the carry: [d_w | d_b])
             flat = torch.cat([dwb[:, :K].reshape(-1), dwb[:, K]])
-            return dx, None, None, (flat if d_carry is None else flat.add_(d_carry)), None, None
+            return dx, None, None, _o._carried(flat, d_carry), None, None
         return dx, dwb[:, :K], dwb[:, K], None, None, None
 
 
 def _linear_tall_node(x, w, b, celu_in=False):
     """``_LinearTall`` with the gradients of (w, b) carried across the applications of a block inside a weight_scope."""
     M, K = w.shape
-
-    def split(flat):     # [d_w (M x K) | d_b (M)]: two contiguous pieces
-        return flat[:M * K].view(M, K), flat[M * K:]
-    key = ("carry-lintall", id(w), id(b))
-    hit = _o._SCOPE.fwd.get(key) if _o._SCOPE is not None else None
-    first = not (hit is not None and hit[0] is w)          # the block's first application of this pass: its backward runs LAST
-    carry = _o._carry_for(key, (w, b), M * (K + 1), split) if (w.requires_grad or b.requires_grad) else None
-    if carry is None:
+    carry = _o._Carry(("carry-lintall", id(w), id(b)), (w, b), ((M, K), (M,)))      # [d_w (M x K) | d_b (M)]: two contiguous pieces
+    if carry.tensor is None:
         return _LinearTall.apply(x, w, b, None, celu_in)
-    y, carry = _LinearTall.apply(x, w, b, carry, celu_in, first)
-    _o._carry_store(key, w, carry)
+    y, carry_out = _LinearTall.apply(x, w, b, carry.tensor, celu_in, carry.first)
+    carry.store(carry_out)
     return y
 
 
@@ -997,28 +974,19 @@ def _want_gru_fused(N):
     return _o.GRU_FUSED in ("1", True) or (_o.GRU_FUSED == "auto" and N >= _o.GRU_FUSED_MIN_NODES)
 
 def _gru_block(x, h, identity, w_ih, w_hh, b_ih, b_hh, act, slope, celu_in, rng=None, node=None):
-    """``_GruBlock`` with the gradients of its four parameters carried across the block's applications (see _ParamBundle)."""
+    """``_GruBlock`` with the gradients of its four parameters carried across the block's applications (see ops._Carry)."""
     M, C = w_ih.shape
-    def split(flat):      # [d_w_ih | d_b_ih | d_w_hh | d_b_hh], every piece contiguous: autograd takes the views without a copy
-        w1, b1, w2, b2 = flat.split([M * C, M, M * C, M])
-        return w1.view(M, C), w2.view(M, C), b1, b2
-    key = ("carry-gru", id(w_ih))
-    hit = _o._SCOPE.fwd.get(key) if _o._SCOPE is not None else None
-    first = not (hit is not None and hit[0] is w_ih)        # the block's first application of this pass: its backward runs LAST
-    carry = _o._carry_for(key, (w_ih, w_hh, b_ih, b_hh), 2 * M * (C + 1), split)
+    # [d_w_ih | d_b_ih | d_w_hh | d_b_hh], every piece contiguous: autograd takes the views without a copy
+    carry = _o._Carry(("carry-gru", id(w_ih)), (w_ih, w_hh, b_ih, b_hh), ((M, C), (M,), (M, C), (M,)), order=(0, 2, 1, 3))
     took = {} if node is not None else None        # (filled by the forward when its route wrote the product: xw, a_ij)
-    out, h_new, out_drop, carry = _GruBlock.apply(x, h, identity, w_ih, w_hh, b_ih, b_hh, act, slope, celu_in, carry, rng, first,
-                                                  None if node is None else (node[0], node[1], took))
-    if carry is not None:
-        _o._carry_store(key, w_ih, carry)
+    out, h_new, out_drop, carry_out = _GruBlock.apply(x, h, identity, w_ih, w_hh, b_ih, b_hh, act, slope, celu_in, carry.tensor, rng,
+                                                      carry.first, None if node is None else (node[0], node[1], took))
+    carry.store(carry_out)
     if out_drop is not None:
         _o.register_dropped(out, out_drop, rng[2])
     if took:
         _o.register_node_product(out_drop if out_drop is not None else out, node[0], took["xw"], took["a_ij"])
     return out, h_new
-
-
-_GRU_BATCH_MIN_ROWS = 512       # (a wave's row range must fit into one operand set: glam_wgrad_gemm_pair_split_seg)
 
 
 class _GruBlock(torch.autograd.Function):
@@ -1256,25 +1224,17 @@ class _GruBlock(torch.autograd.Function):
             check(lib.glam_ts_gemm_celu(ptr(d_gi), M, M, 0, ptr(image_t(w_ih)), None, ptr(dx), C, C, ptr(x) if celu_in else None, C, N, st),
                   "glam_ts_gemm_celu")
             check(lib.glam_ts_gemm_add(ptr(d_gh), M, M, ptr(image_t(w_hh)), None, ptr(dh), C, C, ptr(d_h), C, N, st), "glam_ts_gemm_add")
-        if ctx.carried and scope is not None and _o.GRU_WGRAD_BATCH and N >= _GRU_BATCH_MIN_ROWS:
-            # The weight gradients of ALL applications of the block in one launch pair: every application but the first parks its
-            # operands in the scope and passes the carry on untouched; the first one (its backward runs last: everything later in
-            # the forward depends on its outputs) multiplies the parked sets together — [d_gi_1; d_gi_2; d_gi_3]^T [x_1; x_2; x_3] —
-            # three sets per launch.  3 launches + 3 reductions -> 1 + 1 per training step at message_steps = 3.
-            key = ("gru-parked", id(w_ih))
-            parked = scope.bwd.setdefault(key, (w_ih, []))[1]
-            parked.append((d_gi, x, d_gh, h, bool(celu_q), gates))
-            if not ctx.first_app:
+        if ctx.carried and _o._parks(scope, N):
+            # The weight gradients of ALL applications of the block in one launch pair (see ops._park): the first application multiplies
+            # the parked sets together — [d_gi_1; d_gi_2; d_gi_3]^T [x_1; x_2; x_3] —, one CELU fold and gate layout per launch
+            groups = _o._park(scope, "gru", w_ih, ctx.first_app, (d_gi, x, d_gh, h, bool(celu_q), gates), (bool(celu_q), gates))
+            if groups is None:
                 return dx, dh, d_id, None, None, None, None, None, None, None, d_carry, None, None, None
-            sets = list(parked)
-            parked.clear()
             flat = torch.empty(2 * M * (C + 1), **f)
             dw_ih, db_ih, dw_hh, db_hh = flat.split([M * C, M, M * C, M])
             add = [None] * 4 if d_carry is None else list(f32c(d_carry, "d_carry").split([M * C, M, M * C, M]))
             vp = ctypes.c_void_p
-            while sets:
-                grp = [t for t in sets if t[4:] == sets[0][4:]][:3]
-                sets = [t for t in sets if all(t is not u for u in grp)]
+            for grp in groups:
                 n = len(grp)
                 ws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
                 arr = lambda i: (vp * n)(*[t[i].data_ptr() for t in grp])
@@ -1307,7 +1267,7 @@ class _GruBlock(torch.autograd.Function):
                                                  ptr(d_gh), M, M, ptr(h), C, C, 0, ptr(dw_hh), ptr(db_hh), N, ptr(ws), ws.numel(),
                                                  ptr(dc[0]), ptr(dc[1]), ptr(dc[2]), ptr(dc[3]), st), "glam_wgrad_gemm_pair_split")
         if ctx.carried:
-            return dx, dh, d_id, None, None, None, None, None, None, None, (flat if d_carry is None else flat.add_(d_carry)), None, None, None
+            return dx, dh, d_id, None, None, None, None, None, None, None, _o._carried(flat, d_carry), None, None, None
         return dx, dh, d_id, dw_ih.view(M, C), dw_hh.view(M, C), db_ih, db_hh, None, None, None, None, None, None, None
 
 

@@ -448,3 +448,77 @@ def test_launch_saving_hints_are_host_logic():
     assert ops.cat_cols([torch.zeros(2, 1)] * 9).shape == (2, 9)
     assert ops.GRU_WGRAD_BATCH in (True, False) and ops.PRESTAGE in (True, False) and ops.NORM_DROP in (True, False) and ops.DENSE_LINEAR in (True, False)
 
+
+
+def test_gradient_carry_threads_one_flat_buffer_through_a_blocks_applications(monkeypatch):
+    """ops._Carry on CPU tensors: the block's first application of a pass is told apart from the later ones (three and four
+    applications), every application gets the carry the previous one stored, and the bundle's backward hands each parameter the view
+    of its piece of the flat buffer — consecutive pieces, in parameter order unless ``order`` says otherwise."""
+    w, b = torch.randn(3, 4, requires_grad=True), torch.randn(3, requires_grad=True)
+    for n in (3, 4):
+        with ops.weight_scope():
+            firsts, carries = [], []
+            for _ in range(n):
+                c = ops._Carry(("carry-test", id(w)), (w, b), ((3, 4), (3,)))
+                assert c.tensor is not None and (not carries or c.tensor is carries[-1])
+                firsts.append(c.first)
+                carries.append(c.tensor.view(-1))       # (what a node returns as its carry output)
+                c.store(carries[-1])
+        assert firsts == [True] + [False] * (n - 1)
+    g = torch.arange(15.0)
+    dw, db = torch.autograd.grad(carries[0], (w, b), g)
+    assert torch.equal(dw, g[:12].view(3, 4)) and torch.equal(db, g[12:])
+    assert dw.data_ptr() == g.data_ptr() and db.data_ptr() == g.data_ptr() + 12 * 4       # views, no copies
+    views = ops._flat_views(g, ((3, 4), (3,)))
+    assert [v.shape for v in views] == [(3, 4), (3,)] and views[1].data_ptr() == views[0].data_ptr() + views[0].numel() * 4
+    # memory order != parameter order (the GRU's [d_w_ih | d_b_ih | d_w_hh | d_b_hh] for (w_ih, w_hh, b_ih, b_hh))
+    w2, b2 = torch.randn(3, 4, requires_grad=True), torch.randn(3, requires_grad=True)
+    with ops.weight_scope():
+        c = ops._Carry(("carry-test", id(w)), (w, w2, b, b2), ((3, 4), (3,), (3, 4), (3,)), order=(0, 2, 1, 3))
+    g = torch.arange(30.0)
+    gw, gw2, gb, gb2 = torch.autograd.grad(c.tensor, (w, w2, b, b2), g)
+    assert torch.equal(gw, g[:12].view(3, 4)) and torch.equal(gb, g[12:15]) and torch.equal(gw2, g[15:27].view(3, 4)) and torch.equal(gb2, g[27:])
+    # no carry outside a scope, without gradients, or with the switch off
+    assert ops._Carry(("carry-test", id(w)), (w, b), ((3, 4), (3,))).tensor is None
+    with ops.weight_scope():
+        with torch.no_grad():
+            assert ops._Carry(("carry-test", id(w)), (w, b), ((3, 4), (3,))).tensor is None
+        monkeypatch.setattr(ops, "GRAD_CARRY", False)
+        assert ops._Carry(("carry-test", id(w)), (w, b), ((3, 4), (3,))).tensor is None
+    flat, d = torch.ones(4), torch.full((4,), 2.0)
+    assert ops._carried(flat, None) is flat and torch.equal(ops._carried(flat, d, summed=True), torch.ones(4))
+    assert ops._carried(flat, d) is flat and torch.equal(flat, torch.full((4,), 3.0))
+
+
+def test_parked_weight_gradient_sets_are_launched_by_the_first_application(monkeypatch):
+    """ops._park with fake launches: the later applications park (their backward runs first), the first one gets every parked set in
+    groups of at most three that never mix compatibility keys and keep parking order, and the parked list is empty after a flush even
+    when a launch raises (a retried backward must not count a set twice)."""
+    scope, owner = ops._WeightScope(), torch.zeros(1)
+
+    def flush(first_set, compat=None):
+        launched = []
+        addend = None
+        for grp in ops._park(scope, "test", owner, True, first_set, compat):
+            launched.append((list(grp), addend))         # (a launch chains the previous group's result in as its addend)
+            addend = len(launched)
+        return launched
+
+    for n in (3, 4):                                     # applications n, ..., 2 park; application 1 launches
+        assert all(ops._park(scope, "test", owner, False, k) is None for k in range(n, 1, -1))
+        assert flush(1) == ([([3, 2, 1], None)] if n == 3 else [([4, 3, 2], None), ([1], 1)])
+    keys = "abaaba"
+    for k in range(5):
+        ops._park(scope, "test", owner, False, k, keys[k])
+    assert flush(5, keys[5]) == [([0, 2, 3], None), ([1, 4], 1), ([5], 2)]
+    ops._park(scope, "test", owner, False, "later")
+
+    def failing_launch(grp):
+        raise RuntimeError("launch failed")
+    with pytest.raises(RuntimeError):
+        for grp in ops._park(scope, "test", owner, True, "first"):
+            failing_launch(grp)
+    assert ops._park(scope, "test", owner, True, None) == []
+    assert ops._parks(scope, 512) and not ops._parks(scope, 511) and not ops._parks(None, 4096)
+    monkeypatch.setattr(ops, "GRU_WGRAD_BATCH", False)
+    assert not ops._parks(scope, 4096)

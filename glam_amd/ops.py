@@ -21,6 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import GlamHipError, check, f32c, ptr, require_device, stream
+from ._memo import TensorMemo
 
 
 # --------------------------------------------------------------------------------------
@@ -379,20 +380,14 @@ def pad_group(items):
 # zero hands the caller the [N, C] VIEW of it (slice_cols) and remembers the padded tensor; when that view comes back as
 # the input of the next op (conv -> GRU -> next message step), pad_cols returns the padded tensor itself instead of
 # copying: the per-step pad / slice glue of the odd widths disappears without changing any module interface.
-_PADDED: dict = {}      # data_ptr -> (weakref(padded tensor), its version counter at registration)
+_PADDED = TensorMemo("ptr")      # the padded tensors themselves (TensorMemo.referent): no value goes with them
 
 
 def slice_cols(x_p, C):
     """``x_p[:, :C]`` of a padded tensor whose columns ``C..`` are zero (the caller guarantees it)."""
     if x_p.size(1) == C:
         return x_p
-    key = x_p.data_ptr()
-
-    def _drop(ref, k=key):
-        hit = _PADDED.get(k)
-        if hit is not None and hit[0] is ref:
-            _PADDED.pop(k, None)
-    _PADDED[key] = (weakref.ref(x_p, _drop), x_p._version)
+    _PADDED.put(x_p, True)
     v = x_p[:, :C]
     v._glam_padded = x_p      # the view keeps its padded tensor alive (a view of a VIEW — the skip-connection alias of _TripletLayer —
     return v                  # only references the root storage owner: the registered object would die with the caller's local)
@@ -400,12 +395,10 @@ def slice_cols(x_p, C):
 
 def padded_base(x):
     """The registered zero-padded tensor that ``x[N, C]`` is the untouched view of, or None."""
-    hit = _PADDED.get(x.data_ptr()) if x.dim() == 2 else None
-    if hit is not None:
-        base = hit[0]()
-        if base is not None and base._version == hit[1] and base.size(0) == x.size(0) and base.size(1) > x.size(1) and \
-                x.stride() == (base.size(1), 1) and base.data_ptr() == x.data_ptr() and base.dtype == x.dtype:
-            return base
+    base = _PADDED.referent(x) if x.dim() == 2 else None
+    if base is not None and base.size(0) == x.size(0) and base.size(1) > x.size(1) and \
+            x.stride() == (base.size(1), 1) and base.data_ptr() == x.data_ptr() and base.dtype == x.dtype:
+        return base
     return None
 
 
@@ -420,40 +413,28 @@ def pad_cols(x, Cp):
     C = x.size(1)
     if not x.requires_grad and x.grad_fn is None:
         # a DATA tensor (e.g. the atom features x[N, 15] of a cached loader batch): padded once per tensor, not once per pass
-        key = id(x)
-        hit = _PAD_DATA.get(key)
-        if hit is not None and hit[0]() is x and hit[1] == x._version and hit[2].size(1) == Cp:
-            return hit[2]
-        padded = torch.nn.functional.pad(x, (0, Cp - C))
-        try:
-            _PAD_DATA[key] = (weakref.ref(x, lambda _r, k=key: _PAD_DATA.pop(k, None)), x._version, padded)
-        except TypeError:
-            pass
+        padded = _PAD_DATA.get(x)
+        if padded is None or padded.size(1) != Cp:
+            padded = torch.nn.functional.pad(x, (0, Cp - C))
+            _PAD_DATA.put(x, padded)
         return padded
     return _scoped(_SCOPE.fwd if _SCOPE else None, ("pad-cols", id(x), Cp), x, lambda: torch.nn.functional.pad(x, (0, Cp - C)))
 
 
-_PAD_DATA: dict = {}
+_PAD_DATA = TensorMemo("id")      # data tensor -> its zero-padded copy
 
 
-_GI_CACHE: dict = {}
+_GI_CACHE = TensorMemo("id")      # edge_index -> (num_nodes, GraphIndex)
 
 
 def graph_index(edge_index, num_nodes):
     """Cached ``GraphIndex`` for this very tensor object (dropped when the tensor dies or is
     modified in place)."""
-    key = id(edge_index)
-    hit = _GI_CACHE.get(key)
-    if hit is not None:
-        ref, version, n, gi = hit
-        if ref() is edge_index and version == edge_index._version and n == int(num_nodes):
-            return gi
+    hit = _GI_CACHE.get(edge_index)
+    if hit is not None and hit[0] == int(num_nodes):
+        return hit[1]
     gi = GraphIndex(edge_index, num_nodes)
-    try:
-        ref = weakref.ref(edge_index, lambda _r, k=key, c=_GI_CACHE: c.pop(k, None))
-        _GI_CACHE[key] = (ref, edge_index._version, int(num_nodes), gi)
-    except TypeError:
-        pass
+    _GI_CACHE.put(edge_index, (int(num_nodes), gi))
     return gi
 
 
@@ -480,22 +461,14 @@ class SegmentPtr:
             _check_flag(err, "batch must be non-decreasing with ids in [0, num_graphs)")
 
 
-_SP_CACHE: dict = {}
+_SP_CACHE = TensorMemo("id")      # batch vector -> SegmentPtr
 
 
 def segment_ptr(batch, num_graphs=None):
-    key = id(batch)
-    hit = _SP_CACHE.get(key)
-    if hit is not None:
-        ref, version, sp = hit
-        if ref() is batch and version == batch._version and (num_graphs is None or sp.B == int(num_graphs)):
-            return sp
-    sp = SegmentPtr(batch, num_graphs)
-    try:
-        ref = weakref.ref(batch, lambda _r, k=key, c=_SP_CACHE: c.pop(k, None))
-        _SP_CACHE[key] = (ref, batch._version, sp)
-    except TypeError:
-        pass
+    sp = _SP_CACHE.get(batch)
+    if sp is None or not (num_graphs is None or sp.B == int(num_graphs)):
+        sp = SegmentPtr(batch, num_graphs)
+        _SP_CACHE.put(batch, sp)
     return sp
 
 
@@ -1185,43 +1158,35 @@ def manual_seed(seed, device=None):
 
 # A tail kernel that also wrote Dropout(p)(out) — the input of the NEXT message step's conv (layer.py:255-259) — registers the
 # pair here; the block's dropout call on that very tensor then returns the twin instead of launching a kernel.
-_DROPPED: dict = {}      # data_ptr(out) -> (weakref(out), out._version, out_drop, p)
+_DROPPED = TensorMemo("ptr")      # out -> (out_drop, p)
 
 
 def register_dropped(out, out_drop, p):
-    key = out.data_ptr()
-
-    def _gone(ref, k=key):
-        hit = _DROPPED.get(k)
-        if hit is not None and hit[0] is ref:
-            _DROPPED.pop(k, None)
-    _DROPPED[key] = (weakref.ref(out, _gone), out._version, out_drop, float(p))
+    _DROPPED.put(out, (out_drop, float(p)))
 
 
 def take_dropped(x, p):
-    hit = _DROPPED.get(x.data_ptr())
-    if hit is not None and hit[0]() is x and hit[1] == x._version and hit[3] == float(p):
-        _DROPPED.pop(x.data_ptr(), None)
-        return hit[2]
+    hit = _DROPPED.get(x)
+    if hit is not None and hit[1] == float(p):
+        return _DROPPED.take(x)[0]
     return None
+
+
+_ONEHOT_CACHE = TensorMemo("id")      # tensor -> whether its rows are one-hot
 
 
 def rows_are_one_hot(t):
     """True iff every row of ``t`` is one-hot (one host sync, cached per tensor object like the CSR staging).  Inside a stream capture an
     answer that is not cached yet is ``False`` (no read-back there): the contraction path is always correct."""
-    key = id(t)
-    hit = _ONEHOT_CACHE.get(key)
-    if hit is not None and hit[0]() is t and hit[1] == t._version:
-        return hit[2]
+    ok = _ONEHOT_CACHE.get(t)
+    if ok is not None:
+        return ok
     mark = getattr(t, "_glam_onehot", None)      # (flag, tensor version) known from the host side (data.PackedDataset): no read-back
     if not (mark is not None and mark[1] == t._version) and t.is_cuda and torch.cuda.is_current_stream_capturing():
         return False
     ok = bool(mark[0]) if (mark is not None and mark[1] == t._version) else \
         (bool((((t == 0) | (t == 1)).all() & (t.sum(dim=1) == 1).all()).item()) if t.numel() else True)
-    try:
-        _ONEHOT_CACHE[key] = (weakref.ref(t, lambda _r, k=key, c=_ONEHOT_CACHE: c.pop(k, None)), t._version, ok)
-    except TypeError:
-        pass
+    _ONEHOT_CACHE.put(t, ok)
     return ok
 
 
@@ -1275,29 +1240,20 @@ def block_feeds_itself(on=True):
         _FEEDS_ITSELF = prev
 
 
-_NODE_PRODUCTS: dict = {}      # data_ptr(rows) -> (weakref(rows), rows._version, rows.shape, staged, xw, a_ij)
+_NODE_PRODUCTS = TensorMemo("ptr")      # rows -> (rows.shape, staged, xw, a_ij)
 
 
 def register_node_product(rows, staged, xw, a_ij):
     """``xw | a_ij = rows @ [W_node | Wa]`` of the layer whose staged images are ``staged`` exist already (the GRU step that wrote ``rows``
     wrote them): ``_TripletLayer`` takes them when exactly these rows arrive with exactly these images."""
-    key = rows.data_ptr()
-
-    def _gone(ref, k=key):
-        hit = _NODE_PRODUCTS.get(k)
-        if hit is not None and hit[0] is ref:
-            _NODE_PRODUCTS.pop(k, None)
-    _NODE_PRODUCTS[key] = (weakref.ref(rows, _gone), rows._version, tuple(rows.shape), staged, xw, a_ij)
+    _NODE_PRODUCTS.put(rows, (tuple(rows.shape), staged, xw, a_ij))
 
 
 def take_node_product(x, staged):
-    hit = _NODE_PRODUCTS.get(x.data_ptr())
-    if hit is None:
+    hit = _NODE_PRODUCTS.get(x, same_object=False)      # the consumer may hold another tensor object over the same rows
+    if hit is None or hit[0] != tuple(x.shape) or not x.is_contiguous() or hit[1] is not staged or not NODE_IN_GRU:
         return None
-    if hit[0]() is None or hit[1] != x._version or hit[2] != tuple(x.shape) or not x.is_contiguous() or hit[3] is not staged or not NODE_IN_GRU:
-        return None
-    _NODE_PRODUCTS.pop(x.data_ptr(), None)
-    return hit[4], hit[5]
+    return _NODE_PRODUCTS.take(x, same_object=False)[2:]
 
 
 def first_node_spec(conv, N, edge_index, edge_attr):

@@ -6,7 +6,6 @@ scope, the padded-column bookkeeping and the index staging live in ``glam_amd/op
 from __future__ import annotations
 
 import os
-import weakref
 
 import torch
 
@@ -543,9 +542,6 @@ def nnconv_edge_conditioned(x, edge_attr, gi, w0, b0, w1, b1, root, bias, mean=T
             return _NNConvEC.apply(x, edge_attr, gi, w0, b0, wstack, bias, mean, True)
         return _NNConvEC.apply(x, edge_attr, gi, w0, b0, wstack, bias, mean), x
     return _NNConvEC.apply(x, edge_attr, gi, w0, b0, wstack, bias, mean)
-
-
-_ONEHOT_CACHE: dict = {}
 
 
 class _PairPool(torch.autograd.Function):

@@ -522,3 +522,101 @@ def test_parked_weight_gradient_sets_are_launched_by_the_first_application(monke
     assert ops._parks(scope, 512) and not ops._parks(scope, 511) and not ops._parks(None, 4096)
     monkeypatch.setattr(ops, "GRU_WGRAD_BATCH", False)
     assert not ops._parks(scope, 4096)
+
+
+@pytest.mark.parametrize("kind", ["id", "ptr"])
+def test_tensor_memo_entries_follow_the_tensors_life_and_version(kind):
+    """glam_amd._memo.TensorMemo on CPU tensors: an entry goes when its tensor dies, misses after an in-place write until registered
+    again, ``take`` pops, another tensor object over the same rows hits only a "ptr" table asked with ``same_object=False``, and an
+    object that takes no weak references is not stored."""
+    import gc
+    from glam_amd._memo import TensorMemo
+    memo = TensorMemo(kind)
+    t = torch.zeros(4, 6)
+    memo.put(t, "a")
+    assert len(memo) == 1 and memo.get(t) == "a" and memo.referent(t) is t
+    t.add_(1)
+    assert memo.get(t) is None and memo.take(t) is None and memo.referent(t) is None and len(memo) == 1
+    memo.put(t, "b")
+    assert memo.get(t) == "b"
+    twin = t.detach()                                    # another object, the same rows, the same version counter
+    assert memo.get(twin) is None and memo.take(twin) is None
+    assert memo.get(twin, same_object=False) == ("b" if kind == "ptr" else None)
+    assert memo.referent(twin) is (t if kind == "ptr" else None)
+    assert memo.take(t) == "b" and memo.take(t) is None and len(memo) == 0
+    memo.put(t, "c")
+    del t, twin
+    gc.collect()
+    assert len(memo) == 0
+    memo.put(torch.zeros(2), 1)
+    memo.clear()
+    assert len(memo) == 0
+
+    class Plain:                                         # (no __weakref__ slot)
+        __slots__ = ("_version",)
+
+        def data_ptr(self):
+            return 64
+    obj = Plain()
+    obj._version = 0
+    memo.put(obj, "x")
+    assert len(memo) == 0 and memo.get(obj) is None
+
+
+@pytest.mark.parametrize("kind", ["id", "ptr"])
+def test_tensor_memo_finaliser_spares_a_newer_entry_under_the_same_key(kind):
+    """Ids and addresses come back.  Tensor B registered under the key tensor A still holds: when A dies, its finaliser must leave B's
+    entry alone.  Replacing an entry drops its weakref, and a dead weakref calls nothing, so A's finaliser only runs at all while
+    something else still holds A's entry: the test holds it."""
+    import gc
+    from glam_amd._memo import TensorMemo
+    memo = TensorMemo(kind)
+    a = torch.zeros(4, 6)
+    b = a.detach()                                       # shares a's data_ptr and keeps the storage, not a, alive
+    if kind == "id":
+        memo._key = lambda t: 7                          # two live objects never share an id: force the slot
+    memo.put(a, "a")
+    held = list(memo._d.values())                        # A's entry, and with it A's weakref, outlives its place in the table
+    memo.put(b, "b")
+    del a
+    gc.collect()
+    assert held[0][0]() is None and len(memo) == 1 and memo.get(b) == "b"
+    del b
+    gc.collect()
+    assert len(memo) == 0
+
+
+def test_tensor_side_tables_of_ops_keep_their_hit_conditions(monkeypatch):
+    """The tables of glam_amd.ops behind TensorMemo, on CPU tensors (pure bookkeeping): the padded-view registry does not pop and ends
+    with a write to the base; a dropped twin goes to the very tensor it was registered for with the very ``p``, once; a node product
+    goes to any tensor object over the registered rows with the same shape and the same staged images, once."""
+    xp = torch.zeros(6, 48)
+    v = ops.slice_cols(xp, 45)
+    assert ops.padded_base(v) is xp and ops.padded_base(v) is xp
+    xp.add_(1.0)
+    assert ops.padded_base(v) is None
+
+    out, twin = torch.randn(5, 8), torch.randn(5, 8)
+    ops.register_dropped(out, twin, 0.2)
+    assert ops.take_dropped(out, 0.1) is None                       # another rate: no hit, and the entry stays
+    assert ops.take_dropped(out.detach(), 0.2) is None              # another tensor object
+    assert ops.take_dropped(out, 0.2) is twin and ops.take_dropped(out, 0.2) is None
+    ops.register_dropped(out, twin, 0.2)
+    out.mul_(2.0)
+    assert ops.take_dropped(out, 0.2) is None
+
+    monkeypatch.setattr(ops, "NODE_IN_GRU", True)
+    rows, staged, xw, a_ij = torch.randn(16, 24), object(), torch.randn(16, 96), torch.randn(16, 8)
+    ops.register_node_product(rows, staged, xw, a_ij)
+    assert ops.take_node_product(rows, object()) is None            # other staged images
+    assert ops.take_node_product(rows.view(8, 48), staged) is None  # another shape over the same address
+    assert ops.take_node_product(rows.as_strided((16, 24), (1, 16)), staged) is None      # the same shape, not contiguous
+    got = ops.take_node_product(rows.detach(), staged)              # another tensor object over the same rows: a hit
+    assert got is not None and got[0] is xw and got[1] is a_ij
+    assert ops.take_node_product(rows, staged) is None              # taken
+    ops.register_node_product(rows, staged, xw, a_ij)
+    monkeypatch.setattr(ops, "NODE_IN_GRU", False)
+    assert ops.take_node_product(rows, staged) is None
+    monkeypatch.setattr(ops, "NODE_IN_GRU", True)
+    rows.add_(1.0)
+    assert ops.take_node_product(rows, staged) is None

@@ -2,6 +2,10 @@
 
 The library is the product: if it is missing, or a tensor is not resident on a HIP device,
 every op raises — there is no CPU or eager-PyTorch fallback behind these entry points.
+
+Two views of the one library: ``load()`` is the raw binding, whose entry points return their status codes (``0`` or ``GLAM_E_*``)
+for the caller to compare; ``api()`` is what the package itself calls — every status-returning entry point raises ``GlamHipError``
+with the library's message by itself, so a call site is a plain ``lib.glam_x(...)`` and a launch's error cannot be dropped.
 """
 from __future__ import annotations
 
@@ -189,15 +193,32 @@ SIGNATURES = {
     "glam_triplet_layer_bwd": (_i32, [_vp] * 14 + [_i64, _i64, _i32, _i32, _i32, _f32] + [_vp] * 4 + [_sz, _vp]),
 }
 
-_lib = None
+# An ``int`` return is a status (0 = ok, < 0 = GLAM_E_*) that api() checks — the default, so that a new entry point is safe without
+# anyone remembering anything.  The exceptions, whose ``int`` is a VALUE and passes through api() as it is:
+VALUE_RETURNS = frozenset(
+    ["glam_abi_version", "glam_route_enabled", "glam_prof_end", "glam_ce_loss_max_classes", "glam_adam_max_tensors", "glam_ranger_max_tensors"]
+    + [f"glam_{s}_supported" for s in ("nnconv_ec", "pair_pool_add", "triplet_fwd_ell", "triplet_layer_ws", "triplet_layer_infer", "relation_mlp",
+                                       "gru_fused", "gru_ws", "linear_narrow", "ts_gemm_relu", "ts_gemm_rrelu", "graph_norm_drop")])
+
+_lib = _api = None
 
 
 class GlamHipError(RuntimeError):
     pass
 
 
+def _bind(checked):
+    lib = ctypes.CDLL(LIB_PATH)
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(lib, name)          # AttributeError if the ABI and the header disagree
+        fn.restype, fn.argtypes = res, args
+        if checked and res is _i32 and name not in VALUE_RETURNS:
+            fn.errcheck = _raise_on_status
+    return lib
+
+
 def load():
-    """Load libglam_hip.so (after torch, so that both share one HIP runtime)."""
+    """Load libglam_hip.so (after torch, so that both share one HIP runtime): the RAW binding, every entry point returns its code."""
     global _lib
     if _lib is not None:
         return _lib
@@ -205,15 +226,23 @@ def load():
         raise GlamHipError(
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C glam_amd/csrc`). glam_amd has no CPU / eager fallback.")
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if the ABI and the header disagree
-        fn.restype, fn.argtypes = res, args
+    lib = _bind(checked=False)
     if lib.glam_abi_version() != ABI_VERSION:
         raise GlamHipError(f"{LIB_PATH}: ABI version {lib.glam_abi_version()}, this package binds version {ABI_VERSION} "
                            "(a stale build: `make -C glam_amd/csrc`)")
     _lib = lib
     return lib
+
+
+def api():
+    """The CHECKED view of the same library, which the package calls: a status-returning entry point raises ``GlamHipError`` by itself
+    (ctypes ``errcheck`` on a second handle of the one loaded library: its own function objects, and no Python frame around a call);
+    the value-returning ones (``size_t`` queries, ``glam_last_error``, VALUE_RETURNS) are those of ``load()``."""
+    global _api
+    if _api is None:
+        load()
+        _api = _bind(checked=True)
+    return _api
 
 
 def route_enabled(name):
@@ -225,11 +254,20 @@ def route_enabled(name):
     return rc == 1
 
 
+def _failure(what, rc):
+    return GlamHipError(f"{what} failed (code {rc}): {load().glam_last_error().decode('utf-8', 'replace')}")
+
+
 def check(rc, what):
-    if rc == 0:
-        return
-    msg = load().glam_last_error().decode("utf-8", "replace")
-    raise GlamHipError(f"{what} failed (code {rc}): {msg}")
+    """Raise for the non-zero status ``rc`` of the raw call named ``what`` (callers of ``load()``; ``api()`` needs none)."""
+    if rc != 0:
+        raise _failure(what, rc)
+
+
+def _raise_on_status(rc, fn, args):
+    if rc != 0:
+        raise _failure(fn.__name__, rc)
+    return rc
 
 
 class kernel_timer:
@@ -240,18 +278,18 @@ class kernel_timer:
         self.capacity, self.n = capacity, 0
 
     def __enter__(self):
-        check(load().glam_prof_begin(self.capacity), "glam_prof_begin")
+        api().glam_prof_begin(self.capacity)
         return self
 
     def __exit__(self, *exc):
-        self.n = load().glam_prof_end()
+        self.n = api().glam_prof_end()
         return False
 
     def records(self):
-        lib, out = load(), []
+        lib, out = api(), []
         name, grid, us = ctypes.create_string_buffer(128), ctypes.c_int32(), ctypes.c_float()
         for i in range(self.n):
-            check(lib.glam_prof_read(i, name, 128, ctypes.byref(grid), ctypes.byref(us)), "glam_prof_read")
+            lib.glam_prof_read(i, name, 128, ctypes.byref(grid), ctypes.byref(us))
             out.append((name.value.decode(), int(grid.value), float(us.value)))
         return out
 

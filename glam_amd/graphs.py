@@ -352,14 +352,14 @@ class GraphedCallable:
     # -- recognition -----------------------------------------------------------------------------------------------------------
     def _fingerprint(self, tensors):
         from . import _lib
-        lib = _lib.load()
+        lib = _lib.api()
         dev = tensors[0].device
         if self._fp is None or self._fp.device != dev:
             self._fp = torch.empty(1, dtype=torch.int64, device=dev)
         n = len(tensors)
         bufs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
         sizes = (ctypes.c_int64 * n)(*[t.numel() * t.element_size() for t in tensors])
-        _lib.check(lib.glam_batch_fingerprint(n, bufs, sizes, self._fp.data_ptr(), _lib.stream()), "glam_batch_fingerprint")
+        lib.glam_batch_fingerprint(n, bufs, sizes, self._fp.data_ptr(), _lib.stream())
         return int(self._fp.item())                  # (the one read-back of a recognised call)
 
     def _key(self, module, datas, index):

@@ -63,14 +63,12 @@ class _MeanLoss(torch.autograd.Function):
         if target.dtype != torch.float32:
             target = target.to(torch.float32)
         p, t = f32c(pred, "prediction"), f32c(target, "target")
-        lib, dev, n = _lib.load(), pred.device, pred.numel()
+        lib, dev, n = _lib.api(), pred.device, pred.numel()
         out = torch.empty(2, dtype=torch.float32, device=dev)             # loss | 1 / count
         grad = torch.empty_like(p)
         ws = _workspace(dev, lib) if n > 1024 else None
-        rc = lib.glam_loss_fwd(ptr(p), ptr(t), n, kind, int(masked), out.data_ptr(), out.data_ptr() + 4, ptr(grad), ptr(ws),
-                               ws.numel() if ws is not None else 0, ptr(_ticket(dev)) if n > 1024 else None, _stream(dev))
-        if rc != 0:
-            raise GlamHipError(f"glam_loss_fwd failed (code {rc}): {lib.glam_last_error().decode()}")
+        lib.glam_loss_fwd(ptr(p), ptr(t), n, kind, int(masked), out.data_ptr(), out.data_ptr() + 4, ptr(grad), ptr(ws),
+                          ws.numel() if ws is not None else 0, ptr(_ticket(dev)) if n > 1024 else None, _stream(dev))
         ctx.save_for_backward(grad, out)
         ctx.shape = pred.shape
         return out[0]
@@ -84,12 +82,10 @@ class _MeanLoss(torch.autograd.Function):
 def _scale_back(ctx, g_up):
     """d_input = grad * g_up / denominator (``glam_loss_bwd``) from the (grad, [loss | 1 / denominator]) the forward saved."""
     grad, out = ctx.saved_tensors
-    lib, dev = _lib.load(), grad.device
+    lib, dev = _lib.api(), grad.device
     g_up = f32c(g_up.reshape(1), "loss gradient")
     d_pred = torch.empty_like(grad)
-    rc = lib.glam_loss_bwd(ptr(grad), out.data_ptr() + 4, ptr(g_up), grad.numel(), ptr(d_pred), _stream(dev))
-    if rc != 0:
-        raise GlamHipError(f"glam_loss_bwd failed (code {rc}): {lib.glam_last_error().decode()}")
+    lib.glam_loss_bwd(ptr(grad), out.data_ptr() + 4, ptr(g_up), grad.numel(), ptr(d_pred), _stream(dev))
     return d_pred.view(ctx.shape)
 
 
@@ -101,7 +97,7 @@ class _CrossEntropy(torch.autograd.Function):
             raise GlamHipError(f"cross entropy: logits [B, C] and int64 labels [B] expected, got {tuple(x.shape)} and "
                                f"{tuple(y.shape)} {y.dtype}")
         B, C = x.shape
-        lib, dev = _lib.load(), x.device
+        lib, dev = _lib.api(), x.device
         if B < 1 or not 1 <= C <= _max_classes():
             raise GlamHipError(f"cross entropy: B = {B}, C = {C} outside the kernel's range (B >= 1, 1 <= C <= {_max_classes()})")
         x, y = f32c(x, "logits"), y.contiguous()
@@ -112,10 +108,8 @@ class _CrossEntropy(torch.autograd.Function):
         out = torch.empty(2, dtype=torch.float32, device=dev)             # loss | 1 / denominator
         grad = torch.empty_like(x)
         ws = _workspace(dev, lib)
-        rc = lib.glam_ce_loss_fwd(ptr(x), ptr(y), ptr(weight), B, C, int(ignore_index), int(focal), float(alpha), float(gamma),
-                                  out.data_ptr(), out.data_ptr() + 4, ptr(grad), ptr(ws), ws.numel(), ptr(_ticket(dev)), _stream(dev))
-        if rc != 0:
-            raise GlamHipError(f"glam_ce_loss_fwd failed (code {rc}): {lib.glam_last_error().decode()}")
+        lib.glam_ce_loss_fwd(ptr(x), ptr(y), ptr(weight), B, C, int(ignore_index), int(focal), float(alpha), float(gamma),
+                             out.data_ptr(), out.data_ptr() + 4, ptr(grad), ptr(ws), ws.numel(), ptr(_ticket(dev)), _stream(dev))
         ctx.save_for_backward(grad, out)
         ctx.shape = x.shape
         return out[0]
@@ -175,7 +169,7 @@ def _elementwise_ok(mod, input, target):
 
 
 def _max_classes():
-    return _lib.load().glam_ce_loss_max_classes()
+    return _lib.api().glam_ce_loss_max_classes()
 
 
 def _class_logits_ok(input, target):

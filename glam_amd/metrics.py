@@ -69,10 +69,6 @@ def _code(dtype):
     return 1 if dtype == torch.float64 else 0
 
 
-def _run(fn, *args):
-    _lib.check(fn(*args), fn.__name__)
-
-
 def _record(rec):
     host = rec.cpu()
     return host[:16].tolist(), host[16:].view(torch.float64).tolist()
@@ -86,7 +82,7 @@ def _check_n(n, what):
 def _binary(y_true, y_score, y_pred, masked, pred_mode, threshold=0.5, alpha=20.0, fractions=(), multi_task=False, negate=False):
     """One call of glam_metrics_binary; returns (int fields, float fields, n rows)."""
     dev = _device()
-    lib = _lib.load()
+    lib = _lib.api()
     yt, ys = _to_device(y_true, dev, "y_true"), _to_device(y_score, dev, "y_score")
     yp = _to_device(y_pred, dev, "y_pred") if y_pred is not None else None
     if multi_task:
@@ -109,9 +105,9 @@ def _binary(y_true, y_score, y_pred, masked, pred_mode, threshold=0.5, alpha=20.
     ws = torch.empty(max(lib.glam_metrics_workspace_bytes(n, max(tasks, 1), 0), 1), dtype=torch.uint8, device=dev)
     rec = torch.empty(32, dtype=torch.int64, device=dev)
     pct = (ctypes.c_double * 5)(*fractions)
-    _run(lib.glam_metrics_binary, _lib.ptr(score), _lib.ptr(label), _lib.ptr(pred), _code(score.dtype), _code(ldt), n, tasks,
-         int(masked), 0 if pred is not None else pred_mode, float(threshold), float(alpha), pct, len(fractions), _lib.ptr(ws), ws.numel(),
-         _lib.ptr(rec), _lib.stream())
+    lib.glam_metrics_binary(_lib.ptr(score), _lib.ptr(label), _lib.ptr(pred), _code(score.dtype), _code(ldt), n, tasks, int(masked),
+                            0 if pred is not None else pred_mode, float(threshold), float(alpha), pct, len(fractions), _lib.ptr(ws), ws.numel(),
+                            _lib.ptr(rec), _lib.stream())
     iv, dv = _record(rec)
     return iv, dv, n
 
@@ -164,7 +160,7 @@ def binary_metrics_multi_target_nan(y_true, y_score, y_pred=None, nan_fill=-1, t
 
 def _regression(y_true, y_pred):
     dev = _device()
-    lib = _lib.load()
+    lib = _lib.api()
     y, f = _to_device(y_true, dev, "y_true").reshape(-1), _to_device(y_pred, dev, "y_pred").reshape(-1)
     if y.shape != f.shape:
         raise ValueError(f"Found input variables with inconsistent numbers of samples: [{y.numel()}, {f.numel()}]")
@@ -174,7 +170,7 @@ def _regression(y_true, y_pred):
     y, f = y.to(dt).contiguous(), f.to(dt).contiguous()
     ws = torch.empty(max(lib.glam_metrics_workspace_bytes(n, 1, 0), 1), dtype=torch.uint8, device=dev)
     rec = torch.empty(32, dtype=torch.int64, device=dev)
-    _run(lib.glam_metrics_regression, _lib.ptr(y), _lib.ptr(f), _code(dt), n, _lib.ptr(ws), ws.numel(), _lib.ptr(rec), _lib.stream())
+    lib.glam_metrics_regression(_lib.ptr(y), _lib.ptr(f), _code(dt), n, _lib.ptr(ws), ws.numel(), _lib.ptr(rec), _lib.stream())
     iv, dv = _record(rec)
     return iv, dv, n
 
@@ -250,7 +246,7 @@ def multi_class_metrics(y_true, y_score, y_pred=None):
     """``y_score (N, n_class)``, ``y_true (N,)`` in [0, n_class): accuracy and macro precision / recall / F1 over the classes that occur
     in the labels or the predictions (prediction: the first argmax of each row)."""
     dev = _device()
-    lib = _lib.load()
+    lib = _lib.api()
     yt = _to_device(y_true, dev, "y_true").reshape(-1)
     ys = _to_device(y_score, dev, "y_score")
     yp = _to_device(y_pred, dev, "y_pred").reshape(-1) if y_pred is not None else None
@@ -269,8 +265,8 @@ def multi_class_metrics(y_true, y_score, y_pred=None):
         raise ValueError(f"multi_class_metrics: {n_class} classes; the device form supports 1 to 4096")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     rec = torch.empty(32, dtype=torch.int64, device=dev)
-    _run(lib.glam_metrics_multiclass, _lib.ptr(score), _lib.ptr(label), _lib.ptr(pred), _code(score.dtype), _code(ldt), n, n_class,
-         _lib.ptr(ws), ws.numel(), _lib.ptr(rec), _lib.stream())
+    lib.glam_metrics_multiclass(_lib.ptr(score), _lib.ptr(label), _lib.ptr(pred), _code(score.dtype), _code(ldt), n, n_class,
+                                _lib.ptr(ws), ws.numel(), _lib.ptr(rec), _lib.stream())
     iv, dv = _record(rec)
     if iv[2]:
         raise ValueError(f"labels and predictions must be integers in [0, {n_class})")

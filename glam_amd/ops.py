@@ -20,7 +20,7 @@ import weakref
 import torch
 
 from . import _lib
-from ._lib import GlamHipError, check, f32c, ptr, require_device, stream
+from ._lib import GlamHipError, check, f32c, ptr, require_device, stream     # noqa: F401  (check: for callers of the raw binding, as ops.check)
 from ._memo import TensorMemo
 
 
@@ -90,7 +90,7 @@ class GraphIndex:
         ei = edge_index if edge_index.is_contiguous() else edge_index.contiguous()
         self.N, self.E = int(num_nodes), int(ei.size(1))
         self.device = ei.device
-        lib = _lib.load()
+        lib = _lib.api()
         dev = ei.device
         i32 = dict(dtype=torch.int32, device=dev)
         self.rowptr = torch.empty(self.N + 1, **i32)
@@ -104,8 +104,7 @@ class GraphIndex:
         self._ell_t = False            # the same by source (out-degree), for the pipelined backward B2
         self._err = torch.zeros(1, **i32)
         ws = torch.empty(lib.glam_csr_workspace_bytes(self.N, self.E), dtype=torch.uint8, device=dev)
-        check(lib.glam_csr_build(ptr(ei), self.N, self.E, 0, ptr(self.rowptr), ptr(self.src), ptr(self.eid),
-                                 ptr(self._err), ptr(ws), ws.numel(), stream()), "glam_csr_build")
+        lib.glam_csr_build(ptr(ei), self.N, self.E, 0, ptr(self.rowptr), ptr(self.src), ptr(self.eid), ptr(self._err), ptr(ws), ws.numel(), stream())
         # tensors built by glam_amd.data's collation carry a trust mark — the tensor's version counter at marking time: ids valid by
         # construction (checked once on the host when the dataset was packed) and not written since: no read-back, so a loop over
         # fresh batches has no host sync per step
@@ -132,11 +131,10 @@ class GraphIndex:
         if self._ell is False:
             self._ell = None
             if self.N > 0:
-                lib = _lib.load()
+                lib = _lib.api()
                 i32 = dict(dtype=torch.int32, device=self.device)
                 es, ee, ovf = torch.empty(self.N, 4, **i32), torch.empty(self.N, 4, **i32), torch.zeros(1, **i32)
-                check(lib.glam_ell_build(ptr(self.rowptr), ptr(self.src), ptr(self.eid), self.N, ptr(es), ptr(ee), ptr(ovf), stream()),
-                      "glam_ell_build")
+                lib.glam_ell_build(ptr(self.rowptr), ptr(self.src), ptr(self.eid), self.N, ptr(es), ptr(ee), ptr(ovf), stream())
                 if int(ovf.item()) == 0:
                     self._ell = (es, ee)
         return self._ell
@@ -150,11 +148,11 @@ class GraphIndex:
         if self._ell_t is False:
             self._ell_t = None
             if self.N > 0:
-                lib = _lib.load()
+                lib = _lib.api()
                 colptr, dst, eid_t = self.transpose()
                 i32 = dict(dtype=torch.int32, device=self.device)
                 es, ee, ovf = torch.empty(self.N, 4, **i32), torch.empty(self.N, 4, **i32), torch.zeros(1, **i32)
-                check(lib.glam_ell_build(ptr(colptr), ptr(dst), ptr(eid_t), self.N, ptr(es), ptr(ee), ptr(ovf), stream()), "glam_ell_build(T)")
+                lib.glam_ell_build(ptr(colptr), ptr(dst), ptr(eid_t), self.N, ptr(es), ptr(ee), ptr(ovf), stream())
                 if int(ovf.item()) == 0:
                     self._ell_t = (es, ee)
         return self._ell_t
@@ -162,7 +160,7 @@ class GraphIndex:
     def transpose(self):
         """CSR by source (built on first backward)."""
         if self._t is None:
-            lib = _lib.load()
+            lib = _lib.api()
             i32 = dict(dtype=torch.int32, device=self.device)
             colptr, dst, eid_t = torch.empty(self.N + 1, **i32), torch.empty(self.E, **i32), torch.empty(self.E, **i32)
             ws = torch.empty(lib.glam_csr_workspace_bytes(self.N, self.E), dtype=torch.uint8, device=self.device)
@@ -173,8 +171,7 @@ class GraphIndex:
                 ei = torch.empty(2, self.E, dtype=torch.int64, device=self.device)
                 ei[0, self.eid.long()] = self.src.long()
                 ei[1, self.eid.long()] = dst64
-            check(lib.glam_csr_build(ptr(ei), self.N, self.E, 1, ptr(colptr), ptr(dst), ptr(eid_t),
-                                     ptr(self._err), ptr(ws), ws.numel(), stream()), "glam_csr_build(T)")
+            lib.glam_csr_build(ptr(ei), self.N, self.E, 1, ptr(colptr), ptr(dst), ptr(eid_t), ptr(self._err), ptr(ws), ws.numel(), stream())
             self._t = (colptr, dst, eid_t)
         return self._t
 
@@ -247,7 +244,7 @@ def prestage(triplet=None, images=(), gru_pre=()):
     scope = _SCOPE
     if scope is None or not PRESTAGE:
         return 0
-    lib = _lib.load()
+    lib = _lib.api()
     f = None
     args_t = [None] * 5 + [0] * 5 + [None]
     built = 0
@@ -291,7 +288,7 @@ def prestage(triplet=None, images=(), gru_pre=()):
     wp = (ctypes.c_void_p * max(n, 1))(*[ptr(j[0]) for j in jobs])
     ip = (ctypes.c_void_p * max(n, 1))(*[ptr(j[2]) for j in jobs])
     dims = (ctypes.c_int32 * (4 * max(n, 1)))(*[v for j in jobs for v in j[1]])
-    check(lib.glam_prestage(*args_t, n, wp, dims, ip, stream()), "glam_prestage")
+    lib.glam_prestage(*args_t, n, wp, dims, ip, stream())
     return built
 
 
@@ -323,8 +320,7 @@ def _pad_group_launch(src, dst, specs, backward):
     n = len(specs)
     vp = ctypes.c_void_p * n
     dims = (ctypes.c_int32 * (5 * n))(*[v for sp in specs for v in sp])
-    check(_lib.load().glam_pad_group(n, vp(*[None if t is None else t.data_ptr() for t in src]), vp(*[t.data_ptr() for t in dst]), dims,
-                                     backward, stream()), "glam_pad_group")
+    _lib.api().glam_pad_group(n, vp(*[None if t is None else t.data_ptr() for t in src]), vp(*[t.data_ptr() for t in dst]), dims, backward, stream())
 
 
 class _CatCols(torch.autograd.Function):
@@ -454,8 +450,7 @@ class SegmentPtr:
             raise IndexError(f"batch must be non-decreasing with ids in [0, num_graphs) (num_graphs = {self.B})")
         self.ptr = torch.empty(self.B + 1, dtype=torch.int32, device=batch.device)
         err = torch.zeros(1, dtype=torch.int32, device=batch.device)
-        check(_lib.load().glam_batch_ptr(ptr(batch.contiguous()), self.N, self.B, ptr(self.ptr), ptr(err), stream()),
-              "glam_batch_ptr")
+        _lib.api().glam_batch_ptr(ptr(batch.contiguous()), self.N, self.B, ptr(self.ptr), ptr(err), stream())
         poll_checks()
         if validate and getattr(batch, "_glam_trusted", None) != batch._version:
             _check_flag(err, "batch must be non-decreasing with ids in [0, num_graphs)")
@@ -487,18 +482,16 @@ class _TripletAggregate(torch.autograd.Function):
                                f"edge_attr={tuple(edge_attr.shape)} M={tuple(M.shape)} for N={N} E={E} H={H} Cp={Cp} De={De}")
         aggr = torch.empty(N, H * Cp, dtype=torch.float32, device=xw.device)
         stats = torch.empty(N, 8, dtype=torch.float32, device=xw.device)
-        lib = _lib.load()
+        lib = _lib.api()
         # Batches whose working set leaves the 256 MiB LLC: the software-pipelined kernel (bit-identical; 0.56 vs 0.44 of the HBM
         # peak at B = 16 384).  Below that the general kernel's three waves per SIMD win (9.4 vs 10.4 us at B = 1 024).
         ell = gi.ell() if (emul and GraphIndex.wants_ell(N, H, Cp) and lib.glam_triplet_fwd_ell_supported(H, Cp, De)) else None
         if ell is not None:
-            check(lib.glam_triplet_fwd_ell(ptr(xw), ptr(a_ij), ptr(edge_attr), ptr(w_edge), ptr(M), ptr(ell[0]), ptr(ell[1]), N, E, H, Cp, De,
-                                           float(slope), int(rows_are_one_hot(edge_attr)), ptr(aggr), ptr(stats), 0, stream()),
-                  "glam_triplet_fwd_ell")
+            lib.glam_triplet_fwd_ell(ptr(xw), ptr(a_ij), ptr(edge_attr), ptr(w_edge), ptr(M), ptr(ell[0]), ptr(ell[1]), N, E, H, Cp, De,
+                                     float(slope), int(rows_are_one_hot(edge_attr)), ptr(aggr), ptr(stats), 0, stream())
         else:
-            check(lib.glam_triplet_fwd(ptr(xw), ptr(a_ij), ptr(edge_attr), ptr(w_edge), ptr(M), ptr(gi.rowptr),
-                                       ptr(gi.src), ptr(gi.eid), N, E, H, Cp, De, int(emul), float(slope),
-                                       ptr(aggr), ptr(stats), stream()), "glam_triplet_fwd")
+            lib.glam_triplet_fwd(ptr(xw), ptr(a_ij), ptr(edge_attr), ptr(w_edge), ptr(M), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), N, E, H, Cp, De,
+                                 int(emul), float(slope), ptr(aggr), ptr(stats), stream())
         ctx.save_for_backward(xw, a_ij, edge_attr, w_edge, M, aggr, stats)
         ctx.gi, ctx.dims = gi, (H, Cp, De, int(emul), float(slope))
         return aggr
@@ -510,7 +503,7 @@ class _TripletAggregate(torch.autograd.Function):
         gi = ctx.gi
         H, Cp, De, emul, slope = ctx.dims
         N, E = gi.N, gi.E
-        lib = _lib.load()
+        lib = _lib.api()
         d_aggr = f32c(d_aggr, "d_aggr")
         colptr, dst, eid_t = gi.transpose()
         dev = xw.device
@@ -520,10 +513,9 @@ class _TripletAggregate(torch.autograd.Function):
         d_M = torch.empty_like(M)
         d_ea = torch.zeros_like(edge_attr) if ctx.needs_input_grad[2] else None
         ws = torch.empty(lib.glam_triplet_bwd_workspace_bytes(N, E, H, Cp, De), dtype=torch.uint8, device=dev)
-        check(lib.glam_triplet_bwd(ptr(xw), ptr(a_ij), ptr(edge_attr), ptr(w_edge), ptr(M), ptr(aggr), ptr(stats),
-                                   ptr(d_aggr), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst),
-                                   ptr(eid_t), N, E, H, Cp, De, emul, slope, ptr(d_xw), ptr(d_a_ij), ptr(d_w_edge),
-                                   ptr(d_M), ptr(d_ea), ptr(ws), ws.numel(), stream()), "glam_triplet_bwd")
+        lib.glam_triplet_bwd(ptr(xw), ptr(a_ij), ptr(edge_attr), ptr(w_edge), ptr(M), ptr(aggr), ptr(stats), ptr(d_aggr), ptr(gi.rowptr), ptr(gi.src),
+                             ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t), N, E, H, Cp, De, emul, slope, ptr(d_xw), ptr(d_a_ij), ptr(d_w_edge),
+                             ptr(d_M), ptr(d_ea), ptr(ws), ws.numel(), stream())
         return d_xw, d_a_ij, d_ea, d_w_edge, d_M, None, None, None, None, None, None
 
 
@@ -719,7 +711,7 @@ class _TripletLayer(torch.autograd.Function):
         Dp = ea_p.size(1)
         if gi.N != N or ea_p.size(0) != gi.E or wn.shape != (C, H * C) or wsc.shape != (H * C, C) or Cp != (C + 3) // 4 * 4:
             raise GlamHipError("triplet_layer: shape mismatch")
-        lib, dev = _lib.load(), x_p.device
+        lib, dev = _lib.api(), x_p.device
         HC = H * Cp
         f = dict(dtype=torch.float32, device=dev)
         ctx.carried = carry is not None
@@ -729,8 +721,7 @@ class _TripletLayer(torch.autograd.Function):
         ctx.set_materialize_grads(False)     # the carry of the block's LAST application has no gradient yet: None, not a zero fill
         def build():
             buf = torch.empty(lib.glam_triplet_staged_floats(H, Cp, Dp), **f)
-            check(lib.glam_triplet_stage_params(ptr(wn), ptr(we), ptr(att), ptr(wsc), ptr(bias), C, H, De, Cp, Dp, ptr(buf),
-                                                stream()), "glam_triplet_stage_params")
+            lib.glam_triplet_stage_params(ptr(wn), ptr(we), ptr(att), ptr(wsc), ptr(bias), C, H, De, Cp, Dp, ptr(buf), stream())
             return buf
 
         # the same conv is applied message_steps times per model forward: one staging per pass (see _WeightScope); with
@@ -752,13 +743,11 @@ class _TripletLayer(torch.autograd.Function):
         infer = INFER_FWD and no_backward and (ell is not None or bool(lib.glam_triplet_layer_infer_supported(H, Cp, Dp)))
         aggr, stats = (None, None) if infer else (torch.empty(N, HC, **f), torch.empty(N, 8, **f))
         if ell is not None:
-            check(lib.glam_triplet_layer_fwd_ell(None if given is not None else ptr(x_p), ptr(ea_p), ptr(staged), ptr(ell[0]), ptr(ell[1]), 1, N,
-                                                 gi.E, H, Cp, Dp, float(slope), ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats), ptr(out), stream()),
-                  "glam_triplet_layer_fwd_ell")
+            lib.glam_triplet_layer_fwd_ell(None if given is not None else ptr(x_p), ptr(ea_p), ptr(staged), ptr(ell[0]), ptr(ell[1]), 1, N,
+                                           gi.E, H, Cp, Dp, float(slope), ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats), ptr(out), stream())
         else:
-            check(lib.glam_triplet_layer_fwd(ptr(x_p), ptr(ea_p), ptr(staged), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid),
-                                             N, gi.E, H, Cp, Dp, float(slope), ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats), ptr(out),
-                                             stream()), "glam_triplet_layer_fwd")
+            lib.glam_triplet_layer_fwd(ptr(x_p), ptr(ea_p), ptr(staged), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), N, gi.E, H, Cp, Dp, float(slope),
+                                       ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats), ptr(out), stream())
         if not infer:
             ctx.save_for_backward(x_p, ea_p, wn, we, att, staged, xw, a_ij, aggr, stats)
         ctx.gi, ctx.dims = gi, (C, H, De, Cp, Dp, float(slope))
@@ -774,7 +763,7 @@ class _TripletLayer(torch.autograd.Function):
         C, H, De, Cp, Dp, slope = ctx.dims
         gi, scope = ctx.gi, ctx.scope
         N, E = gi.N, gi.E
-        lib, dev = _lib.load(), x_p.device
+        lib, dev = _lib.api(), x_p.device
         groups = None
         if d_out is None:
             # the layer's output was not used: only the skip connection / the carry pass through — on the first application together
@@ -800,11 +789,11 @@ class _TripletLayer(torch.autograd.Function):
                 in_kernel = d_alias is not None and ell_t is not None and _lib.route_enabled("x3")   # (warp-specialised route only)
                 addend = f32c(d_alias, "d_identity") if in_kernel else None
                 info = (ctypes.c_int64 * 4)()
-                check(lib.glam_triplet_layer_bwd_data_ell(ptr(x_p), ptr(ea_p), ptr(staged), ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats), ptr(d_out),
-                                                          ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t), N, E, C, H, De,
-                                                          Cp, Dp, slope, ptr(d_x), ptr(ell_f[0]) if ell_f else None, ptr(ell_f[1]) if ell_f else None,
-                                                          ptr(ell_t[0]) if ell_t else None, ptr(ell_t[1]) if ell_t else None, 1 if ell_t else 0,
-                                                          None, ptr(ws), ws.numel(), ptr(addend), info, stream()), "glam_triplet_layer_bwd_data_ell")
+                lib.glam_triplet_layer_bwd_data_ell(ptr(x_p), ptr(ea_p), ptr(staged), ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats), ptr(d_out),
+                                                    ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t), N, E, C, H, De,
+                                                    Cp, Dp, slope, ptr(d_x), ptr(ell_f[0]) if ell_f else None, ptr(ell_f[1]) if ell_f else None,
+                                                    ptr(ell_t[0]) if ell_t else None, ptr(ell_t[1]) if ell_t else None, 1 if ell_t else 0,
+                                                    None, ptr(ws), ws.numel(), ptr(addend), info, stream())
                 if d_alias is not None and not in_kernel:
                     d_x = d_x.add_(d_alias)
                 groups = _park(scope, "triplet", wn, ctx.first_app, (ws, tuple(info), x_p, aggr, d_out))
@@ -822,10 +811,9 @@ class _TripletLayer(torch.autograd.Function):
                 ws2 = torch.empty(2 * lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
                 infos = (ctypes.c_int64 * (4 * n))(*[v for t in grp for v in t[1]])
                 arr = lambda i: (vp * n)(*[t[i].data_ptr() for t in grp])
-                check(lib.glam_triplet_layer_param_grads_sets(n, arr(0), infos, arr(2), arr(3), arr(4), N, C, H, De, Cp, Dp, ptr(wn), ptr(we),
-                                                              ptr(att), ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(o[3]), ptr(o[4]), ptr(c[0]), ptr(c[1]),
-                                                              ptr(c[2]), ptr(c[3]), ptr(c[4]), ptr(ws2), ws2.numel(), stream()),
-                      "glam_triplet_layer_param_grads_sets")
+                lib.glam_triplet_layer_param_grads_sets(n, arr(0), infos, arr(2), arr(3), arr(4), N, C, H, De, Cp, Dp, ptr(wn), ptr(we),
+                                                        ptr(att), ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(o[3]), ptr(o[4]), ptr(c[0]), ptr(c[1]),
+                                                        ptr(c[2]), ptr(c[3]), ptr(c[4]), ptr(ws2), ws2.numel(), stream())
                 carry = out
             return d_x, d_ea, None, None, None, None, None, None, None, None, carry, None, None, None
         # the five parameter gradients are consecutive views of ONE buffer (parameter order), so a data-parallel
@@ -838,25 +826,22 @@ class _TripletLayer(torch.autograd.Function):
             # the skip connection's gradient joins d_x in the epilogue of the d_x product (warp-specialised route)
             in_kernel = d_alias is not None and ell_t is not None and _lib.route_enabled("x3")     # (a 3 x bf16 consumer option)
             addend = f32c(d_alias, "d_identity") if in_kernel else None
-            check(lib.glam_triplet_layer_bwd_params_ell_add(ptr(x_p), ptr(ea_p), ptr(staged), ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats),
-                                                            ptr(d_out), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst),
-                                                            ptr(eid_t), N, E, C, H, De, Cp, Dp, slope, ptr(wn), ptr(we), ptr(att), ptr(d_x),
-                                                            ptr(d_wn), ptr(d_we), ptr(d_att), ptr(d_wsc), ptr(d_bias), ptr(c_wn), ptr(c_we),
-                                                            ptr(c_att), ptr(c_wsc), ptr(c_bias), ptr(ell_f[0]) if ell_f else None,
-                                                            ptr(ell_f[1]) if ell_f else None, ptr(ell_t[0]) if ell_t else None,
-                                                            ptr(ell_t[1]) if ell_t else None, 1 if ell_t else 0,
-                                                            ptr(d_ea), ptr(ws), ws.numel(), ptr(addend), stream()),
-                  "glam_triplet_layer_bwd_params_ell")
+            lib.glam_triplet_layer_bwd_params_ell_add(ptr(x_p), ptr(ea_p), ptr(staged), ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats), ptr(d_out),
+                                                      ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t), N, E, C, H, De, Cp,
+                                                      Dp, slope, ptr(wn), ptr(we), ptr(att), ptr(d_x), ptr(d_wn), ptr(d_we), ptr(d_att), ptr(d_wsc),
+                                                      ptr(d_bias), ptr(c_wn), ptr(c_we), ptr(c_att), ptr(c_wsc), ptr(c_bias),
+                                                      ptr(ell_f[0]) if ell_f else None, ptr(ell_f[1]) if ell_f else None,
+                                                      ptr(ell_t[0]) if ell_t else None, ptr(ell_t[1]) if ell_t else None, 1 if ell_t else 0,
+                                                      ptr(d_ea), ptr(ws), ws.numel(), ptr(addend), stream())
             if d_alias is not None and not in_kernel:
                 d_x = d_x.add_(d_alias)
             if ctx.carried:
                 return d_x, d_ea, None, None, None, None, None, None, None, None, _carried(flatg, d_carry, have_carry), None, None, None
             return d_x, d_ea, d_wn, d_we, d_att, d_wsc, d_bias, None, None, None, None, None, None, None
-        check(lib.glam_triplet_layer_bwd_params(ptr(x_p), ptr(ea_p), ptr(staged), ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats),
-                                                ptr(d_out), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst),
-                                                ptr(eid_t), N, E, C, H, De, Cp, Dp, slope, ptr(wn), ptr(we), ptr(att), ptr(d_x),
-                                                ptr(d_wn), ptr(d_we), ptr(d_att), ptr(d_wsc), ptr(d_bias), ptr(d_ea), ptr(ws),
-                                                ws.numel(), stream()), "glam_triplet_layer_bwd_params")
+        lib.glam_triplet_layer_bwd_params(ptr(x_p), ptr(ea_p), ptr(staged), ptr(xw), ptr(a_ij), ptr(aggr), ptr(stats), ptr(d_out), ptr(gi.rowptr),
+                                          ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t), N, E, C, H, De, Cp, Dp, slope, ptr(wn),
+                                          ptr(we), ptr(att), ptr(d_x), ptr(d_wn), ptr(d_we), ptr(d_att), ptr(d_wsc), ptr(d_bias), ptr(d_ea), ptr(ws),
+                                          ws.numel(), stream())
         if d_alias is not None:
             d_x = d_x.add_(d_alias)
         if ctx.carried:
@@ -907,7 +892,7 @@ def triplet_layer(x_p, ea_p, weight_node, weight_edge, att, weight_scale, bias, 
         # cached); with them the C++ node launches the same warp-specialised kernels as the Python node: one trajectory, bit for bit
         ell_f = ell_b = None
         onehot = False
-        if _ws_route(_lib.load(), gi.N, heads, x_p.size(1), ea_p.size(1), ea_p):
+        if _ws_route(_lib.api(), gi.N, heads, x_p.size(1), ea_p.size(1), ea_p):
             onehot = True
             ell_f = gi.ell()
             if torch.is_grad_enabled():
@@ -958,13 +943,12 @@ class _TripletLayerWide(torch.autograd.Function):
         ctx.carried = carry is not None      # gradient carry of the block's parameters (see _Carry)
         if ctx.carried:
             ctx.set_materialize_grads(False)
-        lib, dev = _lib.load(), x_p.device
+        lib, dev = _lib.api(), x_p.device
         f = dict(dtype=torch.float32, device=dev)
 
         def build():
             buf = torch.empty(lib.glam_triplet_plain_floats(H, Cp, Dp), **f)
-            check(lib.glam_triplet_stage_plain(ptr(wn), ptr(we), ptr(att), ptr(wsc), ptr(bias), C, H, De, Cp, Dp, ptr(buf),
-                                               stream()), "glam_triplet_stage_plain")
+            lib.glam_triplet_stage_plain(ptr(wn), ptr(we), ptr(att), ptr(wsc), ptr(bias), C, H, De, Cp, Dp, ptr(buf), stream())
             return buf
 
         scope = _SCOPE
@@ -986,15 +970,15 @@ class _TripletLayerWide(torch.autograd.Function):
             prestage(None, imgs)
         if mfma:     # the 120 KB-image k_ts_gemm variant: xw and a_ij in one launch
             img1 = _scoped(scope.fwd if scope else None, ("wide-img-node", id(wn)), wn, lambda: _ts_image(Wcat, Cp, HC + 8, False))
-            check(lib.glam_ts_gemm(ptr(x_p), Cp, Cp, None, 0, 0, ptr(img1), None, ptr(xw), HC, HC, ptr(a_ij), 8, 8, N, st), "glam_ts_gemm")
+            lib.glam_ts_gemm(ptr(x_p), Cp, Cp, None, 0, 0, ptr(img1), None, ptr(xw), HC, HC, ptr(a_ij), 8, 8, N, st)
         else:
             torch.matmul(x_p, Wcat[:, :HC], out=xw)                        # layer.py:37
             torch.matmul(x_p, Wcat[:, HC:], out=a_ij)                      # separable attention scalars a_i | a_j
-        check(lib.glam_triplet_fwd(ptr(xw), ptr(a_ij), ptr(ea_p), ptr(We_p), ptr(M), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid),
-                                   N, gi.E, H, Cp, Dp, 1, float(slope), ptr(aggr), ptr(stats), st), "glam_triplet_fwd")
+        lib.glam_triplet_fwd(ptr(xw), ptr(a_ij), ptr(ea_p), ptr(We_p), ptr(M), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid),
+                             N, gi.E, H, Cp, Dp, 1, float(slope), ptr(aggr), ptr(stats), st)
         if _wide_tall_supported(H, Cp):      # layer.py:57-61, 276 -> 92: the long-reduction 3 x bf16 kernel (tall_x3.hip)
             img2 = _scoped(scope.fwd if scope else None, ("wide-img-upd", id(wn)), wn, lambda: _ts_image(Ws_p, HC, Cp, False))
-            check(lib.glam_ts_gemm(ptr(aggr), HC, HC, None, 0, 0, ptr(img2), ptr(bias_p), ptr(out), Cp, Cp, None, 0, 0, N, st), "glam_ts_gemm")
+            lib.glam_ts_gemm(ptr(aggr), HC, HC, None, 0, 0, ptr(img2), ptr(bias_p), ptr(out), Cp, Cp, None, 0, 0, N, st)
         else:
             torch.addmm(bias_p, aggr, Ws_p, out=out)
         ctx.scope = scope
@@ -1011,7 +995,7 @@ class _TripletLayerWide(torch.autograd.Function):
         C, H, De, Cp, Dp, slope = ctx.dims
         gi = ctx.gi
         N, E, HC = gi.N, gi.E, H * Cp
-        lib, dev = _lib.load(), x_p.device
+        lib, dev = _lib.api(), x_p.device
         f = dict(dtype=torch.float32, device=dev)
         d_out = f32c(d_out, "d_out")
         if N == 0:        # an empty batch: every gradient is zero
@@ -1032,20 +1016,19 @@ class _TripletLayerWide(torch.autograd.Function):
         if mfma:
             img3 = _scoped(scope.bwd if scope else None, ("wide-img-dagg", id(wn)), wn, lambda: _ts_image(Ws_p, Cp, HC, True))
             d_aggr = torch.empty(N, HC, **f)
-            check(lib.glam_ts_gemm(ptr(d_out), Cp, Cp, None, 0, 0, ptr(img3), None, ptr(d_aggr), HC, HC, None, 0, 0, N, stream()), "glam_ts_gemm")
+            lib.glam_ts_gemm(ptr(d_out), Cp, Cp, None, 0, 0, ptr(img3), None, ptr(d_aggr), HC, HC, None, 0, 0, N, stream())
         else:
             d_aggr = torch.matmul(d_out, Ws_p.t())
         d_xw, d_a = torch.empty(N, HC, **f), torch.empty(N, 8, **f)
         d_ea = torch.zeros_like(ea_p) if ctx.needs_input_grad[1] else None
         ws = torch.empty(lib.glam_triplet_bwd_workspace_bytes(N, E, H, Cp, Dp), dtype=torch.uint8, device=dev)
-        check(lib.glam_triplet_bwd(ptr(xw), ptr(a_ij), ptr(ea_p), ptr(We_p), ptr(M), ptr(aggr), ptr(stats), ptr(d_aggr),
-                                   ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t), N, E, H, Cp, Dp, 1,
-                                   slope, ptr(d_xw), ptr(d_a), ptr(dstaged[o_we:]), ptr(dstaged[o_m:]), ptr(d_ea), ptr(ws),
-                                   ws.numel(), stream()), "glam_triplet_bwd")
+        lib.glam_triplet_bwd(ptr(xw), ptr(a_ij), ptr(ea_p), ptr(We_p), ptr(M), ptr(aggr), ptr(stats), ptr(d_aggr), ptr(gi.rowptr), ptr(gi.src),
+                             ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t), N, E, H, Cp, Dp, 1, slope, ptr(d_xw), ptr(d_a), ptr(dstaged[o_we:]),
+                             ptr(dstaged[o_m:]), ptr(d_ea), ptr(ws), ws.numel(), stream())
         if _wide_tall_supported(H, Cp):      # d_x = [d_xw | d_a] @ Wcat^T: both sources in one launch
             img4 = _scoped(scope.bwd if scope else None, ("wide-img-dx", id(wn)), wn, lambda: _ts_image(Wcat, HC + 8, Cp, True))
             d_x = torch.empty(N, Cp, **f)
-            check(lib.glam_ts_gemm(ptr(d_xw), HC, HC, ptr(d_a), 8, 8, ptr(img4), None, ptr(d_x), Cp, Cp, None, 0, 0, N, stream()), "glam_ts_gemm")
+            lib.glam_ts_gemm(ptr(d_xw), HC, HC, ptr(d_a), 8, 8, ptr(img4), None, ptr(d_x), Cp, Cp, None, 0, 0, N, stream())
         else:
             d_x = torch.matmul(d_xw, Wcat[:, :HC].t())
             d_x.addmm_(d_a, Wcat[:, HC:].t())
@@ -1064,23 +1047,21 @@ class _TripletLayerWide(torch.autograd.Function):
                 n = len(grp)
                 arr = lambda i: (vp * n)(*[t[i].data_ptr() for t in grp])
                 wws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
-                check(lib.glam_wgrad_gemm_sets2(n, arr(0), HC, HC, None, 0, 0, 1, arr(1), Cp, Cp, N, ptr(dstaged[o_wsb:]), Cp, 1,
-                                                None if g == 0 else ptr(dstaged[o_wsb:]), ptr(wws), wws.numel(), stream()),
-                      "glam_wgrad_gemm_sets2")
+                lib.glam_wgrad_gemm_sets2(n, arr(0), HC, HC, None, 0, 0, 1, arr(1), Cp, Cp, N, ptr(dstaged[o_wsb:]), Cp, 1,
+                                          None if g == 0 else ptr(dstaged[o_wsb:]), ptr(wws), wws.numel(), stream())
                 wws2 = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
-                check(lib.glam_wgrad_gemm_sets2(n, arr(2), HC, HC, arr(3), 8, 8, 0, arr(4), Cp, Cp, N, ptr(dstaged), 1, HC + 8,
-                                                None if g == 0 else ptr(dstaged), ptr(wws2), wws2.numel(), stream()),
-                      "glam_wgrad_gemm_sets2")
+                lib.glam_wgrad_gemm_sets2(n, arr(2), HC, HC, arr(3), 8, 8, 0, arr(4), Cp, Cp, N, ptr(dstaged), 1, HC + 8,
+                                          None if g == 0 else ptr(dstaged), ptr(wws2), wws2.numel(), stream())
         else:
             wws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
             # d_WsB = [aggr | 1]^T d_out ;  d_Wcat = x^T [d_xw | d_a], computed as ([d_xw | d_a]^T x)^T
-            check(lib.glam_wgrad_gemm(ptr(aggr), HC, HC, None, 0, 0, 1, ptr(d_out), Cp, Cp, 0, N, ptr(dstaged[o_wsb:]), Cp, 1,
-                                      ptr(wws), wws.numel(), stream()), "glam_wgrad_gemm")
-            check(lib.glam_wgrad_gemm(ptr(d_xw), HC, HC, ptr(d_a), 8, 8, 0, ptr(x_p), Cp, Cp, 0, N, ptr(dstaged), 1, HC + 8,
-                                      ptr(wws), wws.numel(), stream()), "glam_wgrad_gemm")
+            lib.glam_wgrad_gemm(ptr(aggr), HC, HC, None, 0, 0, 1, ptr(d_out), Cp, Cp, 0, N, ptr(dstaged[o_wsb:]), Cp, 1,
+                                ptr(wws), wws.numel(), stream())
+            lib.glam_wgrad_gemm(ptr(d_xw), HC, HC, ptr(d_a), 8, 8, 0, ptr(x_p), Cp, Cp, 0, N, ptr(dstaged), 1, HC + 8,
+                                ptr(wws), wws.numel(), stream())
         flatg, (d_wn, d_we, d_att, d_wsc, d_bias) = _flat_grads(_triplet_shapes(wn, we, att, H), dev)
-        check(lib.glam_triplet_stage_params_bwd(ptr(wn), ptr(we), ptr(att), ptr(dstaged), C, H, De, Cp, Dp, ptr(d_wn), ptr(d_we),
-                                                ptr(d_att), ptr(d_wsc), ptr(d_bias), stream()), "glam_triplet_stage_params_bwd")
+        lib.glam_triplet_stage_params_bwd(ptr(wn), ptr(we), ptr(att), ptr(dstaged), C, H, De, Cp, Dp, ptr(d_wn), ptr(d_we),
+                                          ptr(d_att), ptr(d_wsc), ptr(d_bias), stream())
         if ctx.carried:       # one add of the flat buffer per application instead of five per-parameter accumulations
             return d_x, d_ea, None, None, None, None, None, None, None, None, _carried(flatg, d_carry), None
         return d_x, d_ea, d_wn, d_we, d_att, d_wsc, d_bias, None, None, None, None, None
@@ -1097,9 +1078,9 @@ def _wide_tall_supported(H, Cp):
 
 def _ts_image(W, K, M, transposed):
     """k_ts_gemm weight image of the logical ``[K, M]`` matrix ``W`` (or ``W^T`` of the stored ``[M, K]`` matrix)."""
-    lib = _lib.load()
+    lib = _lib.api()
     img = torch.empty(lib.glam_ts_gemm_image_bytes(K, M) // 4, dtype=torch.float32, device=W.device)
-    check(lib.glam_ts_gemm_make_image(ptr(W), W.stride(0), int(transposed), K, M, ptr(img), stream()), "glam_ts_gemm_make_image")
+    lib.glam_ts_gemm_make_image(ptr(W), W.stride(0), int(transposed), K, M, ptr(img), stream())
     return img
 
 
@@ -1269,7 +1250,7 @@ def first_node_spec(conv, N, edge_index, edge_attr):
     hit = _SCOPE.fwd.get(("triplet", id(wn), id(conv.weight_edge), id(conv.weight_triplet_att), id(conv.weight_scale), id(conv.bias)))
     if hit is None or hit[0] is not wn or edge_attr is None or edge_attr.dim() != 2 or edge_attr.size(1) != De or edge_attr.dtype != torch.float32:
         return None
-    if not _ws_route(_lib.load(), N, H, C, De, edge_attr) or graph_index(edge_index, N).ell() is None:
+    if not _ws_route(_lib.api(), N, H, C, De, edge_attr) or graph_index(edge_index, N).ell() is None:
         return None
     return hit[1], H * C
 

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from . import ops as _o
-from ._lib import GlamHipError, check, f32c, ptr, require_device, stream
+from ._lib import GlamHipError, f32c, ptr, require_device, stream
 
 # --------------------------------------------------------------------------------------
 # dense linear on the fp32 matrix cores + GRU gate math (MessageBlock remainder)
@@ -45,12 +45,12 @@ class _Linear(torch.autograd.Function):
         M, Kw = w.shape
         if Kw > K or (Kw < K and ctx.needs_input_grad[0]):
             raise GlamHipError("linear: weight wider than the input / narrow weight with a differentiable input")
-        lib, dev = _lib.load(), x.device
+        lib, dev = _lib.api(), x.device
         scope = _o._SCOPE
 
         def build():
             img = torch.empty(lib.glam_ts_gemm_image_bytes(K, M) // 4, dtype=torch.float32, device=dev)
-            check(lib.glam_ts_gemm_make_image(ptr(w), Kw, 1, Kw, M, ptr(img), stream()), "glam_ts_gemm_make_image")
+            lib.glam_ts_gemm_make_image(ptr(w), Kw, 1, Kw, M, ptr(img), stream())
             return img
 
         img = _o._scoped(scope.fwd if scope else None, ("lin", id(w)), w, build)
@@ -68,25 +68,25 @@ class _Linear(torch.autograd.Function):
             eff = torch.empty(2, dtype=torch.int64, device=dev)
             y_drop = torch.empty_like(y) if p > 0 else None
             if nd is not None:
-                check(lib.glam_ts_gemm_act_node(ptr(x), K, K, ptr(img), ptr(b), M, N, 4, lo, hi, p, ptr(_o.rng_state(dev)), ptr(eff), ptr(y), ptr(y_drop),
-                                                ptr(nd[0]), nd[1], ptr(nd[2]), ptr(nd[3]), stream()), "glam_ts_gemm_act_node")
+                lib.glam_ts_gemm_act_node(ptr(x), K, K, ptr(img), ptr(b), M, N, 4, lo, hi, p, ptr(_o.rng_state(dev)), ptr(eff), ptr(y), ptr(y_drop),
+                                          ptr(nd[0]), nd[1], ptr(nd[2]), ptr(nd[3]), stream())
             else:
-                check(lib.glam_ts_gemm_rrelu(ptr(x), K, K, ptr(img), ptr(b), M, N, lo, hi, p, ptr(_o.rng_state(dev)), ptr(eff), ptr(y), ptr(y_drop),
-                                             stream()), "glam_ts_gemm_rrelu")
+                lib.glam_ts_gemm_rrelu(ptr(x), K, K, ptr(img), ptr(b), M, N, lo, hi, p, ptr(_o.rng_state(dev)), ptr(eff), ptr(y), ptr(y_drop),
+                                       stream())
             ctx.save_for_backward(x, w, y)
             ctx.rrelu, ctx.eff = (lo, hi, p), eff
             ctx.has_bias = b is not None
             ctx.scope = scope
             return y, y_drop
         if relu and nd is not None:
-            check(lib.glam_ts_gemm_act_node(ptr(x), K, K, ptr(img), ptr(b), M, N, 1, 0.0, 0.0, 0.0, None, None, ptr(y), None, ptr(nd[0]), nd[1],
-                                            ptr(nd[2]), ptr(nd[3]), stream()), "glam_ts_gemm_act_node")
+            lib.glam_ts_gemm_act_node(ptr(x), K, K, ptr(img), ptr(b), M, N, 1, 0.0, 0.0, 0.0, None, None, ptr(y), None, ptr(nd[0]), nd[1],
+                                      ptr(nd[2]), ptr(nd[3]), stream())
             ctx.save_for_backward(x, w, y)
         elif relu:
-            check(lib.glam_ts_gemm_relu(ptr(x), K, K, ptr(img), ptr(b), ptr(y), M, M, N, stream()), "glam_ts_gemm_relu")
+            lib.glam_ts_gemm_relu(ptr(x), K, K, ptr(img), ptr(b), ptr(y), M, M, N, stream())
             ctx.save_for_backward(x, w, y)
         else:
-            check(lib.glam_ts_gemm(ptr(x), K, K, None, 0, 0, ptr(img), ptr(b), ptr(y), M, M, None, 0, 0, N, stream()), "glam_ts_gemm")
+            lib.glam_ts_gemm(ptr(x), K, K, None, 0, 0, ptr(img), ptr(b), ptr(y), M, M, None, 0, 0, N, stream())
             ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
         ctx.scope = scope
@@ -105,8 +105,8 @@ class _Linear(torch.autograd.Function):
             dy_drop = None if dy_drop is None else f32c(dy_drop, "dy_drop")
             d_pre = torch.empty_like(y_act)
             lo, hi, p = ctx.rrelu
-            check(_lib.load().glam_bias_res_act_rng_bwd(ptr(y_act), ptr(dy), ptr(dy_drop), N, M, _o.ACT_CODES["rrelu"], 0.0, lo, hi, p, ptr(ctx.eff),
-                                                        ptr(d_pre), stream()), "glam_bias_res_act_rng_bwd")
+            _lib.api().glam_bias_res_act_rng_bwd(ptr(y_act), ptr(dy), ptr(dy_drop), N, M, _o.ACT_CODES["rrelu"], 0.0, lo, hi, p, ptr(ctx.eff),
+                                                 ptr(d_pre), stream())
             dy = d_pre
         dy = f32c(dy, "dy")
         y_relu = ctx.saved_tensors[2] if (len(ctx.saved_tensors) == 3 and ctx.rrelu is None) else None
@@ -115,18 +115,18 @@ class _Linear(torch.autograd.Function):
         mask_in_product = y_relu is not None and _o.RELU_IN_WGRAD and not ctx.needs_input_grad[0] and K + 1 <= 64
         if y_relu is not None and not mask_in_product:
             dy = torch.ops.aten.threshold_backward(dy, y_relu, 0.0)
-        lib, dev = _lib.load(), x.device
+        lib, dev = _lib.api(), x.device
         f = dict(dtype=torch.float32, device=dev)
         dx = None
         if ctx.needs_input_grad[0]:
             def build():
                 img = torch.empty(lib.glam_ts_gemm_image_bytes(M, K) // 4, **f)
-                check(lib.glam_ts_gemm_make_image(ptr(w), K, 0, M, K, ptr(img), stream()), "glam_ts_gemm_make_image")
+                lib.glam_ts_gemm_make_image(ptr(w), K, 0, M, K, ptr(img), stream())
                 return img
 
             img = _o._scoped(ctx.scope.bwd if ctx.scope else None, ("lin", id(w)), w, build)
             dx = torch.empty(N, K, **f)
-            check(lib.glam_ts_gemm(ptr(dy), M, M, None, 0, 0, ptr(img), None, ptr(dx), K, K, None, 0, 0, N, stream()), "glam_ts_gemm")
+            lib.glam_ts_gemm(ptr(dy), M, M, None, 0, 0, ptr(img), None, ptr(dx), K, K, None, 0, 0, N, stream())
         ws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
         if K + 1 <= 64:
             # weight and bias gradients as separate contiguous tensors: autograd keeps them as they are (views of one [M, K + 1] buffer
@@ -135,19 +135,15 @@ class _Linear(torch.autograd.Function):
             Kw = w.size(1)
             dw, db = torch.empty(M, Kw, **f), torch.empty(M, **f)
             if mask_in_product:
-                check(lib.glam_wgrad_gemm_split_relu(ptr(dy), ptr(y_relu), M, M, ptr(x), Kw, K, ptr(dw), ptr(db), N, ptr(ws), ws.numel(), stream()),
-                      "glam_wgrad_gemm_split_relu")
+                lib.glam_wgrad_gemm_split_relu(ptr(dy), ptr(y_relu), M, M, ptr(x), Kw, K, ptr(dw), ptr(db), N, ptr(ws), ws.numel(), stream())
             else:
-                check(lib.glam_wgrad_gemm_split(ptr(dy), M, M, ptr(x), Kw, K, ptr(dw), ptr(db), N, ptr(ws), ws.numel(), stream()),
-                      "glam_wgrad_gemm_split")
+                lib.glam_wgrad_gemm_split(ptr(dy), M, M, ptr(x), Kw, K, ptr(dw), ptr(db), N, ptr(ws), ws.numel(), stream())
             return dx, dw, (db if ctx.has_bias else None), None, None, None
         dwb = torch.empty(M + 1, K + 1, **f)          # [d_w | d_b] (+ a spare row / column for the ones trick)
         if M <= 64:   # out[k, m] = sum_n [x|1][n,k] dy[n,m]  ->  written transposed into dwb[m, k]
-            check(lib.glam_wgrad_gemm(ptr(x), K, K, None, 0, 0, 1, ptr(dy), M, M, 0, N, ptr(dwb), 1, K + 1, ptr(ws), ws.numel(),
-                                      stream()), "glam_wgrad_gemm")
+            lib.glam_wgrad_gemm(ptr(x), K, K, None, 0, 0, 1, ptr(dy), M, M, 0, N, ptr(dwb), 1, K + 1, ptr(ws), ws.numel(), stream())
         else:         # out[m, k] = sum_n dy[n,m] [x|1][n,k]
-            check(lib.glam_wgrad_gemm(ptr(dy), M, M, None, 0, 0, 0, ptr(x), K, K, 1, N, ptr(dwb), K + 1, 1, ptr(ws), ws.numel(),
-                                      stream()), "glam_wgrad_gemm")
+            lib.glam_wgrad_gemm(ptr(dy), M, M, None, 0, 0, 0, ptr(x), K, K, 1, N, ptr(dwb), K + 1, 1, ptr(ws), ws.numel(), stream())
         dw = dwb[:M, :w.size(1)]
         db = dwb[:M, K] if ctx.has_bias else None
         return dx, dw, db, None, None, None
@@ -164,10 +160,10 @@ class _RelationMLP(torch.autograd.Function):
         w1, b1, w2, b2 = f32c(w1, "w1"), f32c(b1, "b1"), f32c(w2, "w2"), f32c(b2, "b2")
         Hd, De = w1.shape
         M = w2.size(0)
-        lib = _lib.load()
+        lib = _lib.api()
         h = torch.empty(De, Hd, dtype=torch.float32, device=w1.device)
         out = torch.empty(De, M, dtype=torch.float32, device=w1.device)
-        check(lib.glam_relation_mlp_fwd(ptr(w1), ptr(b1), ptr(w2), ptr(b2), De, Hd, M, ptr(h), ptr(out), stream()), "glam_relation_mlp_fwd")
+        lib.glam_relation_mlp_fwd(ptr(w1), ptr(b1), ptr(w2), ptr(b2), De, Hd, M, ptr(h), ptr(out), stream())
         ctx.save_for_backward(h, w2)
         return out
 
@@ -177,13 +173,12 @@ class _RelationMLP(torch.autograd.Function):
         h, w2 = ctx.saved_tensors
         De, Hd = h.shape
         M = w2.size(0)
-        lib, dev = _lib.load(), h.device
+        lib, dev = _lib.api(), h.device
         d_out = f32c(d_out, "d_out")
         f = dict(dtype=torch.float32, device=dev)
         d_w1, d_b1, d_w2, d_b2 = torch.empty(Hd, De, **f), torch.empty(Hd, **f), torch.empty(M, Hd, **f), torch.empty(M, **f)
         ws = torch.empty(lib.glam_relation_mlp_workspace_bytes(De, Hd, M), dtype=torch.uint8, device=dev)
-        check(lib.glam_relation_mlp_bwd(ptr(d_out), ptr(h), ptr(w2), De, Hd, M, ptr(d_w1), ptr(d_b1), ptr(d_w2), ptr(d_b2), ptr(ws),
-                                        ws.numel(), stream()), "glam_relation_mlp_bwd")
+        lib.glam_relation_mlp_bwd(ptr(d_out), ptr(h), ptr(w2), De, Hd, M, ptr(d_w1), ptr(d_b1), ptr(d_w2), ptr(d_b2), ptr(ws), ws.numel(), stream())
         return d_w1, d_b1, d_w2, d_b2
 
 
@@ -195,7 +190,7 @@ def relation_mlp(nn, De):
     if (len(mods) == 3 and isinstance(mods[0], torch.nn.Linear) and isinstance(mods[1], torch.nn.ReLU) and isinstance(mods[2], torch.nn.Linear)
             and mods[0].bias is not None and mods[2].bias is not None and mods[0].in_features == De
             and mods[0].weight.is_cuda and mods[0].weight.dtype == torch.float32 and mods[2].weight.dtype == torch.float32
-            and _lib.load().glam_relation_mlp_supported(De, mods[0].out_features, mods[2].out_features)):
+            and _lib.api().glam_relation_mlp_supported(De, mods[0].out_features, mods[2].out_features)):
         return _RelationMLP.apply(mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias)
     p = next(nn.parameters())
     return nn(torch.eye(De, dtype=p.dtype, device=p.device))
@@ -229,12 +224,12 @@ class _MatmulTall(torch.autograd.Function):
         if K % 4 == 0 and M % 4 == 0 and K <= 320 and M <= 64 and N > 0 and _lib.route_enabled("x3"):
             # NNConv's [N, 300] x [300, 60] relation product (and any K <= 320 x M <= 64): the long-reduction 3 x bf16 kernel (tall_x3.hip)
             # (an 80 KB-image fp32 k_ts_gemm<4, 20, 4> measured 18.9 us against the library's 15 at N = 20 k and was not kept)
-            lib = _lib.load()
+            lib = _lib.api()
             scope = ctx.scope
             img = _o._scoped(scope.fwd if scope else None, ("tall-fwd", id(w)), w, lambda: _o._ts_image(w, K, M, False))
             out = torch.empty(N, M, dtype=torch.float32, device=a.device)
-            check(lib.glam_ts_gemm(ptr(a), K, K, None, 0, 0, ptr(img), ptr(f32c(bias, "bias")) if bias is not None else None, ptr(out), M, M,
-                                   None, 0, 0, N, stream()), "glam_ts_gemm")
+            lib.glam_ts_gemm(ptr(a), K, K, None, 0, 0, ptr(img), ptr(f32c(bias, "bias")) if bias is not None else None, ptr(out), M, M,
+                             None, 0, 0, N, stream())
         else:
             out = torch.matmul(a, w) if bias is None else torch.addmm(f32c(bias, "bias"), a, w)
         res = (out,) + ((a_in.view_as(a_in),) if ctx.aliased else ()) + ((carry.view(-1),) if ctx.carried else ())
@@ -260,24 +255,24 @@ class _MatmulTall(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             if M <= 64 and K <= 64 and M % 4 == 0 and K % 4 == 0 and linear_supported(M, K) and N > 0:
                 # a layer-sized product (GCNConv 60 -> 60): k_ts_gemm, the skip connection's gradient added in its epilogue
-                lib = _lib.load()
+                lib = _lib.api()
                 scope = ctx.scope
                 img = _o._scoped(scope.bwd if scope else None, ("tall-dx", id(w)), w, lambda: _o._ts_image(w, M, K, True))
                 da = torch.empty(N, K, dtype=torch.float32, device=a.device)
                 if d_alias is not None:
                     d_alias = f32c(d_alias, "d_identity")
-                    check(lib.glam_ts_gemm_add(ptr(dy), M, M, ptr(img), None, ptr(da), K, K, ptr(d_alias), K, N, stream()), "glam_ts_gemm_add")
+                    lib.glam_ts_gemm_add(ptr(dy), M, M, ptr(img), None, ptr(da), K, K, ptr(d_alias), K, N, stream())
                     d_alias = None
                 else:
-                    check(lib.glam_ts_gemm(ptr(dy), M, M, None, 0, 0, ptr(img), None, ptr(da), K, K, None, 0, 0, N, stream()), "glam_ts_gemm")
+                    lib.glam_ts_gemm(ptr(dy), M, M, None, 0, 0, ptr(img), None, ptr(da), K, K, None, 0, 0, N, stream())
             elif M <= 96 and K <= 320 and K > 64:
                 # dy[N, M] @ w^T[M, K] with a wide output: the 120 KB-image k_ts_gemm variant (the library GEMM picks 16x256
                 # tiles for this shape: 44 us for 60 -> 300 at N = 20 k)
-                lib = _lib.load()
+                lib = _lib.api()
                 scope = ctx.scope
                 img = _o._scoped(scope.bwd if scope else None, ("tall-dx", id(w)), w, lambda: _o._ts_image(w, M, K, True))
                 da = torch.empty(N, K, dtype=torch.float32, device=a.device)
-                check(lib.glam_ts_gemm(ptr(dy), M, M, None, 0, 0, ptr(img), None, ptr(da), K, K, None, 0, 0, N, stream()), "glam_ts_gemm")
+                lib.glam_ts_gemm(ptr(dy), M, M, None, 0, 0, ptr(img), None, ptr(da), K, K, None, 0, 0, N, stream())
             else:
                 da = torch.matmul(dy, w.t())
             if d_alias is not None:
@@ -292,30 +287,29 @@ class _MatmulTall(torch.autograd.Function):
             groups = _o._park(scope, "tall", w, ctx.first_app, (a, dy))
             if groups is None:
                 return da, None, None, d_carry, None
-            lib = _lib.load()
+            lib = _lib.api()
             dwb = torch.empty(K + 1, M, dtype=torch.float32, device=a.device)
             add = None if d_carry is None else f32c(d_carry, "d_carry")
             vp = ctypes.c_void_p
             for grp in groups:
                 n = len(grp)
                 ws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=a.device)
-                check(lib.glam_wgrad_gemm_sets(n, (vp * n)(*[t[0].data_ptr() for t in grp]), K, K, 1, (vp * n)(*[t[1].data_ptr() for t in grp]),
-                                               M, M, N, ptr(dwb), M, 1, ptr(add), ptr(ws), ws.numel(), stream()), "glam_wgrad_gemm_sets")
+                lib.glam_wgrad_gemm_sets(n, (vp * n)(*[t[0].data_ptr() for t in grp]), K, K, 1, (vp * n)(*[t[1].data_ptr() for t in grp]),
+                                         M, M, N, ptr(dwb), M, 1, ptr(add), ptr(ws), ws.numel(), stream())
                 add = dwb
             return da, None, None, dwb.view(-1), None
         if ctx.needs_input_grad[1] or ctx.has_bias or ctx.carried:
-            lib = _lib.load()
+            lib = _lib.api()
             ws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=a.device)
             add = f32c(d_carry, "d_carry") if (ctx.carried and d_carry is not None and N > 0) else None
 
             def product(*args):     # (P, I, ldp, ones, Q, J, ldq, out, si, sj): the carry, laid out like `out`, joins in the reduction
                 P, I, ldp, ones, Q, J, ldq, out, si, sj = args
                 if add is None:
-                    check(lib.glam_wgrad_gemm(ptr(P), I, ldp, None, 0, 0, ones, ptr(Q), J, ldq, 0, N, ptr(out), si, sj, ptr(ws), ws.numel(),
-                                              stream()), "glam_wgrad_gemm")
+                    lib.glam_wgrad_gemm(ptr(P), I, ldp, None, 0, 0, ones, ptr(Q), J, ldq, 0, N, ptr(out), si, sj, ptr(ws), ws.numel(), stream())
                 else:
-                    check(lib.glam_wgrad_gemm_add(ptr(P), I, ldp, None, 0, 0, ones, ptr(Q), J, ldq, 0, N, ptr(out), si, sj, ptr(add),
-                                                  ptr(ws), ws.numel(), stream()), "glam_wgrad_gemm_add")
+                    lib.glam_wgrad_gemm_add(ptr(P), I, ldp, None, 0, 0, ones, ptr(Q), J, ldq, 0, N, ptr(out), si, sj, ptr(add),
+                                            ptr(ws), ws.numel(), stream())
 
             if ctx.has_bias:   # [dw ; db] = [a | 1]^T dy   (K + 1 <= 320, M <= 128: matmul_tall's bias condition)
                 dwb = torch.empty(K + 1, M, dtype=torch.float32, device=a.device)
@@ -391,13 +385,13 @@ class _LinearTall(torch.autograd.Function):
             x = torch.celu(x)
         ctx.save_for_backward(x, w)
         if K <= 96 and M <= 320:       # 92 -> 276: k_tall_x3<3, 4, 5> (15 us at N = 20.4 k; the library 29, the fp32 LDS-image kernel 24)
-            lib = _lib.load()
+            lib = _lib.api()
             img = _o._scoped(_o._SCOPE.fwd if _o._SCOPE else None, ("lin", id(w)), w, lambda: _o._ts_image(w, K, M, True))
             y = torch.empty(N, M, dtype=torch.float32, device=x.device)
             if ctx.fold:
-                check(lib.glam_ts_gemm_celu(ptr(x), K, K, 1, ptr(img), ptr(b), ptr(y), M, M, None, 0, N, stream()), "glam_ts_gemm_celu")
+                lib.glam_ts_gemm_celu(ptr(x), K, K, 1, ptr(img), ptr(b), ptr(y), M, M, None, 0, N, stream())
             else:
-                check(lib.glam_ts_gemm(ptr(x), K, K, None, 0, 0, ptr(img), ptr(b), ptr(y), M, M, None, 0, 0, N, stream()), "glam_ts_gemm")
+                lib.glam_ts_gemm(ptr(x), K, K, None, 0, 0, ptr(img), ptr(b), ptr(y), M, M, None, 0, 0, N, stream())
         else:
             y = torch.addmm(b, x, w.t())
         return (y, carry.view(-1)) if ctx.carried else y
@@ -411,7 +405,7 @@ class _LinearTall(torch.autograd.Function):
         dy = f32c(dy, "dy")
         N, K = x.shape
         M = w.size(0)
-        lib = _lib.load()
+        lib = _lib.api()
         f = dict(dtype=torch.float32, device=x.device)
         dx = None
         if ctx.needs_input_grad[0] and M <= 288 and K <= 96 and N > 0:      # dy[N, M] @ w[M, K], long reduction: tall_x3.hip
@@ -419,9 +413,9 @@ class _LinearTall(torch.autograd.Function):
             img = _o._scoped(scope.bwd if scope else None, ("lin-t", id(w)), w, lambda: _o._ts_image(w, M, K, False))
             dx = torch.empty(N, K, **f)
             if ctx.fold:        # ... * celu'(x) in the epilogue
-                check(lib.glam_ts_gemm_celu(ptr(dy), M, M, 0, ptr(img), None, ptr(dx), K, K, ptr(x), K, N, stream()), "glam_ts_gemm_celu")
+                lib.glam_ts_gemm_celu(ptr(dy), M, M, 0, ptr(img), None, ptr(dx), K, K, ptr(x), K, N, stream())
             else:
-                check(lib.glam_ts_gemm(ptr(dy), M, M, None, 0, 0, ptr(img), None, ptr(dx), K, K, None, 0, 0, N, stream()), "glam_ts_gemm")
+                lib.glam_ts_gemm(ptr(dy), M, M, None, 0, 0, ptr(img), None, ptr(dx), K, K, None, 0, 0, N, stream())
         elif ctx.needs_input_grad[0]:
             dx = torch.matmul(dy, w)
         ws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=x.device)
@@ -439,9 +433,9 @@ class _LinearTall(torch.autograd.Function):
                 flat = torch.empty(M * (K + 1), **f)
                 aw, ab = (addf[:M * K], addf[M * K:]) if addf is not None else (None, None)
                 ws2 = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=x.device)
-                check(lib.glam_wgrad_gemm_linear_sets(n, (vp * n)(*[t[0].data_ptr() for t in grp]), M, M, (vp * n)(*[t[1].data_ptr() for t in grp]),
-                                                      K, K, int(grp[0][2]), ptr(flat[:M * K]), ptr(flat[M * K:]), ptr(aw), ptr(ab), N, ptr(ws2),
-                                                      ws2.numel(), stream()), "glam_wgrad_gemm_linear_sets")
+                lib.glam_wgrad_gemm_linear_sets(n, (vp * n)(*[t[0].data_ptr() for t in grp]), M, M, (vp * n)(*[t[1].data_ptr() for t in grp]),
+                                                K, K, int(grp[0][2]), ptr(flat[:M * K]), ptr(flat[M * K:]), ptr(aw), ptr(ab), N, ptr(ws2),
+                                                ws2.numel(), stream())
                 addf = flat
             return dx, None, None, addf, None, None
         add = f32c(d_carry, "d_carry") if (ctx.carried and d_carry is not None and N > 0) else None
@@ -450,14 +444,13 @@ class _LinearTall(torch.autograd.Function):
             flat = torch.empty(M * (K + 1), **f)
             dw, db = flat[:M * K].view(M, K), flat[M * K:]
             aw, ab = (add[:M * K], add[M * K:]) if add is not None else (None, None)
-            check(lib.glam_wgrad_gemm_linear(ptr(dy), M, M, ptr(x), K, K, int(ctx.fold), ptr(dw), ptr(db), ptr(aw), ptr(ab), N, ptr(ws),
-                                             ws.numel(), stream()), "glam_wgrad_gemm_linear")
+            lib.glam_wgrad_gemm_linear(ptr(dy), M, M, ptr(x), K, K, int(ctx.fold), ptr(dw), ptr(db), ptr(aw), ptr(ab), N, ptr(ws),
+                                       ws.numel(), stream())
             if ctx.carried:
                 return dx, None, None, _o._carried(flat, d_carry, add is not None), None, None
             return dx, dw, db, None, None, None
         dwb = torch.empty(M, K + 1, **f)
-        check(lib.glam_wgrad_gemm(ptr(dy), M, M, None, 0, 0, 0, ptr(x), K, K, 1, N, ptr(dwb), K + 1, 1, ptr(ws), ws.numel(), stream()),
-              "glam_wgrad_gemm")
+        lib.glam_wgrad_gemm(ptr(dy), M, M, None, 0, 0, 0, ptr(x), K, K, 1, N, ptr(dwb), K + 1, 1, ptr(ws), ws.numel(), stream())
         if ctx.carried:      # (layout of the carry: [d_w | d_b])
             flat = torch.cat([dwb[:, :K].reshape(-1), dwb[:, K]])
             return dx, None, None, _o._carried(flat, d_carry), None, None
@@ -492,7 +485,7 @@ class _LinearNarrow(torch.autograd.Function):
         N, K = x.shape
         M = w.size(0)
         y = torch.empty(N, M, dtype=torch.float32, device=x.device)
-        check(_lib.load().glam_linear_narrow_fwd(ptr(x), ptr(w), ptr(b), N, K, M, ptr(y), stream()), "glam_linear_narrow_fwd")
+        _lib.api().glam_linear_narrow_fwd(ptr(x), ptr(w), ptr(b), N, K, M, ptr(y), stream())
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
         ctx.set_materialize_grads(False)
@@ -507,14 +500,13 @@ class _LinearNarrow(torch.autograd.Function):
         dy = f32c(dy, "dy")
         N, K = x.shape
         M = w.size(0)
-        lib = _lib.load()
+        lib = _lib.api()
         f = dict(dtype=torch.float32, device=x.device)
         dx = torch.empty(N, K, **f) if ctx.needs_input_grad[0] else None
         dw = torch.empty(M, K, **f)
         db = torch.empty(M, **f) if ctx.has_bias else None
         ws = torch.empty(lib.glam_linear_narrow_bwd_workspace_bytes(K, M), dtype=torch.uint8, device=x.device)
-        check(lib.glam_linear_narrow_bwd(ptr(x), ptr(w), ptr(dy), N, K, M, ptr(dx), ptr(dw), ptr(db), ptr(ws), ws.numel(), stream()),
-              "glam_linear_narrow_bwd")
+        lib.glam_linear_narrow_bwd(ptr(x), ptr(w), ptr(dy), N, K, M, ptr(dx), ptr(dw), ptr(db), ptr(ws), ws.numel(), stream())
         return dx, dw, db
 
 
@@ -532,8 +524,8 @@ class _LinearNarrowAct(torch.autograd.Function):
         M = w.size(0)
         y = torch.empty(N, M, dtype=torch.float32, device=x.device)
         eff = torch.empty(2, dtype=torch.int64, device=x.device)
-        check(_lib.load().glam_linear_narrow_act_fwd(ptr(x), ptr(w), ptr(b), N, K, M, float(lower), float(upper), float(p),
-                                                     ptr(_o.rng_state(x.device)), ptr(eff), ptr(y), stream()), "glam_linear_narrow_act_fwd")
+        _lib.api().glam_linear_narrow_act_fwd(ptr(x), ptr(w), ptr(b), N, K, M, float(lower), float(upper), float(p),
+                                              ptr(_o.rng_state(x.device)), ptr(eff), ptr(y), stream())
         ctx.save_for_backward(x, w)
         ctx.has_bias, ctx.eff, ctx.cfg = b is not None, eff, (float(lower), float(upper), float(p))
         ctx.set_materialize_grads(False)
@@ -548,15 +540,15 @@ class _LinearNarrowAct(torch.autograd.Function):
         dy = f32c(dy, "dy")
         N, K = x.shape
         M = w.size(0)
-        lib = _lib.load()
+        lib = _lib.api()
         f = dict(dtype=torch.float32, device=x.device)
         dx = torch.empty(N, K, **f) if ctx.needs_input_grad[0] else None
         dw = torch.empty(M, K, **f)
         db = torch.empty(M, **f) if ctx.has_bias else None
         ws = torch.empty(lib.glam_linear_narrow_bwd_workspace_bytes(K, M), dtype=torch.uint8, device=x.device)
         lo, hi, p = ctx.cfg
-        check(lib.glam_linear_narrow_act_bwd(ptr(x), ptr(w), ptr(dy), N, K, M, lo, hi, p, ptr(ctx.eff), ptr(dx), ptr(dw), ptr(db), ptr(ws),
-                                             ws.numel(), stream()), "glam_linear_narrow_act_bwd")
+        lib.glam_linear_narrow_act_bwd(ptr(x), ptr(w), ptr(dy), N, K, M, lo, hi, p, ptr(ctx.eff), ptr(dx), ptr(dw), ptr(db), ptr(ws),
+                                       ws.numel(), stream())
         return dx, dw, db, None, None, None
 
 
@@ -594,11 +586,11 @@ class _LinearLib(torch.autograd.Function):
         if ctx.needs_input_grad[2] and dy.data_ptr() % 16:
             db = dy.sum(0)                   # a contiguous view at a storage offset that is not 16-byte aligned: the kernel loads float4
         elif ctx.needs_input_grad[2]:
-            lib = _lib.load()
+            lib = _lib.api()
             N, D = dy.shape
             db = torch.empty(D, dtype=torch.float32, device=dy.device)
             ws = torch.empty(lib.glam_colsum_workspace_bytes(D), dtype=torch.uint8, device=dy.device)   # (touched for N > 2048 only)
-            check(lib.glam_colsum(ptr(dy), N, D, D, ptr(db), ptr(ws), ws.numel(), stream()), "glam_colsum")
+            lib.glam_colsum(ptr(dy), N, D, D, ptr(db), ptr(ws), ws.numel(), stream())
         return dx, dw, db
 
 
@@ -623,7 +615,7 @@ def _dense_ws(dev):
     if ws is None:
         if torch.cuda.is_current_stream_capturing():
             return None      # (born inside a capture it would live in that graph's private pool and outlive it here: this launch goes unsplit)
-        ws = _DENSE_WS[key] = torch.empty(_lib.load().glam_dense_ws_bytes(), dtype=torch.uint8, device=dev)
+        ws = _DENSE_WS[key] = torch.empty(_lib.api().glam_dense_ws_bytes(), dtype=torch.uint8, device=dev)
     return ws
 
 
@@ -642,8 +634,7 @@ class _LinearDense(torch.autograd.Function):
         M = w.size(0)
         y = torch.empty(N, M, dtype=torch.float32, device=x.device)
         ws = _dense_ws(x.device)
-        check(_lib.load().glam_linear_dense_fwd_ws(ptr(x), ptr(w), ptr(b), N, K, M, act, slope, ptr(y), ptr(ws), 0 if ws is None else ws.numel(),
-                                                   stream()), "glam_linear_dense_fwd_ws")
+        _lib.api().glam_linear_dense_fwd_ws(ptr(x), ptr(w), ptr(b), N, K, M, act, slope, ptr(y), ptr(ws), 0 if ws is None else ws.numel(), stream())
         ctx.save_for_backward(x, w, y if act else None)
         ctx.has_bias, ctx.slope = b is not None, (0.0 if act == 1 else slope)
         ctx.set_materialize_grads(False)
@@ -669,8 +660,8 @@ class _LinearDense(torch.autograd.Function):
         if db is not None and dw is None:
             dw = torch.empty(M, K, **f)      # (the bias gradient is the all-ones column of the dy^T [x | 1] product: it comes with dw)
         ws = _dense_ws(x.device)
-        check(_lib.load().glam_linear_dense_bwd_ws(ptr(x), ptr(w), ptr(dy), ptr(y), ctx.slope, N, K, M, ptr(dx), ptr(dw), ptr(db), ptr(ws),
-                                                   0 if ws is None else ws.numel(), stream()), "glam_linear_dense_bwd_ws")
+        _lib.api().glam_linear_dense_bwd_ws(ptr(x), ptr(w), ptr(dy), ptr(y), ctx.slope, N, K, M, ptr(dx), ptr(dw), ptr(db), ptr(ws),
+                                            0 if ws is None else ws.numel(), stream())
         return dx, (dw if need_dw else None), db, None, None
 
 
@@ -730,13 +721,13 @@ def linear_relu(x, weight, bias=None, node=None):
     Kp = (K + 3) // 4 * 4
     f32 = x.dtype == torch.float32 and weight.dtype == torch.float32 and (bias is None or bias.dtype == torch.float32)
     if not (x.dim() == 2 and x.is_cuda and f32 and M % 4 == 0 and linear_supported(K, M) and not _dense_route(x, weight, bias)
-            and _lib.load().glam_ts_gemm_relu_supported(Kp, M) == 1):
+            and _lib.api().glam_ts_gemm_relu_supported(Kp, M) == 1):
         return None
     if Kp != K:
         if x.requires_grad and torch.is_grad_enabled():
             return None                      # (a padded differentiable input takes the padded-weight route of ``linear``)
         x = _o.pad_cols(x, Kp)
-    nd, took = _node_arg(node, M) if _lib.load().glam_ts_gemm_rrelu_supported(Kp, M) == 1 else (None, None)
+    nd, took = _node_arg(node, M) if _lib.api().glam_ts_gemm_rrelu_supported(Kp, M) == 1 else (None, None)
     y = _Linear.apply(x, weight, bias, True, None, nd)
     if took:
         _o.register_node_product(y, node[0], took["xw"], took["a_ij"])
@@ -760,7 +751,7 @@ def linear_rrelu(x, weight, bias, lower, upper, drop_p=0.0, node=None):
     Kp = (K + 3) // 4 * 4
     f32 = x.dtype == torch.float32 and weight.dtype == torch.float32 and (bias is None or bias.dtype == torch.float32)
     if not (_o.RRELU_IN_GEMM and x.dim() == 2 and x.is_cuda and f32 and M % 4 == 0 and linear_supported(K, M) and not _dense_route(x, weight, bias)
-            and 0 < lower <= upper and 0 <= drop_p < 1 and _lib.load().glam_ts_gemm_rrelu_supported(Kp, M) == 1):
+            and 0 < lower <= upper and 0 <= drop_p < 1 and _lib.api().glam_ts_gemm_rrelu_supported(Kp, M) == 1):
         return None
     if Kp != K:
         if x.requires_grad and torch.is_grad_enabled():
@@ -786,12 +777,12 @@ class _LinearSplit(torch.autograd.Function):
         N, K = x.shape
         M = wt.size(1)
         M2 = M - M1
-        lib, dev = _lib.load(), x.device
+        lib, dev = _lib.api(), x.device
         f = dict(dtype=torch.float32, device=dev)
         img = torch.empty(lib.glam_ts_gemm_image_bytes(K, M) // 4, **f)
-        check(lib.glam_ts_gemm_make_image(ptr(wt), M, 0, K, M, ptr(img), stream()), "glam_ts_gemm_make_image")
+        lib.glam_ts_gemm_make_image(ptr(wt), M, 0, K, M, ptr(img), stream())
         y1, y2 = torch.empty(N, M1, **f), torch.empty(N, M2, **f)
-        check(lib.glam_ts_gemm(ptr(x), K, K, None, 0, 0, ptr(img), None, ptr(y1), M1, M1, ptr(y2), M2, M2, N, stream()), "glam_ts_gemm")
+        lib.glam_ts_gemm(ptr(x), K, K, None, 0, 0, ptr(img), None, ptr(y1), M1, M1, ptr(y2), M2, M2, N, stream())
         ctx.save_for_backward(x, wt)
         ctx.M1 = M1
         return y1, y2
@@ -804,20 +795,18 @@ class _LinearSplit(torch.autograd.Function):
         M = wt.size(1)
         M1 = ctx.M1
         M2 = M - M1
-        lib, dev = _lib.load(), x.device
+        lib, dev = _lib.api(), x.device
         f = dict(dtype=torch.float32, device=dev)
         dy1, dy2 = f32c(dy1, "dy1"), f32c(dy2, "dy2")
         dx = None
         if ctx.needs_input_grad[0]:
             img = torch.empty(lib.glam_ts_gemm_image_bytes(M, K) // 4, **f)
-            check(lib.glam_ts_gemm_make_image(ptr(wt), M, 1, M, K, ptr(img), stream()), "glam_ts_gemm_make_image")
+            lib.glam_ts_gemm_make_image(ptr(wt), M, 1, M, K, ptr(img), stream())
             dx = torch.empty(N, K, **f)
-            check(lib.glam_ts_gemm(ptr(dy1), M1, M1, ptr(dy2), M2, M2, ptr(img), None, ptr(dx), K, K, None, 0, 0, N, stream()),
-                  "glam_ts_gemm")
+            lib.glam_ts_gemm(ptr(dy1), M1, M1, ptr(dy2), M2, M2, ptr(img), None, ptr(dx), K, K, None, 0, 0, N, stream())
         ws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
         dwt = torch.empty(K, M, **f)     # out[i = m, j = k] written at dwt[k, m]
-        check(lib.glam_wgrad_gemm(ptr(dy1), M1, M1, ptr(dy2), M2, M2, 0, ptr(x), K, K, 0, N, ptr(dwt), 1, M, ptr(ws), ws.numel(),
-                                  stream()), "glam_wgrad_gemm")
+        lib.glam_wgrad_gemm(ptr(dy1), M1, M1, ptr(dy2), M2, M2, 0, ptr(x), K, K, 0, N, ptr(dwt), 1, M, ptr(ws), ws.numel(), stream())
         return dx, dwt, None
 
 
@@ -837,7 +826,7 @@ class _GruGates(torch.autograd.Function):
         gi, gh, h = f32c(gi, "gi"), f32c(gh, "gh"), f32c(h, "h")
         N, C = h.shape
         h_new = torch.empty_like(h)
-        check(_lib.load().glam_gru_gates_fwd(ptr(gi), ptr(gh), ptr(h), N, C, ptr(h_new), stream()), "glam_gru_gates_fwd")
+        _lib.api().glam_gru_gates_fwd(ptr(gi), ptr(gh), ptr(h), N, C, ptr(h_new), stream())
         ctx.save_for_backward(gi, gh, h)
         return h_new
 
@@ -848,8 +837,7 @@ class _GruGates(torch.autograd.Function):
         N, C = h.shape
         d_hnew = f32c(d_hnew, "d_hnew")
         d_gi, d_gh, d_h = torch.empty_like(gi), torch.empty_like(gh), torch.empty_like(h)
-        check(_lib.load().glam_gru_gates_bwd(ptr(gi), ptr(gh), ptr(h), ptr(d_hnew), N, C, ptr(d_gi), ptr(d_gh), ptr(d_h),
-                                             stream()), "glam_gru_gates_bwd")
+        _lib.api().glam_gru_gates_bwd(ptr(gi), ptr(gh), ptr(h), ptr(d_hnew), N, C, ptr(d_gi), ptr(d_gh), ptr(d_h), stream())
         return d_gi, d_gh, d_h
 
 
@@ -863,8 +851,7 @@ class _GruTail(torch.autograd.Function):
         identity = None if identity is None else f32c(identity, "identity")
         N, C = h.shape
         h_new, out = torch.empty_like(h), torch.empty_like(h)
-        check(_lib.load().glam_gru_tail_fwd(ptr(gi), ptr(gh), ptr(h), ptr(identity), N, C, act, float(slope), ptr(h_new), ptr(out),
-                                            stream()), "glam_gru_tail_fwd")
+        _lib.api().glam_gru_tail_fwd(ptr(gi), ptr(gh), ptr(h), ptr(identity), N, C, act, float(slope), ptr(h_new), ptr(out), stream())
         ctx.save_for_backward(gi, gh, h, out)
         ctx.cfg = (act, float(slope), identity is not None)
         return out, h_new
@@ -879,8 +866,8 @@ class _GruTail(torch.autograd.Function):
         d_hstate = None if d_hstate is None else f32c(d_hstate, "d_hstate")
         d_gi, d_gh, d_h = torch.empty_like(gi), torch.empty_like(gh), torch.empty_like(h)
         d_id = torch.empty_like(h) if has_res else None
-        check(_lib.load().glam_gru_tail_bwd(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_hstate), N, C, act, slope,
-                                            ptr(d_gi), ptr(d_gh), ptr(d_h), ptr(d_id), stream()), "glam_gru_tail_bwd")
+        _lib.api().glam_gru_tail_bwd(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_hstate), N, C, act, slope,
+                                     ptr(d_gi), ptr(d_gh), ptr(d_h), ptr(d_id), stream())
         return d_gi, d_gh, d_h, d_id, None, None
 
 
@@ -949,7 +936,7 @@ def _gru_pre(lib, scope, w_ih, w_hh, C, dev, st):
     weight scope (a training step), shared by every application of the block and by its backward."""
     def build():
         buf = torch.empty(2, lib.glam_gru_ws_pre_bytes(), dtype=torch.uint8, device=dev)
-        check(lib.glam_gru_ws_make_pre(ptr(w_ih), ptr(w_hh), C, ptr(buf[0]), ptr(buf[1]), st), "glam_gru_ws_make_pre")
+        lib.glam_gru_ws_make_pre(ptr(w_ih), ptr(w_hh), C, ptr(buf[0]), ptr(buf[1]), st)
         return buf
     return _o._scoped(scope.fwd if scope else None, ("gru-pre", id(w_ih), id(w_hh)), w_ih, build)
 
@@ -957,7 +944,7 @@ def _gru_pre(lib, scope, w_ih, w_hh, C, dev, st):
 def gru_images_plain(N, C):
     """True when the GRU step of this size runs on the four plain ``k_ts_gemm`` images of its gate matrices (the warp-specialised step,
     or the unfused gate linears) — the set ``ops.prestage`` can build ahead; the fp32 fused step needs its gate-padded images too."""
-    lib = _lib.load()
+    lib = _lib.api()
     if N <= 0 or not linear_supported(C, 3 * C) or lib.glam_ts_gemm_image_bytes(3 * C, C) <= 0:
         return False
     if _want_gru_ws(lib, N, C):
@@ -967,7 +954,7 @@ def gru_images_plain(N, C):
 
 def gru_images_pre(N, C):
     """True when the GRU step of this size reads the pre-split images of ``glam_gru_ws_make_pre`` (the warp-specialised step, default)."""
-    return bool(_o.GRU_PRE) and _want_gru_ws(_lib.load(), N, C)
+    return bool(_o.GRU_PRE) and _want_gru_ws(_lib.api(), N, C)
 
 
 def _want_gru_fused(N):
@@ -1004,14 +991,14 @@ class _GruBlock(torch.autograd.Function):
         identity = None if identity is None else f32c(identity, "identity")
         N, C = h.shape
         M = 3 * C
-        lib, dev = _lib.load(), x.device
+        lib, dev = _lib.api(), x.device
         f = dict(dtype=torch.float32, device=dev)
         scope = _o._SCOPE
 
         def image(w):
             def build():
                 img = torch.empty(lib.glam_ts_gemm_image_bytes(C, M) // 4, **f)
-                check(lib.glam_ts_gemm_make_image(ptr(w), C, 1, C, M, ptr(img), stream()), "glam_ts_gemm_make_image")
+                lib.glam_ts_gemm_make_image(ptr(w), C, 1, C, M, ptr(img), stream())
                 return img
             return _o._scoped(scope.fwd if scope else None, ("lin", id(w)), w, build)
 
@@ -1032,12 +1019,10 @@ class _GruBlock(torch.autograd.Function):
                 if N > 0 and _want_gru_fused(N) and lib.glam_gru_fused_supported(C) and not _want_gru_ws(lib, N, C):
                     # ... and the two gate-padded images of the fused step: six re-layouts of the same two matrices, one launch
                     fused = torch.empty(2, lib.glam_gru_fused_image_bytes() // 4, **f)
-                    check(lib.glam_gru_make_images(ptr(w_ih), ptr(w_hh), C, ptr(ia), ptr(ib), ptr(ta), ptr(tb), ptr(fused[0]), ptr(fused[1]),
-                                                   st), "glam_gru_make_images")
+                    lib.glam_gru_make_images(ptr(w_ih), ptr(w_hh), C, ptr(ia), ptr(ib), ptr(ta), ptr(tb), ptr(fused[0]), ptr(fused[1]), st)
                     scope.fwd[("gru-fused", id(w_ih), id(w_hh))] = (w_ih, fused)
                 else:
-                    check(lib.glam_ts_gemm_make_image_quad(ptr(w_ih), ptr(w_hh), C, M, ptr(ia), ptr(ib), ptr(ta), ptr(tb), st),
-                          "glam_ts_gemm_make_image_quad")
+                    lib.glam_ts_gemm_make_image_quad(ptr(w_ih), ptr(w_hh), C, M, ptr(ia), ptr(ib), ptr(ta), ptr(tb), st)
                 scope.fwd[ka], scope.fwd[kb] = (w_ih, ia), (w_hh, ib)
                 scope.bwd[ka], scope.bwd[kb] = (w_ih, ta), (w_hh, tb)
         h_new, out = torch.empty_like(h), torch.empty_like(h)
@@ -1061,34 +1046,32 @@ class _GruBlock(torch.autograd.Function):
                 nimg = staged[lib.glam_triplet_staged_node_fragments(cols // C, C, 4):]      # ([W_node | Wa] as the producers' operand fragments)
                 xw, a_ij = torch.empty(N, cols, **f), torch.empty(N, 8, **f)
                 if rng is None:
-                    check(lib.glam_gru_ws_fwd_pre_node(ptr(x), ptr(h), ptr(identity), ptr(pre[0]), ptr(b_ih), ptr(b_hh), N, C, int(celu_in), act,
-                                                       float(slope), ptr(gi), ptr(gh), ptr(h_new), ptr(out), ptr(xc), ptr(nimg), cols, ptr(xw),
-                                                       ptr(a_ij), st), "glam_gru_ws_fwd_pre_node")
+                    lib.glam_gru_ws_fwd_pre_node(ptr(x), ptr(h), ptr(identity), ptr(pre[0]), ptr(b_ih), ptr(b_hh), N, C, int(celu_in), act,
+                                                 float(slope), ptr(gi), ptr(gh), ptr(h_new), ptr(out), ptr(xc), ptr(nimg), cols, ptr(xw),
+                                                 ptr(a_ij), st)
                 else:
-                    check(lib.glam_gru_ws_rng_fwd_pre_node(ptr(x), ptr(h), ptr(identity), ptr(pre[0]), ptr(b_ih), ptr(b_hh), N, C, int(celu_in),
-                                                           act, float(slope), lo, hi, p, ptr(_o.rng_state(dev)), ptr(eff), ptr(gi), ptr(gh),
-                                                           ptr(h_new), ptr(out), ptr(out_drop), ptr(xc), ptr(nimg), cols, ptr(xw), ptr(a_ij), st),
-                          "glam_gru_ws_rng_fwd_pre_node")
+                    lib.glam_gru_ws_rng_fwd_pre_node(ptr(x), ptr(h), ptr(identity), ptr(pre[0]), ptr(b_ih), ptr(b_hh), N, C, int(celu_in),
+                                                     act, float(slope), lo, hi, p, ptr(_o.rng_state(dev)), ptr(eff), ptr(gi), ptr(gh),
+                                                     ptr(h_new), ptr(out), ptr(out_drop), ptr(xc), ptr(nimg), cols, ptr(xw), ptr(a_ij), st)
                 took["xw"], took["a_ij"] = xw, a_ij
             elif pre is not None:
                 # ... on the gate matrices as pre-split operand fragments (glam_gru_ws_make_pre: once per weight update, not per block)
                 if rng is None:
-                    check(lib.glam_gru_ws_fwd_pre(ptr(x), ptr(h), ptr(identity), ptr(pre[0]), ptr(b_ih), ptr(b_hh), N, C, int(celu_in), act,
-                                                  float(slope), ptr(gi), ptr(gh), ptr(h_new), ptr(out), ptr(xc), st), "glam_gru_ws_fwd_pre")
+                    lib.glam_gru_ws_fwd_pre(ptr(x), ptr(h), ptr(identity), ptr(pre[0]), ptr(b_ih), ptr(b_hh), N, C, int(celu_in), act,
+                                            float(slope), ptr(gi), ptr(gh), ptr(h_new), ptr(out), ptr(xc), st)
                 else:
-                    check(lib.glam_gru_ws_rng_fwd_pre(ptr(x), ptr(h), ptr(identity), ptr(pre[0]), ptr(b_ih), ptr(b_hh), N, C, int(celu_in), act,
-                                                      float(slope), lo, hi, p, ptr(_o.rng_state(dev)), ptr(eff), ptr(gi), ptr(gh), ptr(h_new),
-                                                      ptr(out), ptr(out_drop), ptr(xc), st), "glam_gru_ws_rng_fwd_pre")
+                    lib.glam_gru_ws_rng_fwd_pre(ptr(x), ptr(h), ptr(identity), ptr(pre[0]), ptr(b_ih), ptr(b_hh), N, C, int(celu_in), act,
+                                                float(slope), lo, hi, p, ptr(_o.rng_state(dev)), ptr(eff), ptr(gi), ptr(gh), ptr(h_new),
+                                                ptr(out), ptr(out_drop), ptr(xc), st)
             elif rng is None:
                 img_a, img_b = image(w_ih), image(w_hh)       # (the plain k_ts_gemm images: GLAM_GRU_PRE=0)
-                check(lib.glam_gru_ws_fwd_xc(ptr(x), ptr(h), ptr(identity), ptr(img_a), ptr(img_b), ptr(b_ih), ptr(b_hh), N, C,
-                                             int(celu_in), act, float(slope), ptr(gi), ptr(gh), ptr(h_new), ptr(out), ptr(xc), st),
-                      "glam_gru_ws_fwd_xc")
+                lib.glam_gru_ws_fwd_xc(ptr(x), ptr(h), ptr(identity), ptr(img_a), ptr(img_b), ptr(b_ih), ptr(b_hh), N, C,
+                                       int(celu_in), act, float(slope), ptr(gi), ptr(gh), ptr(h_new), ptr(out), ptr(xc), st)
             else:
                 img_a, img_b = image(w_ih), image(w_hh)
-                check(lib.glam_gru_ws_rng_fwd_xc(ptr(x), ptr(h), ptr(identity), ptr(img_a), ptr(img_b), ptr(b_ih), ptr(b_hh), N, C,
-                                                 int(celu_in), act, float(slope), lo, hi, p, ptr(_o.rng_state(dev)), ptr(eff), ptr(gi), ptr(gh),
-                                                 ptr(h_new), ptr(out), ptr(out_drop), ptr(xc), st), "glam_gru_ws_rng_fwd_xc")
+                lib.glam_gru_ws_rng_fwd_xc(ptr(x), ptr(h), ptr(identity), ptr(img_a), ptr(img_b), ptr(b_ih), ptr(b_hh), N, C,
+                                           int(celu_in), act, float(slope), lo, hi, p, ptr(_o.rng_state(dev)), ptr(eff), ptr(gi), ptr(gh),
+                                           ptr(h_new), ptr(out), ptr(out_drop), ptr(xc), st)
             if xc is not None:
                 x_keep, x_is_celu = xc, True
         elif N > 0 and _want_gru_fused(N) and lib.glam_gru_fused_supported(C):
@@ -1096,33 +1079,30 @@ class _GruBlock(torch.autograd.Function):
             def build_fused():
                 nb = lib.glam_gru_fused_image_bytes() // 4
                 buf = torch.empty(2, nb, **f)
-                check(lib.glam_gru_fused_make_images(ptr(w_ih), ptr(w_hh), C, ptr(buf[0]), ptr(buf[1]), st), "glam_gru_fused_make_images")
+                lib.glam_gru_fused_make_images(ptr(w_ih), ptr(w_hh), C, ptr(buf[0]), ptr(buf[1]), st)
                 return buf
             imgs = _o._scoped(scope.fwd if scope else None, ("gru-fused", id(w_ih), id(w_hh)), w_ih, build_fused)
             if rng is None:
-                check(lib.glam_gru_fused_fwd(ptr(x), ptr(h), ptr(identity), ptr(imgs[0]), ptr(imgs[1]), ptr(b_ih), ptr(b_hh), N, C,
-                                             int(celu_in), act, float(slope), ptr(gi), ptr(gh), ptr(h_new), ptr(out), st), "glam_gru_fused_fwd")
+                lib.glam_gru_fused_fwd(ptr(x), ptr(h), ptr(identity), ptr(imgs[0]), ptr(imgs[1]), ptr(b_ih), ptr(b_hh), N, C,
+                                       int(celu_in), act, float(slope), ptr(gi), ptr(gh), ptr(h_new), ptr(out), st)
             else:
-                check(lib.glam_gru_fused_rng_fwd(ptr(x), ptr(h), ptr(identity), ptr(imgs[0]), ptr(imgs[1]), ptr(b_ih), ptr(b_hh), N, C,
-                                                 int(celu_in), act, float(slope), lo, hi, p, ptr(_o.rng_state(dev)), ptr(eff), ptr(gi), ptr(gh),
-                                                 ptr(h_new), ptr(out), ptr(out_drop), st), "glam_gru_fused_rng_fwd")
+                lib.glam_gru_fused_rng_fwd(ptr(x), ptr(h), ptr(identity), ptr(imgs[0]), ptr(imgs[1]), ptr(b_ih), ptr(b_hh), N, C,
+                                           int(celu_in), act, float(slope), lo, hi, p, ptr(_o.rng_state(dev)), ptr(eff), ptr(gi), ptr(gh),
+                                           ptr(h_new), ptr(out), ptr(out_drop), st)
         else:
             if _o.GEMM_PAIR:     # both gate linears in ONE launch (two products of the same kernel variant share the CUs)
                 img_a, img_b = image(w_ih), image(w_hh)     # both alive until the launch is enqueued (outside a scope they are temporaries:
                 #                                             the allocator would hand the first one's memory to the second)
-                check(lib.glam_ts_gemm_pair(ptr(x), C, C, int(celu_in), ptr(img_a), ptr(b_ih), ptr(gi), M, M, None, 0, None, 0,
-                                            ptr(h), C, C, 0, ptr(img_b), ptr(b_hh), ptr(gh), M, M, None, 0, None, 0, N, st),
-                      "glam_ts_gemm_pair")
+                lib.glam_ts_gemm_pair(ptr(x), C, C, int(celu_in), ptr(img_a), ptr(b_ih), ptr(gi), M, M, None, 0, None, 0,
+                                      ptr(h), C, C, 0, ptr(img_b), ptr(b_hh), ptr(gh), M, M, None, 0, None, 0, N, st)
             else:
-                check(lib.glam_ts_gemm_celu(ptr(x), C, C, int(celu_in), ptr(image(w_ih)), ptr(b_ih), ptr(gi), M, M, None, 0, N, st),
-                      "glam_ts_gemm_celu")
-                check(lib.glam_ts_gemm(ptr(h), C, C, None, 0, 0, ptr(image(w_hh)), ptr(b_hh), ptr(gh), M, M, None, 0, 0, N, st), "glam_ts_gemm")
+                lib.glam_ts_gemm_celu(ptr(x), C, C, int(celu_in), ptr(image(w_ih)), ptr(b_ih), ptr(gi), M, M, None, 0, N, st)
+                lib.glam_ts_gemm(ptr(h), C, C, None, 0, 0, ptr(image(w_hh)), ptr(b_hh), ptr(gh), M, M, None, 0, 0, N, st)
             if rng is None:
-                check(lib.glam_gru_tail_fwd(ptr(gi), ptr(gh), ptr(h), ptr(identity), N, C, act, float(slope), ptr(h_new), ptr(out), st),
-                      "glam_gru_tail_fwd")
+                lib.glam_gru_tail_fwd(ptr(gi), ptr(gh), ptr(h), ptr(identity), N, C, act, float(slope), ptr(h_new), ptr(out), st)
             else:     # training mode: RReLU slopes / the next conv's Dropout mask drawn inside the launch
-                check(lib.glam_gru_tail_rng_fwd(ptr(gi), ptr(gh), ptr(h), ptr(identity), N, C, act, float(slope), lo, hi, p,
-                                                ptr(_o.rng_state(dev)), ptr(eff), ptr(h_new), ptr(out), ptr(out_drop), st), "glam_gru_tail_rng_fwd")
+                lib.glam_gru_tail_rng_fwd(ptr(gi), ptr(gh), ptr(h), ptr(identity), N, C, act, float(slope), lo, hi, p,
+                                          ptr(_o.rng_state(dev)), ptr(eff), ptr(h_new), ptr(out), ptr(out_drop), st)
         ctx.save_for_backward(x_keep, h, gi, gh, out, w_ih, w_hh)
         ctx.x_is_celu = x_is_celu
         ctx.gates = gates
@@ -1148,7 +1128,7 @@ class _GruBlock(torch.autograd.Function):
         celu_q = celu_in and not ctx.x_is_celu
         N, C = h.shape
         M = 3 * C
-        lib, dev = _lib.load(), x.device
+        lib, dev = _lib.api(), x.device
         f = dict(dtype=torch.float32, device=dev)
         st = stream()
         d_out = None if d_out is None else f32c(d_out, "d_out")
@@ -1162,7 +1142,7 @@ class _GruBlock(torch.autograd.Function):
         def image_t(w):
             def build():
                 img = torch.empty(lib.glam_ts_gemm_image_bytes(M, C) // 4, **f)
-                check(lib.glam_ts_gemm_make_image(ptr(w), C, 0, M, C, ptr(img), stream()), "glam_ts_gemm_make_image")
+                lib.glam_ts_gemm_make_image(ptr(w), C, 0, M, C, ptr(img), stream())
                 return img
             return _o._scoped(scope.bwd if scope else None, ("lin", id(w)), w, build)
 
@@ -1179,36 +1159,33 @@ class _GruBlock(torch.autograd.Function):
                 if d_out is None:
                     d_out = torch.zeros_like(h)
                 if pre is not None:
-                    check(lib.glam_gru_bwd_ws_pre(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_hstate), ptr(x), ptr(pre[1]), N, C,
-                                                  celu_bwd, act, slope, merge, ptr(d_gi), ptr(d_gh), ptr(d_id), ptr(dx), ptr(d_h), st),
-                          "glam_gru_bwd_ws_pre")
+                    lib.glam_gru_bwd_ws_pre(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_hstate), ptr(x), ptr(pre[1]), N, C,
+                                            celu_bwd, act, slope, merge, ptr(d_gi), ptr(d_gh), ptr(d_id), ptr(dx), ptr(d_h), st)
                 else:
-                    check(lib.glam_gru_bwd_ws(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_hstate), ptr(x), ptr(img_a), ptr(img_b), N,
-                                              C, celu_bwd, act, slope, merge, ptr(d_gi), ptr(d_gh), ptr(d_id), ptr(dx), ptr(d_h), st),
-                          "glam_gru_bwd_ws")
+                    lib.glam_gru_bwd_ws(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_hstate), ptr(x), ptr(img_a), ptr(img_b), N,
+                                        C, celu_bwd, act, slope, merge, ptr(d_gi), ptr(d_gh), ptr(d_id), ptr(dx), ptr(d_h), st)
             else:
                 if d_out is None and d_out_drop is None:
                     d_out = torch.zeros_like(h)
                 if pre is not None:
-                    check(lib.glam_gru_bwd_ws_rng_pre(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_out_drop), ptr(d_hstate), ptr(x),
-                                                      ptr(pre[1]), N, C, celu_bwd, act, slope, rng[0], rng[1], rng[2], ptr(ctx.eff), merge,
-                                                      ptr(d_gi), ptr(d_gh), ptr(d_id), ptr(dx), ptr(d_h), st), "glam_gru_bwd_ws_rng_pre")
+                    lib.glam_gru_bwd_ws_rng_pre(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_out_drop), ptr(d_hstate), ptr(x),
+                                                ptr(pre[1]), N, C, celu_bwd, act, slope, rng[0], rng[1], rng[2], ptr(ctx.eff), merge,
+                                                ptr(d_gi), ptr(d_gh), ptr(d_id), ptr(dx), ptr(d_h), st)
                 else:
-                    check(lib.glam_gru_bwd_ws_rng(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_out_drop), ptr(d_hstate), ptr(x),
-                                                  ptr(img_a), ptr(img_b), N, C, celu_bwd, act, slope, rng[0], rng[1], rng[2], ptr(ctx.eff), merge,
-                                                  ptr(d_gi), ptr(d_gh), ptr(d_id), ptr(dx), ptr(d_h), st), "glam_gru_bwd_ws_rng")
+                    lib.glam_gru_bwd_ws_rng(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_out_drop), ptr(d_hstate), ptr(x),
+                                            ptr(img_a), ptr(img_b), N, C, celu_bwd, act, slope, rng[0], rng[1], rng[2], ptr(ctx.eff), merge,
+                                            ptr(d_gi), ptr(d_gh), ptr(d_id), ptr(dx), ptr(d_h), st)
             dh = d_h
         elif rng is None:
             if d_out is None:
                 d_out = torch.zeros_like(h)
-            check(lib.glam_gru_tail_bwd(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_hstate), N, C, act, slope, ptr(d_gi),
-                                        ptr(d_gh), ptr(d_h), ptr(d_id), st), "glam_gru_tail_bwd")
+            lib.glam_gru_tail_bwd(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_hstate), N, C, act, slope, ptr(d_gi),
+                                  ptr(d_gh), ptr(d_h), ptr(d_id), st)
         else:
             if d_out is None and d_out_drop is None:
                 d_out = torch.zeros_like(h)
-            check(lib.glam_gru_tail_rng_bwd(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_out_drop), ptr(d_hstate), N, C, act, slope,
-                                            rng[0], rng[1], rng[2], ptr(ctx.eff), ptr(d_gi), ptr(d_gh), ptr(d_h), ptr(d_id), st),
-                  "glam_gru_tail_rng_bwd")
+            lib.glam_gru_tail_rng_bwd(ptr(gi), ptr(gh), ptr(h), ptr(out), ptr(d_out), ptr(d_out_drop), ptr(d_hstate), N, C, act, slope,
+                                      rng[0], rng[1], rng[2], ptr(ctx.eff), ptr(d_gi), ptr(d_gh), ptr(d_h), ptr(d_id), st)
         if ws:
             pass
         elif _o.GEMM_PAIR:
@@ -1216,14 +1193,12 @@ class _GruBlock(torch.autograd.Function):
             # with the folded CELU the epilogue multiplies by celu'(x): dx is the gradient of the RAW input
             # d_h = d_gh @ W_hh^T + the direct z * g path of the gate equations (the addend of the GEMM's epilogue); both products in one launch
             img_a, img_b = image_t(w_ih), image_t(w_hh)
-            check(lib.glam_ts_gemm_pair(ptr(d_gi), M, M, 0, ptr(img_a), None, ptr(dx), C, C, ptr(x) if celu_in else None, C, None, 0,
-                                        ptr(d_gh), M, M, 0, ptr(img_b), None, ptr(dh), C, C, None, 0, ptr(d_h), C, N, st),
-                  "glam_ts_gemm_pair")
+            lib.glam_ts_gemm_pair(ptr(d_gi), M, M, 0, ptr(img_a), None, ptr(dx), C, C, ptr(x) if celu_in else None, C, None, 0,
+                                  ptr(d_gh), M, M, 0, ptr(img_b), None, ptr(dh), C, C, None, 0, ptr(d_h), C, N, st)
         else:
             dx, dh = torch.empty(N, C, **f), torch.empty(N, C, **f)
-            check(lib.glam_ts_gemm_celu(ptr(d_gi), M, M, 0, ptr(image_t(w_ih)), None, ptr(dx), C, C, ptr(x) if celu_in else None, C, N, st),
-                  "glam_ts_gemm_celu")
-            check(lib.glam_ts_gemm_add(ptr(d_gh), M, M, ptr(image_t(w_hh)), None, ptr(dh), C, C, ptr(d_h), C, N, st), "glam_ts_gemm_add")
+            lib.glam_ts_gemm_celu(ptr(d_gi), M, M, 0, ptr(image_t(w_ih)), None, ptr(dx), C, C, ptr(x) if celu_in else None, C, N, st)
+            lib.glam_ts_gemm_add(ptr(d_gh), M, M, ptr(image_t(w_hh)), None, ptr(dh), C, C, ptr(d_h), C, N, st)
         if ctx.carried and _o._parks(scope, N):
             # The weight gradients of ALL applications of the block in one launch pair (see ops._park): the first application multiplies
             # the parked sets together — [d_gi_1; d_gi_2; d_gi_3]^T [x_1; x_2; x_3] —, one CELU fold and gate layout per launch
@@ -1239,13 +1214,12 @@ class _GruBlock(torch.autograd.Function):
                 ws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
                 arr = lambda i: (vp * n)(*[t[i].data_ptr() for t in grp])
                 if grp[0][5]:
-                    check(lib.glam_wgrad_gemm_gru_gates_seg(n, arr(0), C, arr(1), C, int(grp[0][4]), arr(3), C, ptr(dw_ih), ptr(db_ih),
-                                                            ptr(dw_hh), ptr(db_hh), N, ptr(ws), ws.numel(), ptr(add[0]), ptr(add[1]),
-                                                            ptr(add[2]), ptr(add[3]), st), "glam_wgrad_gemm_gru_gates_seg")
+                    lib.glam_wgrad_gemm_gru_gates_seg(n, arr(0), C, arr(1), C, int(grp[0][4]), arr(3), C, ptr(dw_ih), ptr(db_ih), ptr(dw_hh),
+                                                      ptr(db_hh), N, ptr(ws), ws.numel(), ptr(add[0]), ptr(add[1]), ptr(add[2]), ptr(add[3]), st)
                 else:
-                    check(lib.glam_wgrad_gemm_pair_split_seg(n, arr(0), M, M, arr(1), C, C, int(grp[0][4]), ptr(dw_ih), ptr(db_ih), arr(2), M, M,
-                                                             arr(3), C, C, 0, ptr(dw_hh), ptr(db_hh), N, ptr(ws), ws.numel(), ptr(add[0]),
-                                                             ptr(add[1]), ptr(add[2]), ptr(add[3]), st), "glam_wgrad_gemm_pair_split_seg")
+                    lib.glam_wgrad_gemm_pair_split_seg(n, arr(0), M, M, arr(1), C, C, int(grp[0][4]), ptr(dw_ih), ptr(db_ih), arr(2), M, M,
+                                                       arr(3), C, C, 0, ptr(dw_hh), ptr(db_hh), N, ptr(ws), ws.numel(), ptr(add[0]),
+                                                       ptr(add[1]), ptr(add[2]), ptr(add[3]), st)
                 add = [dw_ih, db_ih, dw_hh, db_hh]        # a further group adds onto the result in place
             return dx, dh, d_id, None, None, None, None, None, None, None, flat, None, None, None
         # [d_W | d_b] of both linears: out[m, k] = sum_n dy[n, m] * [x | 1][n, k], two products, one launch + one reduction
@@ -1259,13 +1233,11 @@ class _GruBlock(torch.autograd.Function):
             d_carry = None
         if gates:
             one = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())
-            check(lib.glam_wgrad_gemm_gru_gates_seg(1, one(d_gi), C, one(x), C, int(celu_q), one(h), C, ptr(dw_ih), ptr(db_ih), ptr(dw_hh),
-                                                    ptr(db_hh), N, ptr(ws), ws.numel(), ptr(dc[0]), ptr(dc[1]), ptr(dc[2]), ptr(dc[3]), st),
-                  "glam_wgrad_gemm_gru_gates_seg")
+            lib.glam_wgrad_gemm_gru_gates_seg(1, one(d_gi), C, one(x), C, int(celu_q), one(h), C, ptr(dw_ih), ptr(db_ih), ptr(dw_hh),
+                                              ptr(db_hh), N, ptr(ws), ws.numel(), ptr(dc[0]), ptr(dc[1]), ptr(dc[2]), ptr(dc[3]), st)
         else:
-            check(lib.glam_wgrad_gemm_pair_split(ptr(d_gi), M, M, ptr(x), C, C, int(celu_q), ptr(dw_ih), ptr(db_ih),
-                                                 ptr(d_gh), M, M, ptr(h), C, C, 0, ptr(dw_hh), ptr(db_hh), N, ptr(ws), ws.numel(),
-                                                 ptr(dc[0]), ptr(dc[1]), ptr(dc[2]), ptr(dc[3]), st), "glam_wgrad_gemm_pair_split")
+            lib.glam_wgrad_gemm_pair_split(ptr(d_gi), M, M, ptr(x), C, C, int(celu_q), ptr(dw_ih), ptr(db_ih), ptr(d_gh), M, M, ptr(h), C, C, 0,
+                                           ptr(dw_hh), ptr(db_hh), N, ptr(ws), ws.numel(), ptr(dc[0]), ptr(dc[1]), ptr(dc[2]), ptr(dc[3]), st)
         if ctx.carried:
             return dx, dh, d_id, None, None, None, None, None, None, None, _o._carried(flat, d_carry), None, None, None
         return dx, dh, d_id, dw_ih.view(M, C), dw_hh.view(M, C), db_ih, db_hh, None, None, None, None, None, None, None

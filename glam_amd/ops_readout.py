@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from . import ops as _o
-from ._lib import GlamHipError, check, f32c, ptr, require_device, stream
+from ._lib import GlamHipError, f32c, ptr, require_device, stream
 
 # --------------------------------------------------------------------------------------
 # readouts
@@ -28,8 +28,7 @@ class _Pool5(torch.autograd.Function):
             raise GlamHipError(f"pool: x has {N} rows but batch has {sp.N}")
         out = torch.empty(sp.B, (2 + k) * D, dtype=torch.float32, device=x.device)
         topk = torch.empty(sp.B, k, dtype=torch.int32, device=x.device)
-        check(_lib.load().glam_pool5_padded_fwd(ptr(x), ptr(sp.ptr), N, sp.B, ld, D, k, ptr(out), ptr(topk), stream()),
-              "glam_pool5_fwd")
+        _lib.api().glam_pool5_padded_fwd(ptr(x), ptr(sp.ptr), N, sp.B, ld, D, k, ptr(out), ptr(topk), stream())
         ctx.save_for_backward(topk)
         ctx.sp, ctx.dims = sp, (N, ld, D, k)
         return out
@@ -42,8 +41,7 @@ class _Pool5(torch.autograd.Function):
         sp = ctx.sp
         d_out = f32c(d_out, "d_out")
         d_x = torch.empty(N, ld, dtype=torch.float32, device=d_out.device)
-        check(_lib.load().glam_pool5_padded_bwd(ptr(d_out), ptr(sp.ptr), ptr(topk), N, sp.B, ld, D, k, ptr(d_x), stream()),
-              "glam_pool5_bwd")
+        _lib.api().glam_pool5_padded_bwd(ptr(d_out), ptr(sp.ptr), ptr(topk), N, sp.B, ld, D, k, ptr(d_x), stream())
         return d_x, None, None, None
 
 
@@ -68,8 +66,7 @@ class _SegmentPool(torch.autograd.Function):
             raise GlamHipError(f"pool: x has {N} rows but batch has {sp.N}")
         out = torch.empty(sp.B, D, dtype=torch.float32, device=x.device)
         argmax = torch.empty(sp.B, D, dtype=torch.int32, device=x.device) if mode == 2 else None
-        check(_lib.load().glam_segment_pool_fwd(ptr(x), ptr(sp.ptr), N, sp.B, D, mode, ptr(out), ptr(argmax), stream()),
-              "glam_segment_pool_fwd")
+        _lib.api().glam_segment_pool_fwd(ptr(x), ptr(sp.ptr), N, sp.B, D, mode, ptr(out), ptr(argmax), stream())
         ctx.sp, ctx.dims, ctx.argmax = sp, (N, D, mode), argmax
         return out
 
@@ -80,8 +77,7 @@ class _SegmentPool(torch.autograd.Function):
         sp = ctx.sp
         d_out = f32c(d_out, "d_out")
         d_x = torch.empty(N, D, dtype=torch.float32, device=d_out.device)
-        check(_lib.load().glam_segment_pool_bwd(ptr(d_out), ptr(sp.ptr), ptr(ctx.argmax), N, sp.B, D, mode, ptr(d_x),
-                                                stream()), "glam_segment_pool_bwd")
+        _lib.api().glam_segment_pool_bwd(ptr(d_out), ptr(sp.ptr), ptr(ctx.argmax), N, sp.B, D, mode, ptr(d_x), stream())
         return d_x, None, None
 
 
@@ -102,8 +98,7 @@ class _SegmentAttn(torch.autograd.Function):
             raise GlamHipError("segment_attention: gate / v / batch disagree on the node count")
         out = torch.empty(sp.B, D, dtype=torch.float32, device=v.device)
         stats = torch.empty(sp.B, 2, dtype=torch.float32, device=v.device)
-        check(_lib.load().glam_segment_attn_fwd(ptr(gate), ptr(v), ptr(sp.ptr), N, sp.B, D, ptr(out), ptr(stats), stream()),
-              "glam_segment_attn_fwd")
+        _lib.api().glam_segment_attn_fwd(ptr(gate), ptr(v), ptr(sp.ptr), N, sp.B, D, ptr(out), ptr(stats), stream())
         ctx.save_for_backward(gate, v, out, stats)
         ctx.sp = sp
         return out
@@ -116,8 +111,8 @@ class _SegmentAttn(torch.autograd.Function):
         N, D = v.shape
         d_out = f32c(d_out, "d_out")
         d_gate, d_v = torch.empty_like(gate), torch.empty_like(v)
-        check(_lib.load().glam_segment_attn_bwd(ptr(gate), ptr(v), ptr(out), ptr(stats), ptr(d_out), ptr(sp.ptr), N,
-                                                sp.B, D, ptr(d_gate), ptr(d_v), stream()), "glam_segment_attn_bwd")
+        _lib.api().glam_segment_attn_bwd(ptr(gate), ptr(v), ptr(out), ptr(stats), ptr(d_out), ptr(sp.ptr), N,
+                                         sp.B, D, ptr(d_gate), ptr(d_v), stream())
         return d_gate, d_v, None
 
 
@@ -139,15 +134,13 @@ class _BiasResAct(torch.autograd.Function):
         if rng is None:
             if act == _o.ACT_CODES["rrelu"] or not want_out:
                 raise GlamHipError("bias_res_act: 'rrelu' / dropout-only need rng=(lower, upper, drop_p)")
-            check(_lib.load().glam_bias_res_act_fwd(ptr(y), ptr(bias), ptr(identity), N, C, act, float(slope), ptr(out), stream()),
-                  "glam_bias_res_act_fwd")
+            _lib.api().glam_bias_res_act_fwd(ptr(y), ptr(bias), ptr(identity), N, C, act, float(slope), ptr(out), stream())
         else:
             lo, hi, p = (float(v) for v in rng)
             eff = torch.empty(2, dtype=torch.int64, device=y.device)
             out_drop = torch.empty_like(y) if p > 0 else None
-            check(_lib.load().glam_bias_res_act_rng_fwd(ptr(y), ptr(bias), ptr(identity), N, C, act, float(slope), lo, hi, p,
-                                                        ptr(_o.rng_state(y.device)), ptr(eff), ptr(out), ptr(out_drop), stream()),
-                  "glam_bias_res_act_rng_fwd")
+            _lib.api().glam_bias_res_act_rng_fwd(ptr(y), ptr(bias), ptr(identity), N, C, act, float(slope), lo, hi, p,
+                                                 ptr(_o.rng_state(y.device)), ptr(eff), ptr(out), ptr(out_drop), stream())
         ctx.save_for_backward(*([out] if out is not None else []))
         ctx.eff = eff
         ctx.shape = (N, C)
@@ -165,10 +158,10 @@ class _BiasResAct(torch.autograd.Function):
         ref = d_out if d_out is not None else d_out_drop
         d_y = torch.empty_like(ref)
         if rng is None:
-            check(_lib.load().glam_bias_res_act_bwd(ptr(out), ptr(d_out), N, C, act, slope, ptr(d_y), stream()), "glam_bias_res_act_bwd")
+            _lib.api().glam_bias_res_act_bwd(ptr(out), ptr(d_out), N, C, act, slope, ptr(d_y), stream())
         else:
-            check(_lib.load().glam_bias_res_act_rng_bwd(ptr(out), ptr(d_out), ptr(d_out_drop), N, C, act, slope, rng[0], rng[1], rng[2],
-                                                        ptr(ctx.eff), ptr(d_y), stream()), "glam_bias_res_act_rng_bwd")
+            _lib.api().glam_bias_res_act_rng_bwd(ptr(out), ptr(d_out), ptr(d_out_drop), N, C, act, slope, rng[0], rng[1], rng[2],
+                                                 ptr(ctx.eff), ptr(d_y), stream())
         return d_y, (d_y.sum(0) if has_bias else None), (d_y if has_id else None), None, None, None, None
 
 
@@ -206,7 +199,7 @@ class _LstmCell(torch.autograd.Function):
         gates, c_prev = f32c(gates, "gates"), f32c(c_prev, "c")
         B, C = c_prev.shape
         h_new, c_new = torch.empty_like(c_prev), torch.empty_like(c_prev)
-        check(_lib.load().glam_lstm_cell_fwd(ptr(gates), ptr(c_prev), B, C, ptr(h_new), ptr(c_new), stream()), "glam_lstm_cell_fwd")
+        _lib.api().glam_lstm_cell_fwd(ptr(gates), ptr(c_prev), B, C, ptr(h_new), ptr(c_new), stream())
         ctx.save_for_backward(gates, c_prev)
         return h_new, c_new
 
@@ -218,8 +211,7 @@ class _LstmCell(torch.autograd.Function):
         d_h = None if d_h is None else f32c(d_h, "d_h")
         d_c = None if d_c is None else f32c(d_c, "d_c")
         d_gates, d_cp = torch.empty_like(gates), torch.empty_like(c_prev)
-        check(_lib.load().glam_lstm_cell_bwd(ptr(gates), ptr(c_prev), ptr(d_h), ptr(d_c), B, C, ptr(d_gates), ptr(d_cp), stream()),
-              "glam_lstm_cell_bwd")
+        _lib.api().glam_lstm_cell_bwd(ptr(gates), ptr(c_prev), ptr(d_h), ptr(d_c), B, C, ptr(d_gates), ptr(d_cp), stream())
         return d_gates, d_cp
 
 
@@ -239,7 +231,7 @@ class _QueryAttention(torch.autograd.Function):
             raise GlamHipError("query_attention: x / q disagree with the batch vector")
         r = torch.empty(sp.B, D, dtype=torch.float32, device=x.device)
         stats = torch.empty(sp.B, 2, dtype=torch.float32, device=x.device)
-        check(_lib.load().glam_s2s_attn_fwd(ptr(x), ptr(q), ptr(sp.ptr), N, sp.B, D, ptr(r), ptr(stats), stream()), "glam_s2s_attn_fwd")
+        _lib.api().glam_s2s_attn_fwd(ptr(x), ptr(q), ptr(sp.ptr), N, sp.B, D, ptr(r), ptr(stats), stream())
         ctx.save_for_backward(x, q, r, stats)
         ctx.sp = sp
         return r
@@ -251,8 +243,8 @@ class _QueryAttention(torch.autograd.Function):
         sp = ctx.sp
         d_r = f32c(d_r, "d_r")
         d_x, d_q = torch.empty_like(x), torch.empty_like(q)
-        check(_lib.load().glam_s2s_attn_bwd(ptr(x), ptr(q), ptr(r), ptr(stats), ptr(d_r), ptr(sp.ptr), x.size(0), sp.B, x.size(1),
-                                            ptr(d_x), ptr(d_q), stream()), "glam_s2s_attn_bwd")
+        _lib.api().glam_s2s_attn_bwd(ptr(x), ptr(q), ptr(r), ptr(stats), ptr(d_r), ptr(sp.ptr), x.size(0), sp.B, x.size(1),
+                                     ptr(d_x), ptr(d_q), stream())
         return d_x, d_q, None
 
 
@@ -279,8 +271,7 @@ class _EdgeReduce(torch.autograd.Function):
             raise GlamHipError(f"edge_reduce: {E} messages for {gi.E} edges")
         out = torch.empty(gi.N, D, dtype=torch.float32, device=msg.device)
         argmax = torch.empty(gi.N, D, dtype=torch.int32, device=msg.device) if mode == 2 else None
-        check(_lib.load().glam_edge_reduce_fwd(ptr(msg), ptr(gi.rowptr), ptr(gi.eid), gi.N, E, D, mode, ptr(out),
-                                               ptr(argmax), stream()), "glam_edge_reduce_fwd")
+        _lib.api().glam_edge_reduce_fwd(ptr(msg), ptr(gi.rowptr), ptr(gi.eid), gi.N, E, D, mode, ptr(out), ptr(argmax), stream())
         ctx.gi, ctx.dims, ctx.argmax = gi, (E, D, mode), argmax
         return out
 
@@ -291,8 +282,7 @@ class _EdgeReduce(torch.autograd.Function):
         gi = ctx.gi
         d_out = f32c(d_out, "d_out")
         d_msg = torch.empty(E, D, dtype=torch.float32, device=d_out.device)
-        check(_lib.load().glam_edge_reduce_bwd(ptr(d_out), ptr(gi.rowptr), ptr(gi.eid), ptr(ctx.argmax), gi.N, E, D,
-                                               mode, ptr(d_msg), stream()), "glam_edge_reduce_bwd")
+        _lib.api().glam_edge_reduce_bwd(ptr(d_out), ptr(gi.rowptr), ptr(gi.eid), ptr(ctx.argmax), gi.N, E, D, mode, ptr(d_msg), stream())
         return d_msg, None, None
 
 
@@ -320,13 +310,11 @@ class _GraphNorm(torch.autograd.Function):
             # the training-mode Dropout(drop_p) behind the norm from the same launch: the output IS the dropped tensor (graph_norm_drop_supported)
             y = torch.empty_like(x)
             ctx.eff = torch.empty(2, dtype=torch.int64, device=x.device)
-            check(_lib.load().glam_graph_norm_drop_fwd(ptr(x), ptr(sp.ptr), N, sp.B, D, mode, float(scale), float(eps), float(drop_p),
-                                                       ptr(_o.rng_state(x.device)), ptr(ctx.eff), None, ptr(y), stream()),
-                  "glam_graph_norm_drop_fwd")
+            _lib.api().glam_graph_norm_drop_fwd(ptr(x), ptr(sp.ptr), N, sp.B, D, mode, float(scale), float(eps), float(drop_p),
+                                                ptr(_o.rng_state(x.device)), ptr(ctx.eff), None, ptr(y), stream())
         else:
             y = torch.zeros_like(x) if sp.B == 0 else torch.empty_like(x)
-            check(_lib.load().glam_graph_norm_fwd(ptr(x), ptr(sp.ptr), N, sp.B, D, mode, float(scale), float(eps), ptr(y), stream()),
-                  "glam_graph_norm_fwd")
+            _lib.api().glam_graph_norm_fwd(ptr(x), ptr(sp.ptr), N, sp.B, D, mode, float(scale), float(eps), ptr(y), stream())
         ctx.save_for_backward(x)
         ctx.sp, ctx.cfg = sp, (mode, float(scale), float(eps))
         if with_identity:
@@ -345,18 +333,15 @@ class _GraphNorm(torch.autograd.Function):
             return d_id, None, None, None, None, None, None
         gy = f32c(gy, "gy")
         dx = torch.empty_like(x)
-        lib = _lib.load()
+        lib = _lib.api()
         if ctx.drop_p > 0:              # gy is the gradient of the DROPPED output: the mask is regenerated inside the launch
-            check(lib.glam_graph_norm_drop_bwd(ptr(x), None, ptr(gy), ptr(sp.ptr), N, sp.B, D, mode, scale, eps, ctx.drop_p, ptr(ctx.eff),
-                                               ptr(None if d_id is None else f32c(d_id, "d_identity")), ptr(dx), stream()),
-                  "glam_graph_norm_drop_bwd")
+            lib.glam_graph_norm_drop_bwd(ptr(x), None, ptr(gy), ptr(sp.ptr), N, sp.B, D, mode, scale, eps, ctx.drop_p, ptr(ctx.eff),
+                                         ptr(None if d_id is None else f32c(d_id, "d_identity")), ptr(dx), stream())
             return dx, None, None, None, None, None, None
         if d_id is not None and N > 0 and sp.B > 0:
-            check(lib.glam_graph_norm_bwd_add(ptr(x), ptr(gy), ptr(sp.ptr), N, sp.B, D, mode, scale, eps, ptr(f32c(d_id, "d_identity")), ptr(dx),
-                                              stream()), "glam_graph_norm_bwd_add")
+            lib.glam_graph_norm_bwd_add(ptr(x), ptr(gy), ptr(sp.ptr), N, sp.B, D, mode, scale, eps, ptr(f32c(d_id, "d_identity")), ptr(dx), stream())
             return dx, None, None, None, None, None, None
-        check(lib.glam_graph_norm_bwd(ptr(x), ptr(gy), ptr(sp.ptr), N, sp.B, D, mode, scale, eps, ptr(dx), stream()),
-              "glam_graph_norm_bwd")
+        lib.glam_graph_norm_bwd(ptr(x), ptr(gy), ptr(sp.ptr), N, sp.B, D, mode, scale, eps, ptr(dx), stream())
         if d_id is not None:
             dx = d_id if (N == 0 or sp.B == 0) else dx + d_id
         return dx, None, None, None, None, None, None
@@ -365,7 +350,7 @@ class _GraphNorm(torch.autograd.Function):
 def graph_norm_drop_supported(x, sp):
     """The norm + Dropout launch pair exists for this shape (molecule-sized graphs, a multiple of 4 channels <= 64)."""
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and sp.B > 0
-            and _lib.load().glam_graph_norm_drop_supported(x.size(0), sp.B, x.size(1)) == 1)
+            and _lib.api().glam_graph_norm_drop_supported(x.size(0), sp.B, x.size(1)) == 1)
 
 
 def pair_norm(x, sp, scale=1.0, eps=1e-5, with_identity=False, drop_p=0.0):
@@ -390,8 +375,8 @@ class _EdgeWeightedSum(torch.autograd.Function):
         if N != gi.N or E != gi.E:
             raise GlamHipError("edge_weighted_sum: x / w disagree with the edge list")
         out = torch.empty(N, K + int(self_slot), D, dtype=torch.float32, device=x.device)
-        check(_lib.load().glam_edge_wsum_fwd(ptr(x), ptr(w), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), N, E, D, K, int(mean),
-                                             int(self_slot), ptr(out), stream()), "glam_edge_wsum_fwd")
+        _lib.api().glam_edge_wsum_fwd(ptr(x), ptr(w), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), N, E, D, K, int(mean),
+                                      int(self_slot), ptr(out), stream())
         ctx.save_for_backward(w)
         ctx.gi, ctx.cfg = gi, (N, E, D, K, int(mean), int(self_slot))
         ctx.aliased = bool(with_identity)
@@ -411,16 +396,15 @@ class _EdgeWeightedSum(torch.autograd.Function):
         d_out = f32c(d_out, "d_out")
         colptr, dst, eid_t = gi.transpose()
         dx = torch.empty(N, D, dtype=torch.float32, device=d_out.device)
-        lib = _lib.load()
+        lib = _lib.api()
         d_alias = None if d_alias is None else f32c(d_alias, "d_identity")
         if d_alias is not None and K in (4, 8) and D % 4 == 0 and all(t.data_ptr() % 16 == 0 for t in (d_out, w, d_alias)):
             # the skip connection's gradient joins the sums in this launch (no add launch of the autograd engine); the launch
             # exists for 16-byte aligned operands only (glam_edge_wsum_bwd_add refuses the rest)
-            check(lib.glam_edge_wsum_bwd_add(ptr(d_out), ptr(w), ptr(colptr), ptr(dst), ptr(eid_t), ptr(gi.rowptr), N, E, D, K, mean, self_slot,
-                                             ptr(d_alias), ptr(dx), stream()), "glam_edge_wsum_bwd_add")
+            lib.glam_edge_wsum_bwd_add(ptr(d_out), ptr(w), ptr(colptr), ptr(dst), ptr(eid_t), ptr(gi.rowptr), N, E, D, K, mean, self_slot,
+                                       ptr(d_alias), ptr(dx), stream())
             return dx, None, None, None, None, None
-        check(lib.glam_edge_wsum_bwd(ptr(d_out), ptr(w), ptr(colptr), ptr(dst), ptr(eid_t), ptr(gi.rowptr), N, E, D, K,
-                                     mean, self_slot, ptr(dx), stream()), "glam_edge_wsum_bwd")
+        lib.glam_edge_wsum_bwd(ptr(d_out), ptr(w), ptr(colptr), ptr(dst), ptr(eid_t), ptr(gi.rowptr), N, E, D, K, mean, self_slot, ptr(dx), stream())
         return (dx if d_alias is None else dx + d_alias), None, None, None, None, None
 
 
@@ -452,7 +436,7 @@ class _NNConvECStack(torch.autograd.Function):
         w1, b1, root = f32c(w1, "nn.2.weight"), f32c(b1, "nn.2.bias"), f32c(root, "root")
         Cin, Cout = root.shape
         out = torch.empty(34 * Cin, Cout, dtype=torch.float32, device=w1.device)
-        check(_lib.load().glam_nnconv_ec_stack(ptr(w1), ptr(b1), ptr(root), Cin, Cout, ptr(out), stream()), "glam_nnconv_ec_stack")
+        _lib.api().glam_nnconv_ec_stack(ptr(w1), ptr(b1), ptr(root), Cin, Cout, ptr(out), stream())
         ctx.dims = (Cin, Cout)
         return out
 
@@ -464,7 +448,7 @@ class _NNConvECStack(torch.autograd.Function):
         dw1 = torch.empty(Cin * Cout, 32, dtype=torch.float32, device=d_ws.device)
         db1 = torch.empty(Cin * Cout, dtype=torch.float32, device=d_ws.device)
         droot = torch.empty(Cin, Cout, dtype=torch.float32, device=d_ws.device)
-        check(_lib.load().glam_nnconv_ec_unstack(ptr(d_ws), Cin, Cout, ptr(dw1), ptr(db1), ptr(droot), stream()), "glam_nnconv_ec_unstack")
+        _lib.api().glam_nnconv_ec_unstack(ptr(d_ws), Cin, Cout, ptr(dw1), ptr(db1), ptr(droot), stream())
         return dw1, db1, droot
 
 
@@ -486,13 +470,13 @@ class _NNConvEC(torch.autograd.Function):
         Cout = wstack.size(1)
         if N != gi.N or E != gi.E or wstack.size(0) != 34 * Cin or tuple(w0.shape) != (32, De):
             raise GlamHipError("nnconv_edge_conditioned: x / edge_attr / weights disagree with the edge list")
-        lib = _lib.load()
+        lib = _lib.api()
         h = torch.empty(E, 32, dtype=torch.float32, device=x.device)
         out = torch.empty(N, Cout, dtype=torch.float32, device=x.device)
         nws = lib.glam_nnconv_ec_workspace_bytes(N, E, De, Cin, Cout, 0)
         ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=x.device)
-        check(lib.glam_nnconv_ec_fwd(ptr(x), ptr(ea), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), N, E, De, Cin, Cout, ptr(w0), ptr(b0),
-                                     ptr(wstack), ptr(bias), int(mean), ptr(h), ptr(ws), ws.numel(), ptr(out), stream()), "glam_nnconv_ec_fwd")
+        lib.glam_nnconv_ec_fwd(ptr(x), ptr(ea), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), N, E, De, Cin, Cout, ptr(w0), ptr(b0),
+                               ptr(wstack), ptr(bias), int(mean), ptr(h), ptr(ws), ws.numel(), ptr(out), stream())
         del ws
         ctx.save_for_backward(x, ea, wstack, h)
         ctx.gi, ctx.dims, ctx.has_bias = gi, (N, E, De, Cin, Cout, int(mean)), bias is not None
@@ -517,16 +501,16 @@ class _NNConvEC(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         dx, dw0, db0 = torch.empty(N, Cin, **f32), torch.empty(32, De, **f32), torch.empty(32, **f32)
         dws, dbias = torch.empty(34 * Cin, Cout, **f32), torch.empty(Cout, **f32)
-        lib = _lib.load()
+        lib = _lib.api()
         ws = torch.empty(max(lib.glam_nnconv_ec_workspace_bytes(N, E, De, Cin, Cout, 1), 16), dtype=torch.uint8, device=dev)
-        check(lib.glam_nnconv_ec_bwd(ptr(d_out), ptr(x), ptr(ea), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t),
-                                     N, E, De, Cin, Cout, ptr(wstack), ptr(h), mean, ptr(d_alias), ptr(dx), ptr(dw0), ptr(db0), ptr(dws),
-                                     ptr(dbias), ptr(ws), ws.numel(), stream()), "glam_nnconv_ec_bwd")
+        lib.glam_nnconv_ec_bwd(ptr(d_out), ptr(x), ptr(ea), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t),
+                               N, E, De, Cin, Cout, ptr(wstack), ptr(h), mean, ptr(d_alias), ptr(dx), ptr(dw0), ptr(db0), ptr(dws),
+                               ptr(dbias), ptr(ws), ws.numel(), stream())
         return dx, None, None, dw0, db0, dws, (dbias if ctx.has_bias else None), None, None
 
 
 def nnconv_ec_supported(De, hidden, Cin, Cout):
-    return _lib.load().glam_nnconv_ec_supported(De, hidden, Cin, Cout) == 1
+    return _lib.api().glam_nnconv_ec_supported(De, hidden, Cin, Cout) == 1
 
 
 def nnconv_edge_conditioned(x, edge_attr, gi, w0, b0, w1, b1, root, bias, mean=True, with_identity=False, wstack=None):
@@ -556,10 +540,9 @@ class _PairPool(torch.autograd.Function):
         out = torch.empty(P, 2, dtype=torch.float32, device=mol.device)
         arg = torch.empty(P, 2, dtype=torch.int32, device=mol.device)
         sums = torch.empty(P, 2, D, dtype=torch.float32, device=mol.device)
-        lib = _lib.load()
+        lib = _lib.api()
         ws = torch.empty(max(lib.glam_pair_pool_workspace_bytes(P, D), 16), dtype=torch.uint8, device=mol.device)
-        check(lib.glam_pair_pool_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), P, D, ptr(out), ptr(arg), ptr(sums), ptr(ws),
-                                     ws.numel(), stream()), "glam_pair_pool_fwd")
+        lib.glam_pair_pool_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), P, D, ptr(out), ptr(arg), ptr(sums), ptr(ws), ws.numel(), stream())
         ctx.save_for_backward(mol, pro, arg, sums)
         ctx.sps = (msp, psp)
         ctx.aliased = bool(with_identity)
@@ -577,15 +560,15 @@ class _PairPool(torch.autograd.Function):
             return d_ma, d_pa, None, None, None
         d_out = f32c(d_out, "d_out")
         d_mol, d_pro = torch.empty_like(mol), torch.empty_like(pro)
-        lib = _lib.load()
+        lib = _lib.api()
         if d_ma is not None or d_pa is not None:
             d_ma = None if d_ma is None else f32c(d_ma, "d_mol (next use)")
             d_pa = None if d_pa is None else f32c(d_pa, "d_pro (next use)")
-            check(lib.glam_pair_pool_bwd_add(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(arg), ptr(sums), ptr(d_out), msp.B, mol.size(1),
-                                             ptr(d_ma), ptr(d_pa), ptr(d_mol), ptr(d_pro), stream()), "glam_pair_pool_bwd_add")
+            lib.glam_pair_pool_bwd_add(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(arg), ptr(sums), ptr(d_out), msp.B, mol.size(1),
+                                       ptr(d_ma), ptr(d_pa), ptr(d_mol), ptr(d_pro), stream())
         else:
-            check(lib.glam_pair_pool_bwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(arg), ptr(sums), ptr(d_out), msp.B,
-                                         mol.size(1), ptr(d_mol), ptr(d_pro), stream()), "glam_pair_pool_bwd")
+            lib.glam_pair_pool_bwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(arg), ptr(sums), ptr(d_out), msp.B,
+                                   mol.size(1), ptr(d_mol), ptr(d_pro), stream())
         return d_mol, d_pro, None, None, None
 
 
@@ -597,7 +580,7 @@ def pair_pool(mol_out, pro_out, msp, psp, with_identity=False):
         D = mol_out.size(1)
         if (torch.is_grad_enabled() and mol_out.requires_grad and pro_out.requires_grad and mol_out.is_cuda
                 and mol_out.dtype == torch.float32 and pro_out.dtype == torch.float32 and mol_out.size(1) == pro_out.size(1)
-                and _lib.load().glam_pair_pool_add_supported(D) == 1):
+                and _lib.api().glam_pair_pool_add_supported(D) == 1):
             return _PairPool.apply(mol_out, pro_out, msp, psp, True)
         return _PairPool.apply(mol_out, pro_out, msp, psp), mol_out, pro_out
     return _PairPool.apply(mol_out, pro_out, msp, psp)
@@ -613,8 +596,7 @@ class _PairPool5(torch.autograd.Function):
         P, D = msp.B, mol.size(1)
         out = torch.empty(P, 5, dtype=torch.float32, device=mol.device)
         arg = torch.empty(P, 6, dtype=torch.int32, device=mol.device)
-        check(_lib.load().glam_pair_pool5_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), P, D, ptr(out), ptr(arg), stream()),
-              "glam_pair_pool5_fwd")
+        _lib.api().glam_pair_pool5_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), P, D, ptr(out), ptr(arg), stream())
         ctx.save_for_backward(mol, pro, out, arg)
         ctx.sps = (msp, psp)
         return out
@@ -626,8 +608,8 @@ class _PairPool5(torch.autograd.Function):
         msp, psp = ctx.sps
         d_out = f32c(d_out, "d_out")
         d_mol, d_pro = torch.empty_like(mol), torch.empty_like(pro)
-        check(_lib.load().glam_pair_pool5_bwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(out), ptr(arg), ptr(d_out), msp.B,
-                                              mol.size(1), ptr(d_mol), ptr(d_pro), stream()), "glam_pair_pool5_bwd")
+        _lib.api().glam_pair_pool5_bwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(out), ptr(arg), ptr(d_out), msp.B,
+                                       mol.size(1), ptr(d_mol), ptr(d_pro), stream())
         return d_mol, d_pro, None, None
 
 

@@ -122,7 +122,7 @@ class _FlatStateOptimizer(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _lib.load()
+        lib = _lib.api()
         from . import ops
         ops.parameters_written()         # the launch below writes parameters through raw pointers: no version counter moves
         with torch.no_grad():
@@ -236,11 +236,9 @@ class Adam(_FlatStateOptimizer):
     def _call(self, lib, group, plan, table, numel, keep):
         lr_dev, lr = self._lr_arg(group)
         b1, b2 = group["betas"]
-        rc = lib.glam_adam_step(table.ctypes.data, numel.ctypes.data, len(numel), plan.step.data_ptr(), plan.ticket.data_ptr(),
-                                lr_dev.data_ptr() if lr_dev is not None else None, float(lr), float(b1), float(b2), float(group["eps"]),
-                                float(group["weight_decay"]), torch.cuda.current_stream(plan.step.device).cuda_stream)
-        if rc != 0:
-            raise GlamHipError(f"glam_adam_step failed (code {rc}): {lib.glam_last_error().decode()}")
+        lib.glam_adam_step(table.ctypes.data, numel.ctypes.data, len(numel), plan.step.data_ptr(), plan.ticket.data_ptr(),
+                           lr_dev.data_ptr() if lr_dev is not None else None, float(lr), float(b1), float(b2), float(group["eps"]),
+                           float(group["weight_decay"]), torch.cuda.current_stream(plan.step.device).cuda_stream)
 
     def state_dict(self):
         """``torch.optim.Adam``'s layout with a PRIVATE ``step`` per parameter: internally every parameter of a group shares one device
@@ -306,13 +304,10 @@ class Ranger(_FlatStateOptimizer):
         if int(k) != k or k < 1:
             raise ValueError(f'Invalid lookahead steps: {k}')
         b1, b2 = group["betas"]
-        rc = lib.glam_ranger_step(table.ctypes.data, numel.ctypes.data, row.ctypes.data, len(numel), plan.step.data_ptr(),
-                                  plan.ticket.data_ptr(), lr_dev.data_ptr() if lr_dev is not None else None, float(lr), float(b1),
-                                  float(b2), float(group["eps"]), float(group["weight_decay"]), float(self.alpha), int(k),
-                                  float(self.N_sma_threshhold), 1 if self.gc_loc else 0,
-                                  torch.cuda.current_stream(plan.step.device).cuda_stream)
-        if rc != 0:
-            raise GlamHipError(f"glam_ranger_step failed (code {rc}): {lib.glam_last_error().decode()}")
+        lib.glam_ranger_step(table.ctypes.data, numel.ctypes.data, row.ctypes.data, len(numel), plan.step.data_ptr(), plan.ticket.data_ptr(),
+                             lr_dev.data_ptr() if lr_dev is not None else None, float(lr), float(b1), float(b2), float(group["eps"]),
+                             float(group["weight_decay"]), float(self.alpha), int(k), float(self.N_sma_threshhold), 1 if self.gc_loc else 0,
+                             torch.cuda.current_stream(plan.step.device).cuda_stream)
 
     def state_dict(self):
         """The reference's layout: ``step`` a Python int per parameter, the buffers copied out of the flat storage (a checkpoint loaded

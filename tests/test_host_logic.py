@@ -14,10 +14,33 @@ from glam_amd.data import Batch, Data, DataLoader, synth_batch, synth_molecule, 
 from tests.conftest import ROOT, Golden, assert_close
 
 
-def _header_functions():
+def _header_source():
     src = open(os.path.join(ROOT, "include", "glam_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(glam_[a-z0-9_]+)\s*\(", src)))
+    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+
+def _header_functions():
+    return sorted(set(re.findall(r"\b(glam_[a-z0-9_]+)\s*\(", _header_source())))
+
+
+_C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
+              "size_t": ctypes.c_size_t}
+
+
+def _header_prototypes():
+    """name -> (return type, [parameter types]) of every prototype of include/glam_hip.h (they span lines up to ';'); a type is the
+    ctypes scalar of _C_SCALARS, or "pointer" for anything with a '*'.  A type this does not know is a KeyError: extend the table."""
+    def ctype(decl, named):
+        words = [w for w in decl.split() if w != "const"]
+        return "pointer" if "*" in decl else _C_SCALARS[" ".join(words[:-1] if named else words)]
+
+    src = re.sub(r"^\s*#.*$", "", _header_source(), flags=re.M)
+    return {name: (ctype(ret, False), [] if params.strip() == "void" else [ctype(q, True) for q in params.split(",")])
+            for ret, name, params in re.findall(r"([\w \t*]+?)\b(glam_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src)}
+
+
+def _table_type(t):
+    return "pointer" if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer) else t
 
 
 def test_library_exports_every_declared_symbol():
@@ -28,6 +51,69 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), f"libglam_hip.so does not export {n}"
     assert sorted(_lib.SIGNATURES) == names, "ctypes table and include/glam_hip.h disagree"
     assert _lib.load().glam_abi_version() == _lib.ABI_VERSION == 4
+
+
+def test_signature_table_has_the_types_of_the_header():
+    """Names alone load fine with an int bound as int64_t, a float as double or an argument missing, and corrupt the call: every
+    entry of SIGNATURES has the return type and, position by position, the parameter types of its prototype.  The header is the truth."""
+    protos = _header_prototypes()
+    assert sorted(protos) == _header_functions()
+    wrong = []
+    for name, (res, args) in _lib.SIGNATURES.items():
+        table = (_table_type(res), [_table_type(a) for a in args])
+        if table != protos[name]:
+            wrong.append(f"{name}: header {protos[name]}, table {table}")
+    assert not wrong, "\n".join(wrong)
+
+
+# the int-returning entry points whose int is a value, not a status: the checked view hands it through.  Adding one is an edit HERE too.
+_UNCHECKED_INT = ["glam_abi_version", "glam_route_enabled", "glam_prof_end", "glam_ce_loss_max_classes", "glam_adam_max_tensors",
+                  "glam_ranger_max_tensors", "glam_nnconv_ec_supported", "glam_pair_pool_add_supported", "glam_triplet_fwd_ell_supported",
+                  "glam_triplet_layer_ws_supported", "glam_triplet_layer_infer_supported", "glam_relation_mlp_supported",
+                  "glam_gru_fused_supported", "glam_gru_ws_supported", "glam_linear_narrow_supported", "glam_ts_gemm_relu_supported",
+                  "glam_ts_gemm_rrelu_supported", "glam_graph_norm_drop_supported"]
+
+
+def test_checked_view_checks_every_status_and_nothing_else():
+    api, raw = _lib.api(), _lib.load()
+    assert api is not raw and api is _lib.api()
+    ints = [n for n, (res, _) in _lib.SIGNATURES.items() if res is ctypes.c_int]
+    unchecked = sorted(n for n in ints if getattr(api, n).errcheck is None)
+    assert unchecked == sorted(_UNCHECKED_INT) == sorted(_lib.VALUE_RETURNS)
+    for n, (res, _) in _lib.SIGNATURES.items():
+        assert getattr(raw, n).errcheck is None, f"load() must stay the raw binding ({n})"
+        if res is not ctypes.c_int:
+            assert getattr(api, n).errcheck is None, f"{n} returns a value"
+        elif n not in _UNCHECKED_INT:
+            assert getattr(api, n).errcheck is not None, f"{n} returns a status the checked view does not check"
+
+
+def test_checked_view_raises_where_the_raw_binding_returns_a_code():
+    api, raw = _lib.api(), _lib.load()
+    bad_cp = (None, None, None, None, None, None, None, None, 10, 10, 3, 30, 4, 1, 0.2, None, None, None)
+    with pytest.raises(_lib.GlamHipError) as e:
+        api.glam_triplet_fwd(*bad_cp)
+    assert "glam_triplet_fwd" in str(e.value) and "code -1" in str(e.value) and "multiple of 4" in str(e.value)
+    assert str(e.value).startswith("glam_triplet_fwd failed (code -1): ")
+    assert raw.glam_triplet_fwd(*bad_cp) == _lib.GLAM_E_INVALID
+    with pytest.raises(_lib.GlamHipError, match="code -2"):
+        api.glam_triplet_fwd(None, None, None, None, None, None, None, None, 10, 10, 3, 60, 5, 1, 0.2, None, None, None)
+
+
+def test_checked_view_hands_values_through():
+    api, raw = _lib.api(), _lib.load()
+    assert api.glam_nnconv_ec_supported(4, 31, 60, 60) == 0 == raw.glam_nnconv_ec_supported(4, 31, 60, 60)     # (hidden = 32 only)
+    assert raw.glam_nnconv_ec_supported(4, 32, 60, 60) == 1 == api.glam_nnconv_ec_supported(4, 32, 60, 60)
+    assert api.glam_csr_workspace_bytes(1000, 3000) == raw.glam_csr_workspace_bytes(1000, 3000) > 0
+    assert api.glam_abi_version() == raw.glam_abi_version() == _lib.ABI_VERSION
+    assert api.glam_adam_max_tensors() == raw.glam_adam_max_tensors() > 0
+    assert api.glam_last_error() == raw.glam_last_error()
+
+
+def test_check_raises_on_a_non_zero_code_only():
+    assert _lib.check(0, "x") is None
+    with pytest.raises(_lib.GlamHipError, match=r"^x failed \(code -1\): "):
+        _lib.check(-1, "x")
 
 
 def test_abi_rejects_bad_arguments_without_touching_a_gpu():

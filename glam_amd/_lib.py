@@ -127,6 +127,12 @@ SIGNATURES = {
                                    ctypes.POINTER(ctypes.c_double), _i32, _vp, _sz, _vp, _vp]),
     "glam_metrics_regression": (_i32, [_vp, _vp, _i32, _i64, _vp, _sz, _vp, _vp]),
     "glam_metrics_multiclass": (_i32, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp, _sz, _vp, _vp]),
+    "glam_colnorm_workspace_bytes": (_sz, [_i64, _i32]),
+    "glam_batch_norm_fwd": (_i32, [_vp] * 5 + [_i64, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _sz, _i32, _i32, _vp]),
+    "glam_batch_norm_eval_fwd": (_i32, [_vp] * 5 + [_i64, _i32, _f32, _vp, _vp, _vp, _i32, _vp]),
+    "glam_batch_norm_bwd": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _i32, _vp]),
+    "glam_layer_norm_flat_fwd": (_i32, [_vp] * 3 + [_i64, _i32, _f32, _vp, _vp, _vp, _sz, _i32, _i32, _vp]),
+    "glam_layer_norm_flat_bwd": (_i32, [_vp] * 4 + [_i64, _i32, _f32, _vp, _vp, _vp, _vp, _sz, _i32, _i32, _vp]),
     "glam_adam_max_tensors": (_i32, []),
     "glam_adam_step": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp] + [ctypes.c_double] * 5 + [_vp]),
     "glam_ranger_max_tensors": (_i32, []),

@@ -646,6 +646,14 @@ class BatchNorm(torch.nn.Module):
         self.module = torch.nn.BatchNorm1d(in_channels, eps, momentum, affine, track_running_stats)
 
     def forward(self, x):
+        m = self.module
+        # the reference's settings on a float32 [N, C] (training mode: N >= 2) run on csrc/colnorm.hip; everything else is torch's, with
+        # torch's errors (a single row in training mode raises there)
+        if (ops.COLUMN_NORM and ops.column_norm_supported(x) and m.affine and m.track_running_stats and isinstance(m.momentum, float)
+                and x.size(1) == m.num_features and m.weight.dtype == torch.float32 and (x.size(0) >= 2 or not m.training)):
+            if m.training:
+                m.num_batches_tracked.add_(1)
+            return ops.batch_norm(x, m.weight, m.bias, m.running_mean, m.running_var, m.training, m.momentum, m.eps)
         return self.module(x)
 
 
@@ -660,6 +668,10 @@ class LayerNorm(torch.nn.Module):
 
     def forward(self, x, batch=None, with_identity=False):
         ident = x
+        if (batch is None and self.weight is not None and ops.COLUMN_NORM and ops.column_norm_supported(x)
+                and x.size(1) == self.in_channels and self.weight.dtype == torch.float32):
+            out = ops.layer_norm_flat(x, self.weight, self.bias, self.eps)      # statistics and affine from the same launches
+            return (out, ident) if with_identity else out
         if batch is None:
             x = x - x.mean()
             out = x / (x.std(unbiased=False) + self.eps)

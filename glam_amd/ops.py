@@ -1277,6 +1277,8 @@ NORM_DROP = True
 PRESTAGE = True
 # the readout MLP's linear on csrc/dense_x3.hip (0: the GEMM library + separate activation / mask / column-sum launches): A/B switch
 DENSE_LINEAR = True
+# _BatchNorm and the batch-less _LayerNorm on csrc/colnorm.hip (False: torch.nn.BatchNorm1d / the elementwise torch expression): A/B switch
+COLUMN_NORM = True
 # the backward of a ReLU fused into a linear, inside that linear's weight-gradient product (glam_wgrad_gemm_split_relu) where the product
 # is the gradient's only consumer: A/B switch (False: an elementwise launch in front of the product)
 RELU_IN_WGRAD = True
@@ -1284,10 +1286,10 @@ RELU_IN_WGRAD = True
 INFER_FWD = os.environ.get("GLAM_INFER_FWD", "1") != "0"
 
 
-# ---- the dense and readout operator families live in their own modules; their names are part of this namespace ----
-from . import ops_dense as _ops_dense, ops_readout as _ops_readout     # noqa: E402  (they read this module's state at call time)
+# ---- the dense, readout and column-norm operator families live in their own modules; their names are part of this namespace ----
+from . import ops_dense as _ops_dense, ops_norm as _ops_norm, ops_readout as _ops_readout     # noqa: E402  (they read this module's state at call time)
 
-for _m in (_ops_dense, _ops_readout):
+for _m in (_ops_dense, _ops_readout, _ops_norm):
     for _k, _v in vars(_m).items():
         if not _k.startswith("__") and _k != "_o" and _k not in globals():
             globals()[_k] = _v

@@ -947,6 +947,38 @@ int glam_metrics_regression(const void* y, const void* f, int dtype, int64_t n, 
 int glam_metrics_multiclass(const void* score, const void* label, const void* pred, int key_dtype, int label_dtype, int64_t n,
                             int n_class, void* ws, size_t ws_bytes, void* record, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Column norms over a dense, contiguous f32[N, C] (any C >= 1, N * C < 2^31; the 16-byte path when C % 4 == 0 and the [N, C]
+ * pointers are 16-byte aligned, scalar accesses otherwise).  Replaces torch.nn.BatchNorm1d behind _BatchNorm (src_1gp/layer.py:161-167)
+ * and PyG's graph LayerNorm with batch = None behind _LayerNorm (src_1gp/layer.py:170-176; mol_flat and lin_out1, model.py:60-61).
+ * Fixed-order sums, centred variances, no atomics: results are bit-identical from run to run.  DESIGN.md 4.12.
+ *
+ * form: 0 = the library's choice, 1 = one launch (BatchNorm: a block owns a column tile and walks all rows; LayerNorm: one block),
+ * 2 = slab partials + apply launch (needs ws of glam_colnorm_workspace_bytes; form 1 of the LayerNorm backward needs 2 C floats of it).
+ * max_blocks: cap on the grid of each launch (<= 0: the library's 1024); the grid-stride loops cover the rest (test hook).
+ *
+ * BatchNorm, training (N >= 2): y = (x - mean) * rstd * weight + bias with the batch statistics of each column; running_mean <-
+ * (1 - momentum) running_mean + momentum mean, running_var likewise with the UNBIASED variance; save_mean / save_rstd f32[C] are what
+ * the backward reads.  Eval: the same with the running statistics (save_mean = running_mean, save_rstd = 1 / sqrt(running_var + eps)).
+ * Backward: d_bias = sum dy, d_weight = sum dy xhat, dx = weight rstd (dy - mean(dy) - xhat mean(dy xhat)); eval != 0: dx = dy weight rstd. */
+size_t glam_colnorm_workspace_bytes(int64_t N, int C);
+int glam_batch_norm_fwd(const float* x, const float* weight, const float* bias, float* running_mean, float* running_var, int64_t N, int C,
+                        float momentum, float eps, float* y, float* save_mean, float* save_rstd, void* ws, size_t ws_bytes, int form,
+                        int max_blocks, void* stream);
+int glam_batch_norm_eval_fwd(const float* x, const float* weight, const float* bias, const float* running_mean, const float* running_var,
+                             int64_t N, int C, float eps, float* y, float* save_mean, float* save_rstd, int max_blocks, void* stream);
+int glam_batch_norm_bwd(const float* x, const float* dy, const float* weight, const float* mean, const float* rstd, int64_t N, int C,
+                        int eval, float* dx, float* d_weight, float* d_bias, void* ws, size_t ws_bytes, int form, int max_blocks,
+                        void* stream);
+/* Batch-less LayerNorm: m = mean(x), s = sqrt(mean((x - m)^2)) over ALL N * C elements, y = (x - m) / (s + eps) * weight + bias (eps is
+ * added to the standard deviation); stat f32[2] = {m, s} is what the backward reads.  Backward, with g = dy weight: dx = (g - mean(g)) /
+ * (s + eps) - (x - m) mean(g (x - m)) / (s (s + eps)^2), d_weight = sum_rows dy (x - m) / (s + eps), d_bias = sum_rows dy.  A constant
+ * input (s = 0) has no finite gradient. */
+int glam_layer_norm_flat_fwd(const float* x, const float* weight, const float* bias, int64_t N, int C, float eps, float* y, float* stat,
+                             void* ws, size_t ws_bytes, int form, int max_blocks, void* stream);
+int glam_layer_norm_flat_bwd(const float* x, const float* dy, const float* weight, const float* stat, int64_t N, int C, float eps, float* dx,
+                             float* d_weight, float* d_bias, void* ws, size_t ws_bytes, int form, int max_blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

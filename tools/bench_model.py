@@ -22,8 +22,11 @@ ap.add_argument("--preset", default="relu", choices=["relu", "model_default", "r
                      "(model.py:24-33: RReLU x 3, graph_do = end_do = Dropout(0.2), no graph norm) in train(); run_default: run.py:21-38 "
                      "(_NNConv unless --block is given, _PairNorm, flat_do = end_do = Dropout(0.2), RReLU x 3) in train()")
 ap.add_argument("--no-graph", action="store_true")
+ap.add_argument("--no-column-norm", action="store_true", help="_BatchNorm / batch-less _LayerNorm on the torch route (ops.COLUMN_NORM = False)")
 ap.add_argument("--profile", action="store_true")
 args = ap.parse_args()
+if args.no_column_norm:
+    ops.COLUMN_NORM = False
 dev = torch.device("cuda")
 torch.manual_seed(0)
 if args.preset == "relu":

@@ -1,5 +1,6 @@
 """Developer aid: the library's kernel launches of ONE full-model training step, in launch order (glam_prof_* labels and durations; ATen
-launches are not listed: tools/bench_model.py --profile names those).  usage: kernel_sequence.py [batch] [preset]"""
+launches are not listed: tools/bench_model.py --profile names those; the ATen normalisation ops of the step are counted at the end).
+usage: kernel_sequence.py [batch] [preset]      (preset: relu, model_default, colnorm = a norm in every slot)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -13,6 +14,9 @@ torch.manual_seed(0)
 PRESET = sys.argv[2] if len(sys.argv) > 2 else "relu"
 if PRESET == "model_default":      # Architecture()'s keyword defaults in training mode: RReLU x 3, Dropout(0.2) twice
     net = model.Architecture(mol_block="_TripletMessage", message_steps=3).to(dev).train()
+elif PRESET == "colnorm":          # _BatchNorm / batch-less _LayerNorm in the four norm slots (tests/test_gpu_colnorm.py's captured step)
+    net = model.Architecture(pre_norm="_BatchNorm", graph_norm="_BatchNorm", flat_norm="_LayerNorm", end_norm="_BatchNorm", pre_act="ReLU",
+                             graph_act="ReLU", flat_act="ReLU", graph_do="_None()", end_do="_None()", mol_block="_TripletMessage").to(dev)
 else:
     net = model.Architecture(mol_block="_TripletMessage", message_steps=3, graph_do="_None()", end_do="_None()", pre_act="ReLU", graph_act="ReLU",
                              flat_act="ReLU").to(dev)
@@ -39,3 +43,18 @@ for i, (name, grid, us) in enumerate(kt.records()):
     tot += us
     print(f"{i:3d} {us:7.2f} us  grid {grid:6d}  {name}")
 print(f"{i + 1} launches, {tot:.1f} us of kernels")
+
+# the ATen normalisation / whole-tensor statistics ops the step still dispatches (none when every norm of the model is a library kernel)
+import collections
+from torch.utils._python_dispatch import TorchDispatchMode
+NORM_OPS = ("batch_norm", "layer_norm", "aten.mean", "aten.std", "aten.var", "miopen")
+seen = collections.Counter()
+class Log(TorchDispatchMode):
+    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+        if any(k in str(func) for k in NORM_OPS):
+            seen[str(func)] += 1
+        return func(*args, **(kwargs or {}))
+with Log():
+    body()
+torch.cuda.synchronize()
+print("ATen normalisation ops in the step:", dict(seen) if seen else "none")

@@ -157,14 +157,9 @@ class TripletMessage(MessagePassing):
         with ``a_i = x @ Wa[:, :4]``, ``a_j = x @ Wa[:, 4:]``."""
         H, C, De = self.heads, self.node_channels, self.edge_channels
         Cp, Dp = _ceil4(C), _pad_de(De)
-        att = self.weight_triplet_att[0]                                 # [H, 3C]
-        att_ij = torch.stack([att[:, :C], att[:, 2 * C:]], dim=-1)      # [H, C, 2]
         Wn = self.weight_node.view(C, H, C)
-        Wa = torch.bmm(Wn.permute(1, 0, 2), att_ij)                      # [H, Cin, 2]
-        Wa = F.pad(Wa.permute(1, 2, 0), (0, 4 - H)).reshape(C, 8)        # [Cin, (i|j) x 4]
         We = self.weight_edge.view(De, H, C)
-        M = torch.bmm(We.permute(1, 0, 2), att[:, C:2 * C].unsqueeze(-1)).squeeze(-1).t()   # [De, H]
-        M = F.pad(M, (0, 4 - H, 0, Dp - De))
+        Wa, M = self._attention_weights(0, H)
         if Cp != C or Dp != De:
             Wn = F.pad(Wn, (0, Cp - C))
             We = F.pad(We, (0, Cp - C, 0, 0, 0, Dp - De))
@@ -172,6 +167,20 @@ class TripletMessage(MessagePassing):
         else:
             Ws = self.weight_scale
         return Wn.reshape(C, H * Cp), Wa, We.reshape(Dp, H * Cp).contiguous(), M.contiguous(), Ws, Cp, Dp
+
+    def _attention_weights(self, h0, h1):
+        """``(Wa[Cin, 8], M[Dp, 4])`` of heads ``h0:h1`` (at most four): the separable attention weights of ``_staged_weights``, which
+        takes all of them at once; ``glam_amd.explain`` takes groups of four when ``heads > 4``."""
+        H, C, De = self.heads, self.node_channels, self.edge_channels
+        k = h1 - h0
+        att = self.weight_triplet_att[0, h0:h1]                          # [k, 3C]
+        att_ij = torch.stack([att[:, :C], att[:, 2 * C:]], dim=-1)      # [k, C, 2]
+        Wn = self.weight_node.view(C, H, C)[:, h0:h1]
+        Wa = torch.bmm(Wn.permute(1, 0, 2), att_ij)                      # [k, Cin, 2]
+        Wa = F.pad(Wa.permute(1, 2, 0), (0, 4 - k)).reshape(C, 8)        # [Cin, (i|j) x 4]
+        We = self.weight_edge.view(De, H, C)[:, h0:h1]
+        M = torch.bmm(We.permute(1, 0, 2), att[:, C:2 * C].unsqueeze(-1)).squeeze(-1).t()   # [De, k]
+        return Wa, F.pad(M, (0, 4 - k, 0, _pad_de(De) - De))
 
     def forward(self, x, edge_index, edge_attr, size=None):
         # layer.py:36-40 hands `x @ weight_node` and `edge_attr @ weight_edge` to propagate(); here the two products are part of
@@ -329,17 +338,22 @@ class TripletMessageLight(MessagePassing):
         alpha = softmax(F.leaky_relu(logit, self.negative_slope), edge_index_i, ptr=None, num_nodes=size_i)
         return alpha.unsqueeze(-1) * x_j
 
+    def _attention_weights(self):
+        """``(Wa[Cin, 8], M[Dp, 4])``: the separable attention weights (one head; ``logit = a_i[dst] + <edge_attr, M> + a_j[src]``)."""
+        C, De = self.node_channels, self.edge_channels
+        att = self.weight_triplet_att[0]
+        att_ij = torch.stack([att[:C], att[C + De:]], dim=-1)                           # [C, 2]
+        Wa = torch.matmul(self.weight_node, att_ij)                                     # [Cin, 2]
+        Wa = F.pad(Wa.unsqueeze(-1), (0, 3)).reshape(C, 8)
+        return Wa, F.pad(att[C:C + De].unsqueeze(-1), (0, 3, 0, _pad_de(De) - De)).contiguous()     # [Dp, 4]
+
     def _fused(self, x, edge_index, edge_attr):
         C, De = self.node_channels, self.edge_channels
         Cp, Dp = _ceil4(C), _pad_de(De)
         gi = ops.graph_index(edge_index, x.size(0))
 
         def derived():      # parameter-only staging, shared by the message_steps applications of the block (ops.weight_scope)
-            att = self.weight_triplet_att[0]
-            att_ij = torch.stack([att[:C], att[C + De:]], dim=-1)                       # [C, 2]
-            Wa = torch.matmul(self.weight_node, att_ij)                                 # [Cin, 2]
-            Wa = F.pad(Wa.unsqueeze(-1), (0, 3)).reshape(C, 8)
-            M = F.pad(att[C:C + De].unsqueeze(-1), (0, 3, 0, Dp - De)).contiguous()     # [Dp, 4]
+            Wa, M = self._attention_weights()
             Wn = F.pad(self.weight_node, (0, Cp - C)) if Cp != C else self.weight_node
             wt = torch.cat([Wn, Wa], dim=1)
             if Cp != C:

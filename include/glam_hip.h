@@ -979,6 +979,36 @@ int glam_layer_norm_flat_fwd(const float* x, const float* weight, const float* b
 int glam_layer_norm_flat_bwd(const float* x, const float* dy, const float* weight, const float* stat, int64_t N, int C, float eps, float* dx,
                              float* d_weight, float* d_bias, void* ws, size_t ws_bytes, int form, int max_blocks, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Attention export: the weights the fused kernels above never write (they keep only `stats`, the inference forward not even that).
+ * Inference only (no backward), no atomics, every reduction in a fixed order: two runs are bit-equal.  Each entry point returns 0
+ * without launching when N == 0, E == 0 or B == 0.
+ *
+ * glam_edge_attention: the alpha of src_1gp/layer.py:48-51 (TripletMessage) and :92-95 (TripletMessageLight), in the separable form and
+ * the arithmetic of glam_triplet_fwd:
+ *   logit[e,h] = leaky_relu(a_ij[dst,h] + sum_k edge_attr[e,k]*M[k,h] + a_ij[src,4+h], slope)
+ *   alpha      = segment softmax of logit over the incoming edges of dst (max-shifted, denominator + 1e-16)
+ * a_ij f32[N,8]; edge_attr f32[E,De] (De in {4,8}); M f32[De,4]; CSR by target (rowptr,src,eid); 1 <= H <= 4.
+ * Output alpha f32[E,4] in the CALLER's edge order (row eid[e]; one 16-byte store per edge, the layout of B1's alpha_e), columns
+ * H..3 written as zero.  A group of 8 lanes per target node, one edge per lane: a row of at most 8 edges (every molecular graph)
+ * is one pass over memory with its logits in registers; a longer row is strided by its group (max, exp-sum, write) and recomputes
+ * them — a hub's row is walked serially by its 8 lanes, which an export can afford.  In-degree 0 writes nothing. */
+int glam_edge_attention(const float* a_ij, const float* edge_attr, const float* M, const int32_t* rowptr, const int32_t* src,
+                        const int32_t* eid, int64_t N, int64_t E, int H, int De, float slope, float* alpha, void* stream);
+/* "Attention sent": sent f32[N,4], sent[n,h] = sum of alpha[e,h] over the edges that LEAVE n (how much the neighbours listen to atom
+ * n), over the CSR by source (colptr, eid_t of glam_csr_build(by = 1)) and summed in CSR order; columns H..3 are zero.  With E == 0
+ * nothing is launched and sent is left as the caller passed it (glam_amd.explain passes zeros). */
+int glam_edge_attention_sent(const float* alpha, const int32_t* colptr, const int32_t* eid_t, int64_t N, int64_t E, int H, float* sent,
+                             void* stream);
+/* Per-graph softmax weights w f32[N] over contiguous node segments ptr int32[B+1] (max-shifted, denominator + 1e-16).
+ *   gate != NULL: softmax of gate f32[N] — the weights of GlobalAttention behind GlobalLAPool (src_1gp/layer.py:206-220);
+ *   gate == NULL: the logits are <x_n, q_g>, formed in the kernel as in glam_s2s_attn_fwd — Set2Set's read (src_1gp/model.py:41);
+ *                 x rows are ld floats apart and hold D channels, q f32[B,ld]; ld % 4 == 0, ld <= 128, 1 <= D <= ld, else
+ *                 GLAM_E_UNSUPPORTED.
+ * A wave per graph; empty graphs write nothing. */
+int glam_segment_softmax(const float* gate, const float* x, const float* q, const int32_t* ptr, int64_t N, int64_t B, int D, int ld,
+                         float* w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

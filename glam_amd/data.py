@@ -19,6 +19,8 @@ available), so the path's *input layout* is restated here:
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 import torch
 
@@ -194,6 +196,125 @@ class PackedDataset:
         return out
 
 
+def resident_table(ids, ns, es, y_rows):
+    """The slot table of ``DeviceDataset.collate`` (host, O(B) numpy): ``(table, N, E, Y)`` with ``table`` int32 ``[4, B + 1]`` — row 0 the
+    graph ids (one entry of padding), rows 1-3 the exclusive offsets of the slots' nodes, edges and ``y`` rows, each closed by its
+    total.  ``ns`` / ``es`` / ``y_rows``: per-graph counts of the dataset.  ``IndexError`` for an id outside ``[0, len(ns))`` — before
+    anything is launched; the kernel trusts the table."""
+    ids = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids).reshape(-1)
+    if ids.size == 0:
+        ids = np.zeros(0, dtype=np.int64)
+    if ids.dtype.kind not in "iu":
+        raise IndexError(f"graph ids must be integers, got {ids.dtype}")
+    ids = ids.astype(np.int64)
+    n, B = int(ns.shape[0]), int(ids.size)
+    if B and (int(ids.min()) < 0 or int(ids.max()) >= n):
+        raise IndexError(f"graph ids must lie in [0, {n}): got {int(ids.min())} .. {int(ids.max())}")
+    table = np.zeros((4, B + 1), dtype=np.int64)
+    table[0, :B] = ids
+    for row, counts in zip(table[1:], (ns, es, y_rows)):
+        np.cumsum(counts[ids], out=row[1:])
+    if B and int(table[1:, B].max()) >= 2 ** 31 - 1:
+        from ._lib import GlamHipError
+        raise GlamHipError("DeviceDataset.collate: the batch's node / edge / y rows do not fit int32")
+    return table.astype(np.int32), int(table[1, B]), int(table[2, B]), int(table[3, B])
+
+
+class DeviceDataset:
+    """A dataset that LIVES ON THE DEVICE, graph index included, so that collating any set of graph ids is one kernel launch
+    (``glam_collate``, csrc/collate.hip) behind one small host-to-device copy — no per-field copies, no CSR / ELL builds, no read-back.
+
+    A batch is a disjoint union of graphs: its CSR by target and by source and its ELL records are the per-graph ones with two offsets
+    added.  So they are built ONCE, at construction, for the dataset taken as one big disjoint graph (``glam_csr_build`` both ways,
+    ``glam_ell_build`` on each; the two degree flags are read back here and never again), and a batch is a segmented copy.
+
+    On the device: the flat ``x``, graph-local ``ei`` (int32), ``ea``, ``y``; the node / edge / y prefix sums; both CSRs; both ELL pairs
+    (where no degree exceeds 4).  On the host: ``ns`` / ``es`` / ``y_rows`` (numpy), ``valid_ids`` / ``onehot`` as ``PackedDataset``
+    checks them, ``ell_ok`` / ``ell_t_ok``."""
+
+    def __init__(self, data, device):
+        from . import ops
+        packed = data if isinstance(data, PackedDataset) else PackedDataset(data)
+        self.device = device = torch.device(device)
+        if device.type != "cuda":
+            raise ops.GlamHipError(f"DeviceDataset lives on an MI355X HIP device (got {device}); the host path is PackedDataset")
+        self.n = packed.n
+        self.ns, self.es = packed.ns.numpy().copy(), packed.es.numpy().copy()
+        self.y_rows = np.zeros(self.n, dtype=np.int64) if packed.y is None else packed.y_rows.numpy().copy()
+        self.valid_ids, self.onehot = packed.valid_ids, packed.onehot
+        if not self.valid_ids:      # (the dataset-wide index is the per-graph ones side by side only if no edge leaves its graph)
+            raise IndexError("DeviceDataset: an edge_index holds node ids outside its own graph")
+        Nd, Ed, Yd = int(self.ns.sum()), int(self.es.sum()), int(self.y_rows.sum())
+        if max(Nd, Ed, Yd) >= 2 ** 31 - 1:
+            raise ops.GlamHipError(f"DeviceDataset: {Nd} nodes / {Ed} edges / {Yd} y rows do not fit int32")
+        self._row_bytes = []
+        for name, t in (("x", packed.x), ("edge_attr", packed.ea), ("y", packed.y)):
+            rb = 0 if t is None else int(np.prod(t.shape[1:], dtype=np.int64)) * t.element_size()
+            if rb % 4:
+                raise ops.GlamHipError(f"DeviceDataset: rows of {name} ({t.dtype} {tuple(t.shape[1:])}) are no multiple of 4 bytes")
+            self._row_bytes.append(rb)
+        i32 = lambda t: t.to(torch.int32).contiguous().to(device)       # noqa: E731
+        self.x = packed.x.contiguous().to(device)
+        self.ei = i32(packed.ei)
+        self.ea = None if packed.ea is None else packed.ea.contiguous().to(device)
+        self.y = None if packed.y is None else packed.y.contiguous().to(device)
+        self.node_ptr, self.edge_ptr = i32(packed.node_ptr), i32(packed.edge_ptr)
+        self.y_ptr = i32(torch.from_numpy(np.concatenate([[0], np.cumsum(self.y_rows)])))
+        # the dataset as ONE disjoint graph, through the builds every batch's index went through so far
+        ei_all = (packed.ei + torch.repeat_interleave(packed.node_ptr[:-1], packed.es, output_size=Ed).unsqueeze(0)).to(device)
+        gi = ops.GraphIndex(ei_all, Nd, validate=False)
+        self.rowptr, self.src, self.eid = gi.rowptr, gi.src, gi.eid
+        self.colptr, self.dst, self.eid_t = gi.transpose()
+        self.ell, self.ell_t = gi.ell(), gi.ell_t()             # (the one read-back of each degree flag)
+        self.ell_ok, self.ell_t_ok = self.ell is not None, self.ell_t is not None
+        fields = [self.x, self.ei, self.ea, self.y, self.node_ptr, self.edge_ptr, self.y_ptr, self.rowptr, self.src, self.eid,
+                  self.colptr, self.dst, self.eid_t, *(self.ell or (None, None)), *(self.ell_t or (None, None))]
+        self._ds = (ctypes.c_void_p * len(fields))(*[None if t is None else t.data_ptr() for t in fields])
+
+    def __len__(self):
+        return self.n
+
+    def collate(self, ids):
+        """The batch of the graphs ``ids`` (any host sequence, repeats allowed), field by field what
+        ``PackedDataset.collate(ids).to(device)`` gives, with its ``GraphIndex`` and ``SegmentPtr`` already installed in the caches of
+        ``ops.graph_index`` / ``ops.segment_ptr``: the model's first step on it builds nothing and reads nothing back."""
+        from . import _lib, ops
+        table, N, E, Y = resident_table(ids, self.ns, self.es, self.y_rows)
+        B = table.shape[1] - 1
+        dev = self.device
+        _lib.require_device(self.x)
+        # the one host-to-device copy of a batch, out of pinned memory so that it is only enqueued: the host does not wait for the step
+        # before (torch's host allocator hands the block out again once the copy has run)
+        staged = torch.empty(table.shape, dtype=torch.int32, pin_memory=True)
+        staged.numpy()[...] = table
+        tab = staged.to(dev, non_blocking=True)
+        new = lambda t, rows: None if t is None else torch.empty((rows,) + t.shape[1:], dtype=t.dtype, device=dev)   # noqa: E731
+        x, ea, y = new(self.x, N), new(self.ea, E), new(self.y, Y)
+        ei = torch.empty(2, E, dtype=torch.int64, device=dev)
+        batch, ptr = torch.empty(N, dtype=torch.int64, device=dev), torch.empty(B + 1, dtype=torch.int64, device=dev)
+        # the index tensors out of one allocation, every one on a 16-byte boundary
+        ell, ell_t = self.ell_ok and N > 0, self.ell_t_ok and N > 0
+        sizes = [B + 1, N + 1, E, E, N + 1, E, E] + [4 * N if ell else 0] * 2 + [4 * N if ell_t else 0] * 2
+        starts = np.concatenate([[0], np.cumsum([(s + 3) & ~3 for s in sizes])])
+        arena = torch.empty(int(starts[-1]), dtype=torch.int32, device=dev)
+        ptr32, rowptr, src, eid, colptr, dst, eid_t, *ells = [arena[a:a + s] for a, s in zip(starts[:-1].tolist(), sizes)]
+        ells = [t.view(N, 4) if t.numel() else None for t in ells]
+        out = [x, ei, ea, y, batch, ptr, ptr32, rowptr, src, eid, colptr, dst, eid_t, *ells]
+        out = (ctypes.c_void_p * len(out))(*[None if t is None else t.data_ptr() for t in out])
+        _lib.api().glam_collate(self._ds, out, _lib.ptr(tab), B, N, E, Y, int(self.ei.size(1)), *self._row_bytes, _lib.stream())
+        gi = ops.GraphIndex.from_parts(ei, N, rowptr, src, eid, (colptr, dst, eid_t), tuple(ells[:2]) if ell else None,
+                                       tuple(ells[2:]) if ell_t else None)
+        ops._GI_CACHE.put(ei, (N, gi))
+        ops._SP_CACHE.put(batch, ops.SegmentPtr.from_parts(ptr32, N, B))
+        b = Batch(x=x, edge_index=ei, edge_attr=ea, y=y, batch=batch)
+        b.num_graphs, b.ptr = B, ptr
+        b._glam_marks = {"edge_index": ("_glam_trusted", True), "batch": ("_glam_trusted", True)}
+        if self.onehot is not None:
+            b._glam_marks["edge_attr"] = ("_glam_onehot", self.onehot)
+        b._apply_marks()
+        return b
+
+
 class DataLoader:
     """Sequential mini-batch iterator over a list of ``Data`` (the reference's train
     loader does not shuffle: ``src_1gp/trainer.py:37-38``).
@@ -201,9 +322,13 @@ class DataLoader:
     ``device`` / ``cache``: without shuffling the batch composition repeats every epoch, so the collated batches
     can be built and moved to the device ONCE and handed out again as the same tensor objects.  The CSR staging of
     ``ops.graph_index`` is keyed on the ``edge_index`` object, so from the second epoch on a step does no
-    collation, no host-to-device copy, no CSR build and no validation sync."""
+    collation, no host-to-device copy, no CSR build and no validation sync.
 
-    def __init__(self, dataset, batch_size=32, shuffle=False, seed=0, device=None, cache=None):
+    ``resident=True`` (needs a ``device``): the dataset moves to the device once, index included (``DeviceDataset``), and every batch
+    — in the same order, from the same shuffle — is one launch behind one small copy, its graph index installed: what a loop that
+    shuffles, samples or walks a library larger than the cache pays per FRESH batch.  ``cache`` keeps its meaning."""
+
+    def __init__(self, dataset, batch_size=32, shuffle=False, seed=0, device=None, cache=None, resident=False):
         self.dataset, self.batch_size, self.shuffle, self.seed = list(dataset), batch_size, shuffle, seed
         self.device = device
         self.cache = (not shuffle) if cache is None else bool(cache)
@@ -212,11 +337,23 @@ class DataLoader:
         self._epoch = 0
         self._batches = None
         self._packed = None
+        self.resident, self._resident = bool(resident), None
+        if self.resident:
+            if device is None:
+                raise ValueError("DataLoader: resident=True keeps the dataset on a device: pass device=")
+            try:
+                self._packed = PackedDataset(self.dataset)
+            except (ValueError, AttributeError, RuntimeError) as e:
+                raise ValueError(f"DataLoader: resident=True needs records of one layout ({e})") from e
 
     def __len__(self):
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
 
     def _collate(self, idx):
+        if self.resident:
+            if self._resident is None:
+                self._resident = DeviceDataset(self._packed, self.device)
+            return self._resident.collate(idx)
         if self._packed is None:
             try:
                 self._packed = PackedDataset(self.dataset)

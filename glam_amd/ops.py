@@ -112,6 +112,21 @@ class GraphIndex:
         if validate and getattr(edge_index, "_glam_trusted", None) != edge_index._version:   # same failure class as torch's index_select on CPU
             _check_flag(self._err, f"edge_index holds node ids outside [0, {self.N})")
 
+    @classmethod
+    def from_parts(cls, edge_index, num_nodes, rowptr, src, eid, by_source, ell, ell_t):
+        """The index of ``edge_index`` from tensors that ALREADY hold it (``glam_amd.data.DeviceDataset.collate`` writes them in the
+        launch that writes ``edge_index``): nothing is launched, nothing is read back.  ``by_source = (colptr, dst, eid_t)``; ``ell`` /
+        ``ell_t``: the ``[N, 4]`` pair, or ``None`` for an edge list without that form — both arrive resolved, never ``False``."""
+        gi = cls.__new__(cls)
+        gi.N, gi.E, gi.device = int(num_nodes), int(edge_index.size(1)), edge_index.device
+        gi.rowptr, gi.src, gi.eid = rowptr, src, eid
+        gi._ei_ref = weakref.ref(edge_index)
+        gi._t = tuple(by_source)
+        gi._ell = None if ell is None else tuple(ell)
+        gi._ell_t = None if ell_t is None else tuple(ell_t)
+        gi._err = None             # (the flag of the builds: there are none left to run)
+        return gi
+
     # the pipelined forward pays off once xw + aggr (2 * N * H * Cp * 4 bytes) no longer fit the 256 MiB LLC (measured crossover:
     # B = 8 192 -> 0.59 general vs 0.55 pipelined; B = 16 384 -> 0.44-0.48 vs 0.56-0.64 of the HBM peak); ELL_MIN_NODES overrides
     ELL_MIN_NODES = -1          # (>= 0: a node count from which the ELL form is wanted regardless of the LLC)
@@ -454,6 +469,13 @@ class SegmentPtr:
         poll_checks()
         if validate and getattr(batch, "_glam_trusted", None) != batch._version:
             _check_flag(err, "batch must be non-decreasing with ids in [0, num_graphs)")
+
+    @classmethod
+    def from_parts(cls, ptr32, num_nodes, num_graphs):
+        """The segment pointer from an int32 ``ptr[B+1]`` that already exists (``DeviceDataset.collate``): no launch, no read-back."""
+        sp = cls.__new__(cls)
+        sp.N, sp.B, sp.ptr = int(num_nodes), int(num_graphs), ptr32
+        return sp
 
 
 _SP_CACHE = TensorMemo("id")      # batch vector -> SegmentPtr

@@ -1009,6 +1009,40 @@ int glam_edge_attention_sent(const float* alpha, const int32_t* colptr, const in
 int glam_segment_softmax(const float* gate, const float* x, const float* q, const int32_t* ptr, int64_t N, int64_t B, int D, int ld,
                          float* w, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A batch out of a device-resident dataset, its graph index included, in ONE launch.
+ * Replaces: PyG's Batch.from_data_list as the reference's DataLoader runs it for every training batch (src_1gp/trainer.py:37-41,
+ * :292-295: concatenate x / edge_attr / y, offset edge_index by the running node count, build batch and ptr) and, on this side, what
+ * a fresh batch costs after it: a host-to-device copy per field, glam_csr_build for both directions, glam_ell_build for both and
+ * glam_batch_ptr.  A batch is a disjoint union of graphs, so all of these are segmented copies of what was built ONCE for the dataset
+ * taken as one big disjoint graph (glam_csr_build by target and by source, glam_ell_build on each), with two offsets added: slot b
+ * holds graph g = ids[b]; node ids move by node_off[b] - node_ptr[g], edge ids and row pointers by edge_off[b] - edge_ptr[g]; the
+ * -1 of an empty ELL slot stays.  No workspace, no atomics, no flag to read back: the caller has checked the ids.
+ *
+ * ds_host / out_host: HOST arrays of GLAM_COLLATE_FIELDS device pointers, field by field the dataset's tensor and the batch's:
+ *    0 x          rows of x_row_bytes                        ->  x [N rows]
+ *    1 ei         int32 [2, Ed], graph-LOCAL node ids        ->  edge_index int64 [2, E], the batch's node ids
+ *    2 ea         rows of ea_row_bytes (0: none)             ->  edge_attr [E rows]
+ *    3 y          rows of y_row_bytes (0: none)              ->  y [Y rows]
+ *    4 node_ptr   int32 [G + 1]                              ->  batch int64 [N]
+ *    5 edge_ptr   int32 [G + 1]                              ->  ptr int64 [B + 1]
+ *    6 y_ptr      int32 [G + 1]                              ->  ptr int32 [B + 1]  (the readouts' segment pointer)
+ *    7..9   rowptr [Nd + 1], src [Ed], eid [Ed]   (by target) ->  rowptr int32 [N + 1] (rowptr[N] = E), src [E], eid [E]
+ *   10..12  colptr [Nd + 1], dst [Ed], eid_t [Ed] (by source) ->  colptr [N + 1], dst [E], eid_t [E]
+ *   13, 14  ell_src, ell_eid     int32 [Nd, 4]                ->  [N, 4], written when out_host[13] and [14] are given
+ *   15, 16  ell_dst, ell_eid_t   int32 [Nd, 4]                ->  [N, 4], written when out_host[15] and [16] are given
+ * Row sizes are multiples of 4 bytes; rows move as 16-byte units where they are whole units and both tensors start on one, as dwords
+ * otherwise (rows of 15 or 49 floats).  ELL tensors are 16-byte aligned, int64 tensors 8-byte aligned.
+ * table int32 [4, B + 1] (device): ids (B entries, one of padding), then the exclusive offsets of the slots' nodes, edges and y rows,
+ * each closed by its total (N, E, Y).  glam_collate_lds_slots(): the B up to which a block keeps the table in LDS; beyond it the
+ * kernel searches the table in global memory.
+ * GLAM_E_INVALID for null / misaligned pointers and sizes out of range (checked before any device work), GLAM_E_UNSUPPORTED for a
+ * field of 2^31 elements or more. */
+#define GLAM_COLLATE_FIELDS 17
+size_t glam_collate_lds_slots(void);
+int glam_collate(const void* const* ds_host, void* const* out_host, const int32_t* table, int64_t B, int64_t N, int64_t E,
+                 int64_t Y, int64_t Ed, int32_t x_row_bytes, int32_t ea_row_bytes, int32_t y_row_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

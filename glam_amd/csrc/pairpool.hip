@@ -5,6 +5,9 @@
 // are split over kPairSplit blocks (a batch of 32 pairs would otherwise light 32 of 256 CUs), whose (max, argmax, column
 // sum) partials a one-block-per-pair kernel combines in a fixed order.  The mean needs no pairwise work at all:
 // sum(S_i) = <sum_a mol_a, sum_b pro_b>; the two column sums are kept for the backward pass.
+// Screening (glam_pair_pool_indexed_fwd): pair i reads the protein segment pidx[i] of an encoding that holds every protein once —
+// the same kernels with kIndexed = true (the index read is block-uniform; dot products, tie rule and reduction order unchanged, so
+// the maximum is bit for bit that of the replicated call); forward only: no column sums are kept, the argmax is optional.
 #include "common.h"
 
 namespace glam {
@@ -20,14 +23,16 @@ __device__ __forceinline__ bool better(float v, int ix, float best, int bidx) { 
 // Split path (D % 4 == 0, D <= 64).  Block (i, s): residues s*64 + k*16*64 + lane of pair i; wave q takes the ligand rows
 // a = q (mod 4), two at a time (independent dot-product chains; each dot keeps the channel order of the scalar path, so
 // values and argmax are those of the one-block kernel).
+template <bool kIndexed>
 __global__ void __launch_bounds__(kBlock) k_pair_max_partial(const float* mol, const float* pro, const int* mptr,
-                                                            const int* pptr, int D, float* part) {
+                                                            const int* pptr, const int* pidx, int D, float* part) {
     __shared__ __attribute__((aligned(16))) float s_mol[kMolTile * 64];
     __shared__ float s_val[kBlock];
     __shared__ int s_idx[kBlock];
     const int i = blockIdx.x / kPairSplit, sp = blockIdx.x % kPairSplit, tid = threadIdx.x;
     const int lane = tid & 63, q = tid >> 6;
-    const int m0 = mptr[i], m1 = mptr[i + 1], p0 = pptr[i], p1 = pptr[i + 1];
+    const int j = kIndexed ? pidx[i] : i;      // the pair's protein segment
+    const int m0 = mptr[i], m1 = mptr[i + 1], p0 = pptr[j], p1 = pptr[j + 1];
     const int nm = m1 - m0, np = p1 - p0;
     float best = -INFINITY;
     int bidx = 0x7fffffff;
@@ -88,10 +93,12 @@ __global__ void __launch_bounds__(kBlock) k_pair_max_partial(const float* mol, c
     }
 }
 
-__global__ void __launch_bounds__(64) k_pair_finish(const float* mol, const int* mptr, const int* pptr, const float* part,
-                                                   int D, float* out, int* arg, float* sums) {
+template <bool kIndexed>
+__global__ void __launch_bounds__(64) k_pair_finish(const float* mol, const int* mptr, const int* pptr, const int* pidx,
+                                                   const float* part, int D, float* out, int* arg, float* sums) {
     const int i = blockIdx.x, c = threadIdx.x;
-    const int m0 = mptr[i], m1 = mptr[i + 1], p0 = pptr[i], np = pptr[i + 1] - p0, nm = m1 - m0;
+    const int j = kIndexed ? pidx[i] : i;
+    const int m0 = mptr[i], m1 = mptr[i + 1], p0 = pptr[j], np = pptr[j + 1] - p0, nm = m1 - m0;
     const float* pp = part + (size_t)i * kPairSplit * kPartStride;
     float ps = 0.f, ms = 0.f;
     if (c < D) {
@@ -103,8 +110,10 @@ __global__ void __launch_bounds__(64) k_pair_finish(const float* mol, const int*
             ms += v0; ms += v1; ms += v2; ms += v3;
         }
         for (; a < m1; ++a) ms += mol[(size_t)a * D + c];
-        sums[(size_t)i * 2 * D + c] = ms;
-        sums[(size_t)i * 2 * D + D + c] = ps;
+        if (!kIndexed) {
+            sums[(size_t)i * 2 * D + c] = ms;
+            sums[(size_t)i * 2 * D + D + c] = ps;
+        }
     }
     const float tot = group_sum<64>(ms * ps);
     if (c == 0) {
@@ -118,8 +127,10 @@ __global__ void __launch_bounds__(64) k_pair_finish(const float* mol, const int*
         const bool empty = nm <= 0 || np <= 0;
         out[2 * i] = empty ? 0.f : best;
         out[2 * i + 1] = empty ? 0.f : tot / ((float)nm * (float)np);
-        arg[2 * i] = empty ? -1 : m0 + bidx / np;
-        arg[2 * i + 1] = empty ? -1 : p0 + bidx % np;
+        if (!kIndexed || arg) {
+            arg[2 * i] = empty ? -1 : m0 + bidx / np;
+            arg[2 * i + 1] = empty ? -1 : p0 + bidx % np;
+        }
     }
 }
 
@@ -162,15 +173,17 @@ __global__ void __launch_bounds__(kBlock) k_pair_pool_bwd_split(const float* mol
         }
 }
 
+template <bool kIndexed>
 __global__ void __launch_bounds__(kBlock) k_pair_pool_fwd(const float* mol, const float* pro, const int* mptr,
-                                                         const int* pptr, int D, float* out, int* arg) {
+                                                         const int* pptr, const int* pidx, int D, float* out, int* arg) {
     __shared__ __attribute__((aligned(16))) float s_mol[kMolTile * kMaxD];
     __shared__ float s_val[kBlock];
     __shared__ int s_idx[kBlock];
     __shared__ float s_sum[2 * kMaxD];
     __shared__ __attribute__((aligned(16))) float s_part[16 * 16 * 4];
     const int i = blockIdx.x, tid = threadIdx.x;
-    const int m0 = mptr[i], m1 = mptr[i + 1], p0 = pptr[i], p1 = pptr[i + 1];
+    const int j = kIndexed ? pidx[i] : i;
+    const int m0 = mptr[i], m1 = mptr[i + 1], p0 = pptr[j], p1 = pptr[j + 1];
     const int nm = m1 - m0, np = p1 - p0;
     // column sums of both segments (mean)
     block_colsum(mol, m0, m1, D, s_part, s_sum);
@@ -230,8 +243,10 @@ __global__ void __launch_bounds__(kBlock) k_pair_pool_fwd(const float* mol, cons
         const bool empty = nm <= 0 || np <= 0;
         out[2 * i] = empty ? 0.f : s_val[0];
         out[2 * i + 1] = empty ? 0.f : tot / ((float)nm * (float)np);
-        arg[2 * i] = empty ? -1 : m0 + s_idx[0] / np;
-        arg[2 * i + 1] = empty ? -1 : p0 + s_idx[0] % np;
+        if (!kIndexed || arg) {
+            arg[2 * i] = empty ? -1 : m0 + s_idx[0] / np;
+            arg[2 * i + 1] = empty ? -1 : p0 + s_idx[0] % np;
+        }
     }
 }
 
@@ -503,15 +518,41 @@ extern "C" int glam_pair_pool_fwd(const float* mol, const float* pro, const int3
     GLAM_REQUIRE(mol && pro && mol_ptr && pro_ptr && out && argmax && sums, "glam_pair_pool_fwd: null pointer");
     if (pair_split(D)) {
         GLAM_REQUIRE(ws && ws_bytes >= glam_pair_pool_workspace_bytes(P, D), "glam_pair_pool_fwd: workspace too small");
-        hipLaunchKernelGGL(k_pair_max_partial, dim3((int)P * kPairSplit), dim3(kBlock), 0, (hipStream_t)stream, mol, pro, mol_ptr,
-                           pro_ptr, D, (float*)ws);
-        hipLaunchKernelGGL(k_pair_finish, dim3((int)P), dim3(64), 0, (hipStream_t)stream, mol, mol_ptr, pro_ptr, (const float*)ws, D,
-                           out, argmax, sums);
+        hipLaunchKernelGGL(k_pair_max_partial<false>, dim3((int)P * kPairSplit), dim3(kBlock), 0, (hipStream_t)stream, mol, pro, mol_ptr,
+                           pro_ptr, (const int*)nullptr, D, (float*)ws);
+        hipLaunchKernelGGL(k_pair_finish<false>, dim3((int)P), dim3(64), 0, (hipStream_t)stream, mol, mol_ptr, pro_ptr,
+                           (const int*)nullptr, (const float*)ws, D, out, argmax, sums);
     } else {
-        hipLaunchKernelGGL(k_pair_pool_fwd, dim3((int)P), dim3(kBlock), 0, (hipStream_t)stream, mol, pro, mol_ptr, pro_ptr, D, out,
-                           argmax);
+        hipLaunchKernelGGL(k_pair_pool_fwd<false>, dim3((int)P), dim3(kBlock), 0, (hipStream_t)stream, mol, pro, mol_ptr, pro_ptr,
+                           (const int*)nullptr, D, out, argmax);
     }
     GLAM_LAUNCH_CHECK("glam_pair_pool_fwd");
+    return GLAM_OK;
+}
+
+// Screening: pair i against the protein segment pro_of_pair[i] of Q segments (each protein held once).  pro_of_pair is validated by
+// the host (every entry in [0, Q)) and trusted here.  Forward only; argmax may be NULL.
+extern "C" int glam_pair_pool_indexed_fwd(const float* mol, const float* pro, const int32_t* mol_ptr, const int32_t* pro_ptr,
+                                          const int32_t* pro_of_pair, int64_t P, int64_t Q, int D, float* out, int32_t* argmax,
+                                          void* ws, size_t ws_bytes, void* stream) {
+    GLAM_REQUIRE(P >= 0 && P < INT32_MAX / kPairSplit, "glam_pair_pool_indexed_fwd: P out of range");
+    GLAM_REQUIRE(Q >= 0 && Q < INT32_MAX, "glam_pair_pool_indexed_fwd: Q out of range");
+    if (D <= 0 || D > kMaxD) return fail(GLAM_E_UNSUPPORTED, "glam_pair_pool_indexed_fwd: D=%d not in 1..%d", D, kMaxD);
+    if (P == 0) return GLAM_OK;
+    GLAM_REQUIRE(Q > 0, "glam_pair_pool_indexed_fwd: pairs but no protein segment");
+    GLAM_REQUIRE(mol && pro && mol_ptr && pro_ptr && pro_of_pair && out, "glam_pair_pool_indexed_fwd: null pointer");
+    if (pair_split(D)) {
+        GLAM_REQUIRE(aligned16(mol) && aligned16(pro), "glam_pair_pool_indexed_fwd: rows must be 16-byte aligned");
+        GLAM_REQUIRE(ws && ws_bytes >= glam_pair_pool_workspace_bytes(P, D), "glam_pair_pool_indexed_fwd: workspace too small");
+        hipLaunchKernelGGL(k_pair_max_partial<true>, dim3((int)P * kPairSplit), dim3(kBlock), 0, (hipStream_t)stream, mol, pro, mol_ptr,
+                           pro_ptr, pro_of_pair, D, (float*)ws);
+        hipLaunchKernelGGL(k_pair_finish<true>, dim3((int)P), dim3(64), 0, (hipStream_t)stream, mol, mol_ptr, pro_ptr, pro_of_pair,
+                           (const float*)ws, D, out, argmax, (float*)nullptr);
+    } else {
+        hipLaunchKernelGGL(k_pair_pool_fwd<true>, dim3((int)P), dim3(kBlock), 0, (hipStream_t)stream, mol, pro, mol_ptr, pro_ptr,
+                           pro_of_pair, D, out, argmax);
+    }
+    GLAM_LAUNCH_CHECK("glam_pair_pool_indexed_fwd");
     return GLAM_OK;
 }
 

@@ -1174,3 +1174,10 @@ def dot_and_global_pool2(mol_out, pro_out, mol_batch, pro_batch, with_identity=F
     msp = ops.segment_ptr(mol_batch)
     psp = ops.segment_ptr(pro_batch, msp.B)
     return ops.pair_pool(mol_out, pro_out, msp, psp, with_identity)
+
+
+def dot_and_global_pool2_indexed(mol_out, pro_out, mol_batch, pro_sp, pro_of_pair=None, return_argmax=False):
+    """``dot_and_global_pool2`` against proteins that are held ONCE: pair i is ligand i of ``mol_batch`` and the protein segment
+    ``pro_of_pair[i]`` of ``pro_sp`` (the ``SegmentPtr`` of the encoded proteins; ``ops.pair_index`` for the index).  Inference only;
+    widths are handled as there: the rows flow as they are."""
+    return ops.pair_pool_indexed(mol_out, pro_out, ops.segment_ptr(mol_batch), pro_sp, pro_of_pair, return_argmax)

@@ -8,13 +8,17 @@ sub-module names (checkpoint keys ``mol_lin0.*``, ``mol_conv.*``, ``mol_readout.
 """
 from __future__ import annotations
 
+import weakref
+
 import torch
 
 from . import graphs, ops
+from ._lib import GlamHipError
 
 from .layer import _None  # noqa: F401
 from .layer import GlobalPool5, GlobalLAPool, Set2Set  # noqa: F401  (resolved from config strings)
 from .layer import LinearBlock, MessageBlock, dot_and_global_pool2, first_node_spec, flat_then_head, following_dropout, prestage_pass
+from .layer import _BatchNorm, _LayerNorm, _PairNorm, dot_and_global_pool2_indexed
 
 
 def model_args(args):
@@ -78,6 +82,16 @@ class Architecture(torch.nn.Module):
 Model = Architecture
 
 
+class ProteinEncoding:
+    """What ``ArchitectureDTI.encode_proteins`` keeps of ``Q`` protein graphs for ``screen``: ``rows[s]`` the residue rows after
+    message step ``s`` (contiguous, as the fusion reads them), ``sp`` their ``SegmentPtr``, ``flat`` = ``pro_flat(pro_readout(.))``
+    ``[Q, hid]``, ``num_graphs`` = Q, and the stamp of the protein-side parameters it was computed from (``model`` is a weak reference)."""
+
+    def __init__(self, model, rows, sp, flat, stamp):
+        self.model, self.rows, self.sp, self.flat, self.stamp = weakref.ref(model), rows, sp, flat, stamp
+        self.num_graphs = sp.B
+
+
 class ArchitectureDTI(torch.nn.Module):
     """Ligand + protein two-tower model with per-pair fusion (src_2gi_dti_scr/model.py:14-68)."""
 
@@ -133,6 +147,88 @@ class ArchitectureDTI(torch.nn.Module):
         outp = self.pro_flat(self.pro_readout(xp, data_pro.batch, np_))
         out = ops.cat_cols([outm, outp] + fusion)      # (model.py:74-75; contiguous gradients for every piece from one launch)
         return self.lin_out1(self.lin_out0(out))
+
+    # ---- screening: a protein is encoded once, ligand batches stream against it ---------------------------------------------
+    # The reference's screening set scores a whole library against ONE protein (src_2gi_dti_scr/dataset.py:297-318) and still
+    # collates — and runs the protein tower on — one copy of it per pair.  Until the fusion nothing in the protein tower depends
+    # on the ligand, and in eval mode nothing in it depends on the other graphs of the batch, with the exceptions refused below:
+    #   slot given ``batch`` (pro_lin0 / pro_conv):  _None, _BatchNorm (running statistics: per row), _LayerNorm and _PairNorm
+    #       (per graph) are fine; _GraphSizeNorm DROPS ``batch`` (layer.py:193-194) and scales by the batch's total row count.
+    #   pro_flat's slot (no ``batch``):  _None and _BatchNorm are per row; _LayerNorm, _PairNorm and _GraphSizeNorm there take
+    #       statistics (or the row count) over the whole [B, .] matrix: how often each protein is repeated changes them.
+    def _protein_modules(self):
+        return self.pro_lin0, self.pro_conv, self.pro_readout, self.pro_flat
+
+    def _protein_stamp(self):
+        """Changes whenever a protein-side parameter or buffer is written (version counters; storage addresses for ``.data`` swaps and
+        ``.to()``; ``ops.PARAM_EPOCH`` for the optimizers that write through raw pointers)."""
+        ts = [t for m in self._protein_modules() for t in list(m.parameters()) + list(m.buffers())]
+        return ops.PARAM_EPOCH, sum(t._version for t in ts), tuple(t.data_ptr() for t in ts)
+
+    def _screen_guard(self, what):
+        if self.training:
+            raise GlamHipError(f"{what}: the model is in training mode — Dropout / RReLU noise is drawn per protein copy and BatchNorm takes "
+                               "statistics over the replicated rows, so one encoding cannot stand for the copies: call model.eval()")
+        if torch.is_grad_enabled():
+            raise GlamHipError(f"{what} is inference only (the indexed fusion has no backward): call it under torch.no_grad(); "
+                               "training runs model(data_mol, data_pro) on one protein graph per pair")
+        for name, block, ok in (("pro_lin0", self.pro_lin0, (_None, _BatchNorm, _LayerNorm, _PairNorm)),
+                                ("pro_conv", self.pro_conv, (_None, _BatchNorm, _LayerNorm, _PairNorm)),
+                                ("pro_flat", self.pro_flat, (_None, _BatchNorm))):
+            if type(block.norm) not in ok:
+                raise GlamHipError(f"{what}: {name}'s norm {type(block.norm).__name__} is not per graph or per row here — it normalises over "
+                                   "the whole batch (rows of every copy of every protein), so its result depends on how often each protein "
+                                   "is repeated and one encoding cannot reproduce model(data_mol, data_pro)")
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise GlamHipError(f"{what} runs eagerly (a library walk never repeats a batch): not inside a hipGraph capture")
+
+    def encode_proteins(self, data_pro):
+        """The protein tower, once, over the ``Q`` graphs of ``data_pro`` -> ``ProteinEncoding`` for ``screen``.  ``eval()`` mode under
+        ``torch.no_grad()``; valid until a protein-side parameter or buffer changes."""
+        self._screen_guard("encode_proteins")
+        with ops.weight_scope():
+            prestage_pass((self.pro_lin0, self.pro_conv, data_pro.x, data_pro.edge_attr))
+            xp = self.pro_lin0(data_pro.x, batch=data_pro.batch)
+            hp, rows = None, []
+            for _ in range(self.message_steps):
+                xp, hp = self.pro_conv(xp, data_pro.edge_index, data_pro.edge_attr, h=hp, batch=data_pro.batch)
+                rows.append(xp.contiguous())          # (odd widths flow as [N, C] views of padded rows: compacted here, once)
+            nq = getattr(data_pro, "num_graphs", None) or None
+            sp = ops.segment_ptr(data_pro.batch, nq)
+            flat = self.pro_flat(self.pro_readout(xp, data_pro.batch, nq))
+        return ProteinEncoding(self, rows, sp, flat, self._protein_stamp())
+
+    def screen(self, data_mol, enc, pro_of_pair=None, return_argmax=False):
+        """``model(data_mol, B_pro)`` -> ``[P, out_dim]`` for ``B_pro`` = the proteins ``pro_of_pair`` of ``enc`` collated one per ligand,
+        without building ``B_pro`` or running the protein tower: the ligand tower runs on ``data_mol``, every step's fusion reads the
+        encoded residue rows of that step through the pair -> protein index (``ops.pair_pool_indexed``), ``enc.flat`` is gathered by it.
+        ``pro_of_pair``: host integers, one per ligand (``ops.pair_index``); ``None`` when ``enc`` holds one protein.
+        ``return_argmax``: also the per-step ``[P, 2]`` int32 contacts (row of ``data_mol.x``, row of the encoded proteins)."""
+        self._screen_guard("screen")
+        if not isinstance(enc, ProteinEncoding) or enc.model() is not self:
+            raise GlamHipError("screen: the encoding was made by another model (its residue rows are that model's): encode_proteins() on this one")
+        if enc.stamp != self._protein_stamp() or len(enc.rows) != self.message_steps:
+            raise GlamHipError("screen: the encoding is stale — a protein-side parameter or buffer (pro_lin0 / pro_conv / pro_readout / "
+                               "pro_flat) was written since encode_proteins(): encode again")
+        nm = getattr(data_mol, "num_graphs", None) or None
+        msp = ops.segment_ptr(data_mol.batch, nm)
+        index = ops.pair_index(pro_of_pair, msp.B, enc.num_graphs, default="single")       # host-side, before the first launch
+        with ops.weight_scope():
+            prestage_pass((self.mol_lin0, self.mol_conv, data_mol.x, data_mol.edge_attr))
+            xm = self.mol_lin0(data_mol.x, batch=data_mol.batch)
+            hm, fusion, contacts = None, [], []
+            for i in range(self.message_steps):
+                with ops.block_feeds_itself(i + 1 < self.message_steps):
+                    xm, hm = self.mol_conv(xm, data_mol.edge_index, data_mol.edge_attr, h=hm, batch=data_mol.batch)
+                f = dot_and_global_pool2_indexed(xm, enc.rows[i], data_mol.batch, enc.sp, index, return_argmax)
+                if return_argmax:
+                    f, a = f
+                    contacts.append(a)
+                fusion.append(f)
+            outm = self.mol_flat(self.mol_readout(xm, data_mol.batch, nm))
+            outp = enc.flat.index_select(0, index.on(enc.flat.device))
+            out = self.lin_out1(self.lin_out0(ops.cat_cols([outm, outp] + fusion)))
+        return (out, contacts) if return_argmax else out
 
 
 class ArchitectureDDI(torch.nn.Module):

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -617,3 +618,84 @@ def pair_pool5(mol_out, pro_out, msp, psp):
     """``[max, mean, median, min, std]`` of ``mol[seg_i] @ pro[seg_i].T`` per pair -> ``[P, 5]`` (dot_and_global_pool5);
     widths that are multiples of 4 up to 128 (``pad_cols`` the operands first: zero columns do not change a score)."""
     return _PairPool5.apply(mol_out, pro_out, msp, psp)
+
+
+# --------------------------------------------------------------------------------------
+# screening: the fusion against proteins that are held once (csrc/pairpool.hip, glam_pair_pool_indexed_fwd)
+# --------------------------------------------------------------------------------------
+class PairIndex:
+    """A validated pair -> protein index: ``host`` int32 ``[P]`` (numpy) with every entry in ``[0, Q)``.  ``on(device)`` is its device
+    copy, made once per device (out of pinned memory, only enqueued) and shared by every launch that reads it."""
+
+    def __init__(self, host, Q):
+        self.host, self.P, self.Q = host, int(host.shape[0]), int(Q)
+        self._dev = {}
+
+    def on(self, device):
+        device = torch.device(device)
+        t = self._dev.get(device)
+        if t is None:
+            staged = torch.empty(max(self.P, 1), dtype=torch.int32, pin_memory=True)
+            staged.numpy()[:self.P] = self.host
+            t = self._dev[device] = staged.to(device, non_blocking=True)[:self.P]
+        return t
+
+
+def pair_index(pro_of_pair, P, Q, default="identity"):
+    """``PairIndex`` of ``pro_of_pair`` for ``P`` pairs over ``Q`` proteins — host only, before anything is launched (the kernel trusts
+    the index; the policy of ``data.resident_table``).  A host sequence, numpy array or CPU tensor of integers of length ``P``;
+    ``IndexError`` for a wrong length or an entry outside ``[0, Q)``; a device tensor is refused (validating it would be a hidden
+    read-back).  ``None``: ``default="identity"`` pairs ligand i with protein i (needs ``Q == P``), ``default="single"`` pairs every
+    ligand with the one protein (needs ``Q == 1``)."""
+    P, Q = int(P), int(Q)
+    if isinstance(pro_of_pair, PairIndex):
+        if pro_of_pair.P != P or pro_of_pair.Q != Q:
+            raise IndexError(f"pro_of_pair was validated for {pro_of_pair.P} pairs over {pro_of_pair.Q} proteins, not {P} over {Q}")
+        return pro_of_pair
+    if pro_of_pair is None:
+        if default == "identity":
+            if Q != P:
+                raise IndexError(f"pro_of_pair=None pairs ligand i with protein i: {P} ligands but {Q} proteins")
+            return PairIndex(np.arange(P, dtype=np.int32), Q)
+        if Q != 1:
+            raise IndexError(f"pro_of_pair=None screens against the one encoded protein, but the encoding holds {Q}: pass the index")
+        return PairIndex(np.zeros(P, dtype=np.int32), Q)
+    if torch.is_tensor(pro_of_pair):
+        if pro_of_pair.device.type != "cpu":
+            raise GlamHipError("pro_of_pair lives on a device: it is validated on the host before the launch, which would be a hidden "
+                               "read-back — pass the host sequence / numpy array / CPU tensor it was made from")
+        pro_of_pair = pro_of_pair.detach().numpy()
+    idx = np.asarray(pro_of_pair)
+    if idx.size == 0:
+        idx = np.zeros(0, dtype=np.int64)
+    if idx.dtype.kind not in "iu":
+        raise IndexError(f"pro_of_pair must hold integers, got {idx.dtype}")
+    if idx.ndim != 1 or idx.shape[0] != P:
+        raise IndexError(f"pro_of_pair must have one entry per pair: shape {tuple(idx.shape)} for {P} pairs")
+    if P and (int(idx.min()) < 0 or int(idx.max()) >= Q):
+        raise IndexError(f"pro_of_pair must lie in [0, {Q}): got {int(idx.min())} .. {int(idx.max())}")
+    return PairIndex(idx.astype(np.int32), Q)
+
+
+def pair_pool_indexed(mol_out, pro_out, msp, psp, pro_of_pair=None, return_argmax=False):
+    """``[max, mean]`` of ``mol[seg_i] @ pro[seg_q].T`` with ``q = pro_of_pair[i]`` -> ``[P, 2]``: ``pair_pool`` against proteins that are
+    held once (``psp.B`` segments) instead of once per pair.  The max column — and with ``return_argmax`` the ``[P, 2]`` int32 rows of
+    the maximum in ``mol_out`` / ``pro_out`` (-1 for an empty pair) — is bit for bit that of ``pair_pool`` on replicated residue rows.
+    ``pro_of_pair``: see ``pair_index`` (``None`` = identity).  Inference only: there is no backward (training is ``ops.pair_pool``)."""
+    P, Q = msp.B, psp.B
+    index = pair_index(pro_of_pair, P, Q)
+    if torch.is_grad_enabled() and (mol_out.requires_grad or pro_out.requires_grad):
+        raise GlamHipError("pair_pool_indexed is inference only (no backward): call it under torch.no_grad(); the training route is "
+                           "ops.pair_pool on one protein graph per pair")
+    require_device(mol_out, pro_out)
+    mol, pro = f32c(mol_out, "mol_out"), f32c(pro_out, "pro_out")
+    if mol.size(1) != pro.size(1) or mol.size(0) != msp.N or pro.size(0) != psp.N:
+        raise GlamHipError("pair_pool_indexed: the two batches disagree (width / node count)")
+    D = mol.size(1)
+    out = torch.empty(P, 2, dtype=torch.float32, device=mol.device)
+    arg = torch.empty(P, 2, dtype=torch.int32, device=mol.device) if return_argmax else None
+    lib = _lib.api()
+    ws = torch.empty(max(lib.glam_pair_pool_workspace_bytes(P, D), 16), dtype=torch.uint8, device=mol.device)
+    lib.glam_pair_pool_indexed_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(index.on(mol.device)), P, Q, D, ptr(out), ptr(arg),
+                                   ptr(ws), ws.numel(), stream())
+    return (out, arg) if return_argmax else out

@@ -579,6 +579,14 @@ int glam_pair_pool_bwd_add(const float* mol, const float* pro, const int32_t* mo
                            const float* sums, const float* d_out, int64_t P, int D, const float* add_mol, const float* add_pro,
                            float* d_mol, float* d_pro, void* stream);
 
+/* Screening (inference): the same fusion with every protein held ONCE — pair i takes ligand rows mol_ptr[i]..mol_ptr[i+1] and the
+ * residue rows of segment q = pro_of_pair[i] (int32[P], every entry in [0, Q): checked by the caller, trusted here; pro_ptr int32[Q+1]).
+ * out f32[P,2] as above; the max (and argmax: row of mol, row of pro; may be NULL) is bit for bit that of glam_pair_pool_fwd on
+ * physically replicated residue rows.  Forward only.  Workspace: glam_pair_pool_workspace_bytes(P, D). */
+int glam_pair_pool_indexed_fwd(const float* mol, const float* pro, const int32_t* mol_ptr, const int32_t* pro_ptr,
+                               const int32_t* pro_of_pair, int64_t P, int64_t Q, int D, float* out, int32_t* argmax,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* Training-mode block tails of the reference's DEFAULT configuration (src_1gp/model.py:30-31, run.py:35-37: RReLU activations,
  * Dropout(0.2) in front of every conv) — the same launches as glam_gru_tail_* / glam_bias_res_act_* with two additions:
  *   act = 4: torch.nn.RReLU in training mode, out = y > 0 ? y : a * y with a ~ U(rr_lower, rr_upper) per element;

@@ -155,6 +155,148 @@ __global__ void __launch_bounds__(kBlock) k_collate(const CollateArgs a) {
     }
 }
 
+// ---- fixed-capacity batches (glam_collate_padded) ---------------------------------------------------------------------------------
+// The same segmented copy into tensors whose sizes do not depend on the ids: B real graphs, then ONE phantom graph that owns the
+// surplus P = N_cap - N nodes and E_pad = E_cap - E edges.  N and E are read from the table on the device, so grid, sizes and pointers
+// are those of the bucket and the launch can sit in a captured graph.  Phantom node p = N + p carries a contiguous run of self-loops,
+// q + (p < rem) of them from E + p * q + min(p, rem) on (q = E_pad / P, rem = E_pad % P): both CSR orders of the padded edge list are
+// then the real ones followed by the runs, an edge's id its own position.  Phantom x rows are zero, phantom edge_attr rows copies of
+// the dataset's edge row 0 (it carries whatever one-hot mark the dataset has), so every phantom activation is finite.
+struct CollatePadArgs {
+    CollateArgs c;              // (c.N / c.E / c.Y are not read: the totals come from the table)
+    int N_cap, E_cap;
+    int xwo;                    // units per OUTPUT row of x (>= c.xw; the pad units are written as zero)
+};
+
+// phantom node (0-based) that owns phantom edge j, for runs of q + (p < rem) edges
+__device__ __forceinline__ int phantom_owner(int j, int q, int rem) {
+    const int head = rem * (q + 1);
+    return j < head ? j / (q + 1) : rem + (j - head) / q;      // (j >= head only where q >= 1: j < E_pad = head + (P - rem) * q)
+}
+
+template <bool LDS>
+__global__ void __launch_bounds__(kBlock) k_collate_padded(const CollatePadArgs pa) {
+    constexpr int kRow = kCollateSlots + 1;
+    __shared__ int s_tab[LDS ? 6 * kRow : 1];
+    const CollateArgs& a = pa.c;
+    SlotTable<LDS> tn, te, ty;
+    const int B = a.B;
+    if constexpr (LDS) {
+        for (int i = threadIdx.x; i <= B; i += kBlock) {
+            s_tab[i] = a.node_off[i];
+            s_tab[kRow + i] = a.edge_off[i];
+            s_tab[2 * kRow + i] = a.y_off[i];
+            if (i < B) {
+                const int g = a.ids[i];
+                s_tab[3 * kRow + i] = a.node_ptr[g];
+                s_tab[4 * kRow + i] = a.edge_ptr[g];
+                s_tab[5 * kRow + i] = a.y_ptr[g];
+            }
+        }
+        __syncthreads();
+        tn = {s_tab, s_tab + 3 * kRow, nullptr};
+        te = {s_tab + kRow, s_tab + 4 * kRow, nullptr};
+        ty = {s_tab + 2 * kRow, s_tab + 5 * kRow, nullptr};
+    } else {
+        tn = {a.node_off, a.node_ptr, a.ids};
+        te = {a.edge_off, a.edge_ptr, a.ids};
+        ty = {a.y_off, a.y_ptr, a.ids};
+    }
+    const int N = tn.off[B], E = te.off[B], Y = ty.off[B];
+    const int P = pa.N_cap - N, E_pad = pa.E_cap - E;            // (the caller guarantees P >= 1, E_pad >= 0)
+    const int q = P > 0 ? E_pad / P : 0, rem = P > 0 ? E_pad % P : 0;
+    for (int item = blockIdx.x; item < a.first[6]; item += gridDim.x) {
+        int s = 0;
+        while (item >= a.first[s + 1]) ++s;                  // (block-uniform)
+        const int base = (item - a.first[s]) * kCollateItem + threadIdx.x;
+#pragma unroll
+        for (int k = 0; k < kCollateItem / kBlock; ++k) {
+            const int idx = base + k * kBlock;
+            if (s == 0) {                                    // x: real rows, zero pad units, zero phantom rows
+                if (idx >= pa.N_cap * pa.xwo) break;
+                const int r = idx / pa.xwo, c = idx - r * pa.xwo;
+                const bool real = r < N && c < a.xw;
+                int64_t from = 0;
+                if (real) {
+                    const int b = find_slot(tn.off, B, r);
+                    from = ((int64_t)(r - tn.off[b]) + tn.first_of(b)) * a.xw + c;
+                }
+                if (a.xvec) reinterpret_cast<uint4*>(a.ox)[idx] = real ? reinterpret_cast<const uint4*>(a.x)[from] : make_uint4(0, 0, 0, 0);
+                else a.ox[idx] = real ? a.x[from] : 0u;
+            } else if (s == 1) {                             // edge_attr: real rows, then copies of the dataset's row 0
+                if (idx >= pa.E_cap * a.eaw) break;
+                const int r = idx / a.eaw, c = idx - r * a.eaw;
+                int64_t from = c;
+                if (r < E) {
+                    const int b = find_slot(te.off, B, r);
+                    from = ((int64_t)(r - te.off[b]) + te.first_of(b)) * a.eaw + c;
+                }
+                if (a.eavec) reinterpret_cast<uint4*>(a.oea)[idx] = reinterpret_cast<const uint4*>(a.ea)[from];
+                else a.oea[idx] = a.ea[from];
+            } else if (s == 2) {                             // y: the real graphs' rows (the phantom graph has none)
+                if (idx >= Y * a.yw) break;
+                if (a.yvec) copy_unit(ty, B, reinterpret_cast<const uint4*>(a.y), reinterpret_cast<uint4*>(a.oy), idx, a.yw);
+                else copy_unit(ty, B, a.y, a.oy, idx, a.yw);
+            } else if (s == 3) {                             // nodes
+                if (idx > pa.N_cap) break;
+                if (idx == pa.N_cap) { a.orowptr[idx] = pa.E_cap; a.ocolptr[idx] = pa.E_cap; break; }
+                if (idx < N) {
+                    const int b = find_slot(tn.off, B, idx);
+                    const int dn = tn.off[b] - tn.first_of(b), de = te.off[b] - te.first_of(b);
+                    const int sn = idx - dn;
+                    a.obatch[idx] = b;
+                    a.orowptr[idx] = a.rowptr[sn] + de;
+                    a.ocolptr[idx] = a.colptr[sn] + de;
+                    if (a.oell_src) {
+                        a.oell_src[idx] = rebase4(a.ell_src[sn], dn);
+                        a.oell_eid[idx] = rebase4(a.ell_eid[sn], de);
+                    }
+                    if (a.oell_dst) {
+                        a.oell_dst[idx] = rebase4(a.ell_dst[sn], dn);
+                        a.oell_eid_t[idx] = rebase4(a.ell_eid_t[sn], de);
+                    }
+                } else {                                     // phantom node: its run of self-loops, the same by target and by source
+                    const int p = idx - N;
+                    const int start = E + p * q + min(p, rem), len = q + (p < rem);
+                    a.obatch[idx] = B;
+                    a.orowptr[idx] = start;
+                    a.ocolptr[idx] = start;
+                    const int4 nodes = make_int4(len > 0 ? idx : -1, len > 1 ? idx : -1, len > 2 ? idx : -1, len > 3 ? idx : -1);
+                    const int4 edges = make_int4(len > 0 ? start : -1, len > 1 ? start + 1 : -1, len > 2 ? start + 2 : -1, len > 3 ? start + 3 : -1);
+                    if (a.oell_src) { a.oell_src[idx] = nodes; a.oell_eid[idx] = edges; }
+                    if (a.oell_dst) { a.oell_dst[idx] = nodes; a.oell_eid_t[idx] = edges; }
+                }
+            } else if (s == 4) {                             // edges
+                if (idx >= pa.E_cap) break;
+                if (idx < E) {
+                    const int b = find_slot(te.off, B, idx);
+                    const int dn = tn.off[b] - tn.first_of(b), de = te.off[b] - te.first_of(b);
+                    const int se = idx - de;
+                    a.oei[idx] = (int64_t)(a.ei[se] + tn.off[b]);
+                    a.oei[(int64_t)pa.E_cap + idx] = (int64_t)(a.ei[(int64_t)a.Ed + se] + tn.off[b]);
+                    a.osrc[idx] = a.src[se] + dn;
+                    a.oeid[idx] = a.eid[se] + de;
+                    a.odst[idx] = a.dst[se] + dn;
+                    a.oeid_t[idx] = a.eid_t[se] + de;
+                } else {                                     // phantom edge: a self-loop of its owner, at its own position in both orders
+                    const int node = N + phantom_owner(idx - E, q, rem);
+                    a.oei[idx] = node;
+                    a.oei[(int64_t)pa.E_cap + idx] = node;
+                    a.osrc[idx] = node;
+                    a.oeid[idx] = idx;
+                    a.odst[idx] = node;
+                    a.oeid_t[idx] = idx;
+                }
+            } else {                                         // slots: the B real graphs, the phantom graph [N, N_cap)
+                if (idx > B + 1) break;
+                const int v = idx <= B ? a.node_off[idx] : pa.N_cap;
+                a.optr64[idx] = v;
+                a.optr32[idx] = v;
+            }
+        }
+    }
+}
+
 }  // namespace glam
 
 using namespace glam;
@@ -225,5 +367,71 @@ extern "C" int glam_collate(const void* const* ds_host, void* const* out_host, c
     if (B <= kCollateSlots) hipLaunchKernelGGL(k_collate<true>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(k_collate<false>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a);
     GLAM_LAUNCH_CHECK("glam_collate");
+    return GLAM_OK;
+}
+
+extern "C" int glam_collate_padded(const void* const* ds_host, void* const* out_host, const int32_t* table, int64_t B, int64_t N_cap,
+                                   int64_t E_cap, int64_t y_rows, int64_t Ed, int32_t x_row_bytes, int32_t x_out_stride_bytes,
+                                   int32_t ea_row_bytes, int32_t y_row_bytes, void* stream) {
+    GLAM_REQUIRE(ds_host && out_host && table, "glam_collate_padded: null pointer (ds_host / out_host / table)");
+    GLAM_REQUIRE(B >= 1 && N_cap >= 1 && E_cap >= 0 && Ed >= 0 && B < INT32_MAX - 1 && N_cap < INT32_MAX && E_cap < INT32_MAX && Ed < INT32_MAX,
+                 "glam_collate_padded: B / N_cap / E_cap / Ed out of range (B >= 1, N_cap >= 1 for the phantom node, all below 2^31 - 1)");
+    GLAM_REQUIRE(x_row_bytes >= 0 && ea_row_bytes >= 0 && y_row_bytes >= 0 && ((x_row_bytes | ea_row_bytes | y_row_bytes) & 3) == 0,
+                 "glam_collate_padded: row sizes must be multiples of 4 bytes");
+    GLAM_REQUIRE(x_out_stride_bytes >= x_row_bytes && x_out_stride_bytes % 16 == 0,
+                 "glam_collate_padded: the output row stride of x must be a multiple of 16 bytes, at least x_row_bytes");
+    const void* const* d = ds_host;
+    void* const* o = out_host;
+    const bool has_y = y_row_bytes > 0 && o[3];
+    GLAM_REQUIRE(!has_y || (y_rows >= 1 && B * y_rows < INT32_MAX), "glam_collate_padded: y rows per graph must be a positive integer");
+    GLAM_REQUIRE(E_cap == 0 || Ed > 0, "glam_collate_padded: phantom edges copy the dataset's edge row 0: a dataset without edges has E_cap = 0");
+    for (int i = 0; i < GLAM_COLLATE_FIELDS; ++i)
+        GLAM_REQUIRE(aligned_to(d[i], 4) && aligned_to(o[i], i == 1 || i == 4 || i == 5 ? 8 : 4), "glam_collate_padded: misaligned pointer (field %d)", i);
+    GLAM_REQUIRE(aligned_to(table, 4), "glam_collate_padded: misaligned table");
+    GLAM_REQUIRE(o[4] && o[5] && o[6] && o[7] && o[10] && d[4] && d[5] && d[6] && d[7] && d[10] && (x_row_bytes == 0 || (d[0] && o[0] && aligned16(o[0]))),
+                 "glam_collate_padded: null pointer (batch / ptr / rowptr / colptr / prefix sums / x), or x output off a 16-byte boundary");
+    GLAM_REQUIRE(E_cap == 0 || (d[1] && o[1] && d[8] && d[9] && d[11] && d[12] && o[8] && o[9] && o[11] && o[12] && (ea_row_bytes == 0 || (d[2] && o[2]))),
+                 "glam_collate_padded: null pointer (edge fields)");
+    GLAM_REQUIRE(!has_y || d[3], "glam_collate_padded: null pointer (y)");
+    for (int i = 13; i < 17; i += 2) {
+        GLAM_REQUIRE((o[i] != nullptr) == (o[i + 1] != nullptr), "glam_collate_padded: one tensor of an ELL pair without the other");
+        GLAM_REQUIRE(!o[i] || (d[i] && d[i + 1]), "glam_collate_padded: ELL output without the dataset's ELL records");
+        GLAM_REQUIRE(!o[i] || (aligned16(o[i]) && aligned16(o[i + 1]) && aligned16(d[i]) && aligned16(d[i + 1])), "glam_collate_padded: misaligned ELL pointer");
+    }
+    CollatePadArgs pa = {};
+    CollateArgs& a = pa.c;
+    a.x = (const uint32_t*)d[0]; a.ei = (const int*)d[1]; a.ea = (const uint32_t*)d[2]; a.y = (const uint32_t*)d[3];
+    a.node_ptr = (const int*)d[4]; a.edge_ptr = (const int*)d[5]; a.y_ptr = (const int*)d[6];
+    a.rowptr = (const int*)d[7]; a.src = (const int*)d[8]; a.eid = (const int*)d[9];
+    a.colptr = (const int*)d[10]; a.dst = (const int*)d[11]; a.eid_t = (const int*)d[12];
+    a.ell_src = (const int4*)d[13]; a.ell_eid = (const int4*)d[14]; a.ell_dst = (const int4*)d[15]; a.ell_eid_t = (const int4*)d[16];
+    a.ids = table; a.node_off = table + (B + 1); a.edge_off = table + 2 * (B + 1); a.y_off = table + 3 * (B + 1);
+    a.ox = (uint32_t*)o[0]; a.oei = (int64_t*)o[1]; a.oea = (uint32_t*)o[2]; a.oy = (uint32_t*)o[3];
+    a.obatch = (int64_t*)o[4]; a.optr64 = (int64_t*)o[5]; a.optr32 = (int*)o[6];
+    a.orowptr = (int*)o[7]; a.osrc = (int*)o[8]; a.oeid = (int*)o[9]; a.ocolptr = (int*)o[10]; a.odst = (int*)o[11]; a.oeid_t = (int*)o[12];
+    a.oell_src = (int4*)o[13]; a.oell_eid = (int4*)o[14]; a.oell_dst = (int4*)o[15]; a.oell_eid_t = (int4*)o[16];
+    a.B = (int)B; a.Ed = (int)Ed;
+    pa.N_cap = (int)N_cap; pa.E_cap = (int)E_cap;
+    // units as in glam_collate; the output rows of x are whole 16-byte units by contract, so x moves as units where its input rows are
+    const int Y = has_y ? (int)(B * y_rows) : 0;
+    a.xvec = x_row_bytes > 0 && x_row_bytes % 16 == 0 && aligned16(d[0]);
+    a.xw = x_row_bytes / (a.xvec ? 16 : 4);
+    pa.xwo = x_out_stride_bytes / (a.xvec ? 16 : 4);
+    a.eavec = ea_row_bytes > 0 && ea_row_bytes % 16 == 0 && aligned16(d[2]) && aligned16(o[2]);
+    a.eaw = ea_row_bytes / (a.eavec ? 16 : 4);
+    a.yvec = has_y && y_row_bytes % 16 == 0 && aligned16(d[3]) && aligned16(o[3]);
+    a.yw = has_y ? y_row_bytes / (a.yvec ? 16 : 4) : 0;
+    const int64_t count[6] = {x_row_bytes > 0 ? N_cap * pa.xwo : 0, o[2] ? E_cap * a.eaw : 0, (int64_t)Y * a.yw, N_cap + 1, E_cap, B + 2};
+    int64_t items = 0;
+    for (int s = 0; s < 6; ++s) {
+        if (count[s] >= INT32_MAX - kCollateItem) return fail(GLAM_E_UNSUPPORTED, "glam_collate_padded: a field of the batch has 2^31 elements or more");
+        a.first[s] = (int)items;
+        items += (count[s] + kCollateItem - 1) / kCollateItem;
+    }
+    a.first[6] = (int)items;
+    const int grid = grid_for(items, 1, kCollateBlocks);
+    if (B <= kCollateSlots) hipLaunchKernelGGL(k_collate_padded<true>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, pa);
+    else hipLaunchKernelGGL(k_collate_padded<false>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, pa);
+    GLAM_LAUNCH_CHECK("glam_collate_padded");
     return GLAM_OK;
 }

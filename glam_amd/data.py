@@ -220,6 +220,50 @@ def resident_table(ids, ns, es, y_rows):
     return table.astype(np.int32), int(table[1, B]), int(table[2, B]), int(table[3, B])
 
 
+def padded_capacity(ns, es, batch_size, ell):
+    """``(N_cap, E_cap)`` of a fixed-capacity batch (``DeviceDataset.padded``) that holds ANY ``batch_size`` distinct graphs of a dataset
+    with per-graph node / edge counts ``ns`` / ``es`` (host numpy).  ``topB(v)`` = the sum of the ``batch_size`` largest entries of ``v``:
+    ``E_cap = topB(es)``, ``N_cap = topB(ns) + 1`` — one phantom node at least.  ``ell``: the batch carries an ELL form (in- or out-degree
+    <= 4 per node), which the phantom nodes must keep: ``N_cap >= ceil((E_cap + topB(4 ns - es)) / 4)`` gives, for every such set S,
+    ``4 (N_cap - N(S)) - (E_cap - E(S)) = 4 N_cap - E_cap - sum_S (4 n - e) >= 4 N_cap - E_cap - topB(4 ns - es) >= 0``."""
+    ns, es = np.asarray(ns, dtype=np.int64), np.asarray(es, dtype=np.int64)
+    B = int(batch_size)
+    if not 1 <= B <= ns.size:
+        raise ValueError(f"padded batches hold 1 .. {ns.size} distinct graphs of this dataset, got batch_size = {batch_size}")
+    top = lambda v: int(np.partition(v, v.size - B)[v.size - B:].sum())     # noqa: E731
+    e_cap, n_cap = top(es), top(ns) + 1
+    if ell:
+        n_cap = max(n_cap, -(-(e_cap + top(4 * ns - es)) // 4))
+    return n_cap, e_cap
+
+
+def padded_bucket(ns, es, y_rows, batch_size, capacity, ell):
+    """The checked ``(N_cap, E_cap, r)`` of ``DeviceDataset.padded``: ``capacity`` (or ``padded_capacity``) and the one constant count of
+    ``y`` rows per graph.  ``ValueError`` for ``y`` rows that differ between graphs or are absent, and for a capacity that the dataset's
+    largest graph does not fit with one phantom node beside it."""
+    y_rows = np.asarray(y_rows, dtype=np.int64)
+    r = int(y_rows[0]) if y_rows.size else 0
+    if r < 1 or bool((y_rows != r).any()):
+        raise ValueError("padded batches need the same number (>= 1) of y rows for every graph: the loss reads output[:B] against y[B * r]")
+    n_cap, e_cap = padded_capacity(ns, es, batch_size, ell) if capacity is None else (int(capacity[0]), int(capacity[1]))
+    if n_cap - 1 < int(np.max(ns)) or e_cap < int(np.max(es)) or max(n_cap, e_cap) >= 2 ** 31 - 1:
+        raise ValueError(f"capacity ({n_cap}, {e_cap}) does not hold the dataset's largest graph ({int(np.max(ns))} nodes + 1 phantom node, "
+                         f"{int(np.max(es))} edges) or exceeds int32")
+    return n_cap, e_cap, r
+
+
+def padded_fit(batch_size, B, N, E, n_cap, e_cap, ell):
+    """``ValueError`` unless a table of ``B`` slots with ``N`` nodes and ``E`` edges fits the bucket ``(batch_size, n_cap, e_cap)``: one
+    phantom node at least, and phantom degrees <= 4 where the batch carries an ELL form.  Distinct ids always fit the capacity of
+    ``padded_capacity``; repeated ids may not."""
+    if B != batch_size:
+        raise ValueError(f"this padded batch holds exactly {batch_size} graphs, got {B} ids")
+    if N > n_cap - 1 or E > e_cap:
+        raise ValueError(f"{N} nodes / {E} edges exceed the capacity ({n_cap} nodes, one of them phantom, {e_cap} edges): repeated ids?")
+    if ell and 4 * (n_cap - N) < e_cap - E:
+        raise ValueError(f"{e_cap - E} surplus edges on {n_cap - N} phantom nodes exceed degree 4 (the ELL form): repeated ids?")
+
+
 class DeviceDataset:
     """A dataset that LIVES ON THE DEVICE, graph index included, so that collating any set of graph ids is one kernel launch
     (``glam_collate``, csrc/collate.hip) behind one small host-to-device copy — no per-field copies, no CSR / ELL builds, no read-back.
@@ -315,6 +359,143 @@ class DeviceDataset:
         return b
 
 
+    def capacity(self, batch_size):
+        """``(N_cap, E_cap)`` that hold any ``batch_size`` distinct graphs of this dataset (``padded_capacity``; pure host numpy)."""
+        return padded_capacity(self.ns, self.es, batch_size, self.ell_ok or self.ell_t_ok)
+
+    def padded(self, batch_size, capacity=None):
+        """A ``PaddedBatch`` of ``batch_size`` graphs: every tensor allocated once, filled by ``load(ids)``."""
+        return PaddedBatch(self, batch_size, capacity)
+
+
+class PaddedBatch(Batch):
+    """A batch of FIXED CAPACITY over a ``DeviceDataset``: the same tensors, at the same addresses and of the same shapes, hold whatever
+    ``load(ids)`` puts into them (``glam_collate_padded``, csrc/collate.hip), so a training step captured on this object replays for
+    every batch of a shuffling loop (``glam_amd.graphs.GraphedTrainStep``).
+
+    It is an ordinary, valid batch of ``num_graphs = B + 1`` graphs: the ``num_real_graphs = B`` loaded ones first, then one PHANTOM
+    graph that owns the surplus ``N_cap - N`` nodes (zero ``x`` rows) and ``E_cap - E`` edges (self-loops, copies of the dataset's edge
+    row 0).  No kernel knows about it; a model that treats graphs independently gives the real graphs their usual rows, and a loss over
+    ``output[:B]`` (``graphs.padded_loss``) gives the phantom rows a zero gradient.  ``y`` has the real graphs' ``B * r`` rows only.
+    ``x`` is the ``[N_cap, F]`` view of a buffer whose rows are zero-padded to 16 bytes: ``ops.pad_cols`` hands the kernels the buffer
+    itself (a cached padded COPY would go stale with the second ``load``: a kernel write does not bump ``_version``)."""
+
+    def __init__(self, dataset, batch_size, capacity=None):
+        from . import ops
+        ds, B = dataset, int(batch_size)
+        self.ell, self.ell_t = ds.ell_ok, ds.ell_t_ok
+        has_y = ds.y is not None
+        N_cap, E_cap, r = padded_bucket(ds.ns, ds.es, ds.y_rows if has_y else np.zeros(0), B, capacity, self.ell or self.ell_t)
+        dev = ds.device
+        xrb, earb, yrb = ds._row_bytes
+        stride = (xrb + 15) & ~15
+        if stride != xrb and ds.x.dim() != 2:
+            raise ValueError(f"padded batches pad the rows of a 2-D x to 16 bytes; x is {tuple(ds.x.shape)}")
+        xbuf = torch.empty((N_cap, stride // ds.x.element_size()) if stride != xrb else (N_cap,) + ds.x.shape[1:], dtype=ds.x.dtype, device=dev)
+        x = ops.slice_cols(xbuf, ds.x.size(1)) if stride != xrb else xbuf
+        new = lambda t, rows: None if t is None else torch.empty((rows,) + t.shape[1:], dtype=t.dtype, device=dev)   # noqa: E731
+        ea, y = new(ds.ea, E_cap), new(ds.y, B * r)
+        ei = torch.empty(2, E_cap, dtype=torch.int64, device=dev)
+        batch, ptr = torch.empty(N_cap, dtype=torch.int64, device=dev), torch.empty(B + 2, dtype=torch.int64, device=dev)
+        sizes = [B + 2, N_cap + 1, E_cap, E_cap, N_cap + 1, E_cap, E_cap] + [4 * N_cap if self.ell else 0] * 2 + [4 * N_cap if self.ell_t else 0] * 2
+        starts = np.concatenate([[0], np.cumsum([(s + 3) & ~3 for s in sizes])])
+        arena = torch.empty(int(starts[-1]), dtype=torch.int32, device=dev)
+        ptr32, rowptr, src, eid, colptr, dst, eid_t, *ells = [arena[a:a + s] for a, s in zip(starts[:-1].tolist(), sizes)]
+        ells = [t.view(N_cap, 4) if t.numel() else None for t in ells]
+        out = [xbuf, ei, ea, y, batch, ptr, ptr32, rowptr, src, eid, colptr, dst, eid_t, *ells]
+        self._out = (ctypes.c_void_p * len(out))(*[None if t is None else t.data_ptr() for t in out])
+        self._keep = (xbuf, arena)
+        self._launch_args = (B, N_cap, E_cap, r, int(ds.ei.size(1)), xrb, stride, earb, yrb)
+        self._ds, self._table = ds, torch.zeros(4, B + 1, dtype=torch.int32, device=dev)
+        self._tables = self.totals = None
+        self._launched = False
+        super().__init__(x=x, edge_index=ei, edge_attr=ea, y=y, batch=batch)
+        self.num_graphs, self.num_real_graphs, self.ptr = B + 1, B, ptr
+        self.capacity = (N_cap, E_cap)
+        gi = ops.GraphIndex.from_parts(ei, N_cap, rowptr, src, eid, (colptr, dst, eid_t), tuple(ells[:2]) if self.ell else None,
+                                       tuple(ells[2:]) if self.ell_t else None)
+        ops._GI_CACHE.put(ei, (N_cap, gi))
+        ops._SP_CACHE.put(batch, ops.SegmentPtr.from_parts(ptr32, N_cap, B + 1))
+        self._glam_marks = {"edge_index": ("_glam_trusted", True), "batch": ("_glam_trusted", True)}
+        if ds.onehot is not None:
+            self._glam_marks["edge_attr"] = ("_glam_onehot", ds.onehot)
+        self._apply_marks()
+
+    def _tensor_items(self):
+        return [(k, v) for k, v in super()._tensor_items() if not k.startswith("_")]
+
+    def to(self, device, non_blocking=False):
+        if torch.device(device) != self._ds.device:
+            raise ValueError("a PaddedBatch lives on its dataset's device")
+        return self
+
+    def _fit(self, B, N, E):
+        padded_fit(self.num_real_graphs, B, N, E, *self.capacity, self.ell or self.ell_t)
+
+    def load(self, ids=None, step=None, launch=True):
+        """Put the graphs ``ids`` (exactly ``B`` of them) into this batch: the slot table goes to the device out of pinned memory, not
+        waited for, and one launch writes every field and the whole index.  ``step=i`` instead of ``ids``: table ``i`` of the last
+        ``load_many``, a device-to-device copy.  ``launch=False`` uploads the table only — for a batch that a ``GraphedTrainStep`` runs
+        next, whose step (eager, captured or replayed) holds the launch itself.  ``IndexError`` for ids outside the dataset, ``ValueError``
+        for a wrong count or ids (repeated ones) that exceed the capacity — before anything is enqueued."""
+        from . import _lib
+        if (ids is None) == (step is None):
+            raise ValueError("PaddedBatch.load takes either ids or step=")
+        if step is not None:
+            if self._tables is None or not 0 <= int(step) < self._tables.size(0):
+                raise IndexError(f"step {step}: load_many has uploaded {0 if self._tables is None else self._tables.size(0)} tables")
+            self._table.copy_(self._tables[int(step)])
+        else:
+            table, N, E, _Y = resident_table(ids, self._ds.ns, self._ds.es, self._ds.y_rows)
+            self._fit(table.shape[1] - 1, N, E)
+            _lib.require_device(self.edge_index)
+            staged = torch.empty(table.shape, dtype=torch.int32, pin_memory=True)
+            staged.numpy()[...] = table
+            self._table.copy_(staged, non_blocking=True)
+        self._launched = False
+        if launch:
+            self.glam_reload()
+            self._launched = True
+        return self
+
+    def load_many(self, id_lists):
+        """The tables of ``len(id_lists)`` batches (an epoch's) from one numpy pass and ONE upload; ``load(step=i)`` then installs table
+        ``i``.  Same errors as ``load``, for every list, before anything is enqueued.  Returns the number of tables."""
+        ds = self._ds
+        B = self.num_real_graphs
+        rows = [np.asarray(i.cpu() if torch.is_tensor(i) else i).reshape(-1) for i in id_lists]
+        if any(r.size != B for r in rows):
+            raise ValueError(f"this padded batch holds exactly {B} graphs, got id lists of {sorted({int(r.size) for r in rows})}")
+        ids = np.stack(rows) if rows else np.zeros((0, B), dtype=np.int64)
+        if ids.dtype.kind not in "iu":
+            raise IndexError(f"graph ids must be integers, got {ids.dtype}")
+        ids = ids.astype(np.int64)
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= ds.n):
+            raise IndexError(f"graph ids must lie in [0, {ds.n}): got {int(ids.min())} .. {int(ids.max())}")
+        tables = np.zeros((ids.shape[0], 4, B + 1), dtype=np.int64)
+        tables[:, 0, :B] = ids
+        for k, counts in enumerate((ds.ns, ds.es, ds.y_rows), 1):
+            np.cumsum(counts[ids], axis=1, out=tables[:, k, 1:])
+        for N, E in zip(tables[:, 1, B].tolist(), tables[:, 2, B].tolist()):
+            self._fit(B, N, E)
+        staged = torch.empty(tables.shape, dtype=torch.int32, pin_memory=True)
+        staged.numpy()[...] = tables
+        self._tables = staged.to(ds.device, non_blocking=True)
+        self.totals = tables[:, 1:3, B].copy()       # (N, E) per table: what the padding overhead is measured against
+        return int(ids.shape[0])
+
+    def glam_reload(self):
+        """The reload hook of ``GraphedTrainStep``: enqueue the collate launch for the table now on the device — on the current
+        stream, so inside a capture it becomes the graph's first node.  Outside a capture a ``load`` that has launched already is not
+        repeated."""
+        from . import _lib
+        if self._launched and not torch.cuda.is_current_stream_capturing():
+            self._launched = False
+            return
+        B, N_cap, E_cap, r, Ed, xrb, stride, earb, yrb = self._launch_args
+        _lib.api().glam_collate_padded(self._ds._ds, self._out, _lib.ptr(self._table), B, N_cap, E_cap, r, Ed, xrb, stride, earb, yrb, _lib.stream())
+
+
 class DataLoader:
     """Sequential mini-batch iterator over a list of ``Data`` (the reference's train
     loader does not shuffle: ``src_1gp/trainer.py:37-38``).
@@ -326,12 +507,23 @@ class DataLoader:
 
     ``resident=True`` (needs a ``device``): the dataset moves to the device once, index included (``DeviceDataset``), and every batch
     — in the same order, from the same shuffle — is one launch behind one small copy, its graph index installed: what a loop that
-    shuffles, samples or walks a library larger than the cache pays per FRESH batch.  ``cache`` keeps its meaning."""
+    shuffles, samples or walks a library larger than the cache pays per FRESH batch.  ``cache`` keeps its meaning.
 
-    def __init__(self, dataset, batch_size=32, shuffle=False, seed=0, device=None, cache=None, resident=False):
+    ``padded=True`` (needs ``resident=True``): every FULL batch of an epoch is the SAME ``PaddedBatch`` object, reloaded — same order, same
+    shuffle — so that a ``GraphedTrainStep`` captures one graph and replays it for all of them; whoever keeps a yielded batch sees the
+    next one in it.  An epoch's tables are uploaded at once (``PaddedBatch.load_many``).  A short last batch comes from the ordinary
+    ``collate``.  ``collate_in_step=True``: the loader uploads the table only and leaves the launch to the stepper's graph."""
+
+    def __init__(self, dataset, batch_size=32, shuffle=False, seed=0, device=None, cache=None, resident=False, padded=False,
+                 collate_in_step=False):
         self.dataset, self.batch_size, self.shuffle, self.seed = list(dataset), batch_size, shuffle, seed
         self.device = device
-        self.cache = (not shuffle) if cache is None else bool(cache)
+        self.padded, self._padded, self.collate_in_step = bool(padded), None, bool(collate_in_step)
+        if self.padded and not resident:
+            raise ValueError("DataLoader: padded=True reloads one batch of a device-resident dataset: pass resident=True")
+        if self.padded and cache:
+            raise ValueError("DataLoader: padded=True hands out one batch object, reloaded: there is nothing to cache")
+        self.cache = (not shuffle and not self.padded) if cache is None else bool(cache)
         if self.cache and shuffle:
             raise ValueError("DataLoader: cached batches need a fixed order (shuffle=False)")
         self._epoch = 0
@@ -373,7 +565,16 @@ class DataLoader:
                 self._batches = [self._collate(order[s:s + self.batch_size]) for s in range(0, len(order), self.batch_size)]
             yield from self._batches
             return
-        for s in range(0, len(order), self.batch_size):
+        full = 0
+        if self.padded and len(order) >= self.batch_size:
+            if self._resident is None:
+                self._resident = DeviceDataset(self._packed, self.device)
+            if self._padded is None:
+                self._padded = self._resident.padded(self.batch_size)
+            full = self._padded.load_many(order[:len(order) // self.batch_size * self.batch_size].reshape(-1, self.batch_size))
+            for i in range(full):
+                yield self._padded.load(step=i, launch=not self.collate_in_step)
+        for s in range(full * self.batch_size, len(order), self.batch_size):
             yield self._collate(order[s:s + self.batch_size])
 
 

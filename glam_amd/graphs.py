@@ -20,6 +20,11 @@ per application: equal within fp32 rounding.  ``GraphedTrainStep.run(batches)`` 
 bubble of ≈7 µs on this stack (a 99 µs step replays in 92 µs at eight steps per launch, bench.py), and an ESOL epoch at the reference's
 batch size is 36 launches otherwise.  Requirements: an optimizer created with ``capturable=True`` (Adam/AdamW, ``glam_amd.optim.Adam`` / ``Ranger``), a
 loss function of ``(output, batch)`` that stays on the device, and no data-dependent Python control flow in the model.
+
+A loop that SHUFFLES has no recurring batch objects; it gets one by construction: ``glam_amd.data.PaddedBatch`` is one batch of fixed
+capacity that every ``load(ids)`` refills in place.  The stepper calls its reload hook (``glam_reload``: the collate launch) first in
+every step, so the capture holds it and a replay is one table copy and one ``hipGraphLaunch`` per shuffled batch; ``padded_loss`` keeps the
+phantom graph's output row out of the loss, and ``padded_admission`` refuses models that would let it reach the real graphs.
 """
 from __future__ import annotations
 
@@ -71,6 +76,7 @@ class GraphedTrainStep:
         self._pool = None
         self._lr = [None] * len(optimizer.param_groups)
         self._hyper = None
+        self._admitted = False    # the model has passed the admission check of padded batches (once, on the first padded step)
 
     _BAKED = ("betas", "eps", "weight_decay", "amsgrad", "maximize", "momentum", "dampening", "nesterov", "alpha", "centered", "k",
               "N_sma_threshhold")
@@ -102,9 +108,18 @@ class GraphedTrainStep:
         self._hyper = snap
 
     def _step(self, batch):
+        # a fixed-capacity batch (glam_amd.data.PaddedBatch) brings its collate launch along: first in the step, so that a capture holds
+        # it and a replay re-collates whatever table the host has put on the device since
+        reload = getattr(batch, "glam_reload", None)
+        guard = contextlib.nullcontext()
+        if reload is not None:
+            if not self._admitted:
+                guard = padded_admission(self.model)      # (ValueError here for what the module tree shows; the rest at its call)
+            reload()
         self.optimizer.zero_grad(set_to_none=True)
-        with no_graphed_call():           # the whole step is this class's graph: the model's own graphed-callable route stays out of it
+        with no_graphed_call(), guard:    # the whole step is this class's graph: the model's own graphed-callable route stays out of it
             loss = self.loss_fn(self.model(batch), batch)
+        self._admitted = self._admitted or reload is not None
         # the root gradient as a tensor kept across steps: `loss.backward()` alone launches a fill for ones_like(loss) in every step
         one = self._one.get(loss.device) if (loss.dim() == 0 and loss.dtype == torch.float32 and loss.is_cuda) else None
         if one is None and loss.dim() == 0 and loss.dtype == torch.float32 and loss.is_cuda and not torch.cuda.is_current_stream_capturing():
@@ -175,6 +190,53 @@ class GraphedTrainStep:
 
     def graphs(self):
         return sum(1 for s in self._state.values() if s[2] is not None) + len(self._multi)
+
+
+def padded_loss(loss_fn):
+    """``loss_fn(output, batch)`` for a ``PaddedBatch``: the loss sees ``output[:num_real_graphs]`` — ``batch.y`` already holds the real
+    graphs' rows only — so the phantom graph's row gets a zero gradient and adds ``0 * finite`` to every weight gradient.  Any other batch
+    passes through unchanged.  (The slice's backward is a fill and a copy per step)"""
+    def loss(output, batch):
+        n = getattr(batch, "num_real_graphs", None)
+        return loss_fn(output if n is None else output[:n], batch)
+    return loss
+
+
+class padded_admission:
+    """The admission check of padded batches: a ``PaddedBatch`` carries a phantom graph, so every module must compute a graph's output
+    from that graph alone, and nothing may cache what it derives from a batch's CONTENT on the host.  ``ValueError``, naming the
+    module, at construction for ``_BatchNorm`` (statistics over all rows), ``_GraphSizeNorm`` (the reference drops its ``batch``: it scales
+    by the row count) and ``_GCNConv`` / ``_GATConv`` (their self-loop edge list is derived by boolean masking and cached on the
+    ``GraphIndex``: stale on a static buffer); and, as a context manager around the model's first padded forward, for a ``_LayerNorm`` /
+    ``_PairNorm`` that is CALLED without its ``batch`` vector (``flat_norm`` / ``end_norm`` of the reference's models): statistics over all
+    rows again.  Admitted: ``_TripletMessage``, ``_TripletMessageLight``, ``_NNConv``, the norms called per graph, every readout."""
+
+    def __init__(self, model):
+        from . import layer
+        refused = (layer._BatchNorm, layer.BatchNorm, torch.nn.modules.batchnorm._BatchNorm, layer._GraphSizeNorm, layer.GraphSizeNorm,
+                   layer._GCNConv, layer._GATConv, layer.GCNConv, layer.GATConv)
+        self._norms, self._handles = [], []
+        for name, m in model.named_modules():
+            if isinstance(m, refused):
+                raise ValueError(f"padded batches: {name or 'model'} ({type(m).__name__}) makes a graph's output depend on the rest of the "
+                                 f"batch or on host caches derived from its content; it is not admitted (DESIGN.md §4.16)")
+            if isinstance(m, (layer._LayerNorm, layer._PairNorm)):
+                self._norms.append((name, m))
+
+    def __enter__(self):
+        def check(name):
+            def pre(mod, args, kwargs):
+                if (args[1] if len(args) > 1 else kwargs.get("batch")) is None:
+                    raise ValueError(f"padded batches: {name} ({type(mod).__name__}) is called without its batch vector: its statistics "
+                                     f"would run over the phantom graph's rows too; it is not admitted (DESIGN.md §4.16)")
+            return pre
+        self._handles = [m.register_forward_pre_hook(check(name), with_kwargs=True) for name, m in self._norms]
+        return self
+
+    def __exit__(self, *exc):
+        for h in self._handles:
+            h.remove()
+        return False
 
 
 class GraphedForward:
@@ -392,7 +454,9 @@ class GraphedCallable:
         ligand + protein for ``ArchitectureDTI``, two drugs for ``ArchitectureDDI``."""
         fields = [self._fields(d) for d in datas]
         ok = (GRAPHED_CALL and not _suspended and getattr(module, "graphed_call", True) and len(datas) > 0
-              and not module._forward_hooks and not module._forward_pre_hooks and not torch.cuda.is_current_stream_capturing())
+              and not module._forward_hooks and not module._forward_pre_hooks and not torch.cuda.is_current_stream_capturing()
+              # (a fixed-capacity batch is rewritten in place by a kernel, which no version counter sees: never recognised as "the same")
+              and not any(hasattr(d, "glam_reload") for d in datas))
         for x, ei, ea, bv in (fields if ok else ()):
             ok = (ok and all(torch.is_tensor(t) for t in (x, ei, ea, bv)) and x.is_cuda and x.dtype == torch.float32 and not x.requires_grad
                   and x.numel() > 0 and ei.numel() > 0 and ei.dtype == torch.int64 and bv.dtype == torch.int64 and ea.dtype == torch.float32

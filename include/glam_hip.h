@@ -1051,6 +1051,30 @@ size_t glam_collate_lds_slots(void);
 int glam_collate(const void* const* ds_host, void* const* out_host, const int32_t* table, int64_t B, int64_t N, int64_t E,
                  int64_t Y, int64_t Ed, int32_t x_row_bytes, int32_t ea_row_bytes, int32_t y_row_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * glam_collate into tensors of FIXED CAPACITY, so that the launch — grid, sizes, every pointer — is the same for every batch of B graphs
+ * and can sit inside a captured hipGraph.  Replaces: nothing in the reference (its loader shuffles and its step runs eagerly); here it
+ * is what lets a shuffling loop replay one captured training step.
+ * The output is an ordinary batch of B + 1 graphs: the B real ones first, exactly as glam_collate writes them for the same table
+ * (rows [0, N) of the node fields, [0, E) of the edge fields, [0, B * y_rows) of y, slots [0, B] of both ptr), then ONE phantom graph
+ * that owns the surplus P = N_cap - N nodes and E_pad = E_cap - E edges.  N = table[1][B] and E = table[2][B] are read on the device.
+ * Phantom node p (id N + p): batch = B, x row zero, a contiguous run of self-loops (N + p, N + p) of q + (p < rem) edges starting at
+ * E + p * q + min(p, rem), with q = E_pad / P and rem = E_pad % P.  rowptr / colptr continue from E with those run lengths and close
+ * with E_cap at [N_cap]; src = dst = N + p; eid = eid_t = the edge's own position; the ELL records (where given) hold the run in order
+ * and -1 in the free slots; edge_attr rows of phantom edges are copies of the dataset's edge row 0; ptr[B] = N, ptr[B + 1] = N_cap.
+ * out_host as for glam_collate with these sizes: x [N_cap rows of x_out_stride_bytes], edge_index int64 [2, E_cap], edge_attr [E_cap
+ * rows], y [B * y_rows rows], batch [N_cap], ptr int64 / int32 [B + 2], rowptr / colptr [N_cap + 1], src / eid / dst / eid_t [E_cap],
+ * ELL [N_cap, 4].  x_out_stride_bytes >= x_row_bytes, a multiple of 16, x output 16-byte aligned: the pad columns of EVERY row are
+ * written as zero (the kernels' zero-padded row layout, written in place).  y_rows: rows of y per graph, one constant.
+ * The caller guarantees: P >= 1, E_pad >= 0, 4 * P >= E_pad where an ELL pair is given (phantom degrees stay <= 4), table as for
+ * glam_collate.  No workspace, no atomics, no flag.
+ * GLAM_E_INVALID for null / misaligned pointers, B < 1, N_cap < 1, E_cap < 0 or E_cap > 0 over a dataset without edges, sizes
+ * beyond int32, a stride that is no multiple of 16 or below x_row_bytes, y given with y_rows < 1 (all checked before any device
+ * work); GLAM_E_UNSUPPORTED for a field of 2^31 elements or more. */
+int glam_collate_padded(const void* const* ds_host, void* const* out_host, const int32_t* table, int64_t B, int64_t N_cap, int64_t E_cap,
+                        int64_t y_rows, int64_t Ed, int32_t x_row_bytes, int32_t x_out_stride_bytes, int32_t ea_row_bytes,
+                        int32_t y_row_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,12 +1,14 @@
 """Developer aid: the library's kernel launches of ONE full-model training step, in launch order (glam_prof_* labels and durations; ATen
 launches are not listed: tools/bench_model.py --profile names those; the ATen normalisation ops of the step are counted at the end).
-usage: kernel_sequence.py [batch] [preset]      (preset: relu, model_default, colnorm = a norm in every slot)"""
+usage: kernel_sequence.py [batch] [preset]      (preset: relu, model_default, colnorm = a norm in every slot, DESIGN.md 4.12;
+padded = relu on a fixed-capacity batch with the loss over output[:B], DESIGN.md 4.16: the collate launch leads the sequence and the ATen
+ops of the output slice are counted at the end)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from glam_amd import _lib, model, ops, optim, loss as glam_loss
 ops.USE_TORCH_EXT = False      # the route a captured step takes
-from glam_amd.data import synth_batch
+from glam_amd.data import DeviceDataset, synth_batch, synth_molecule
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 dev = torch.device("cuda")
@@ -21,14 +23,22 @@ else:
     net = model.Architecture(mol_block="_TripletMessage", message_steps=3, graph_do="_None()", end_do="_None()", pre_act="ReLU", graph_act="ReLU",
                              flat_act="ReLU").to(dev)
 net.graphed_call = False      # (eager launches: every one carries its own events)
-b = synth_batch(B, seed=0).to(dev)
+if PRESET == "padded":
+    import numpy as np
+    rng = np.random.default_rng(0)
+    b = DeviceDataset([synth_molecule(rng) for _ in range(2 * B)], dev).padded(B)
+    b.load(rng.permutation(2 * B)[:B], launch=False)
+else:
+    b = synth_batch(B, seed=0).to(dev)
 y = b.y.view(-1)
 opt = optim.Adam(net.parameters(), lr=1e-3)
 ONE = torch.ones((), device=dev)
 
 def body():
+    if PRESET == "padded":
+        b.glam_reload()              # (the step's first launch: GraphedTrainStep calls the batch's reload hook)
     opt.zero_grad(set_to_none=True)
-    loss = glam_loss.mse_loss(net(b).view(-1), y)
+    loss = glam_loss.mse_loss(net(b)[:B].view(-1), y)      # (every preset's output has B rows but the padded one's: B + 1)
     loss.backward(gradient=ONE)
     opt.step()
 
@@ -48,6 +58,8 @@ print(f"{i + 1} launches, {tot:.1f} us of kernels")
 import collections
 from torch.utils._python_dispatch import TorchDispatchMode
 NORM_OPS = ("batch_norm", "layer_norm", "aten.mean", "aten.std", "aten.var", "miopen")
+if PRESET == "padded":             # ... and what the slice output[:B] adds: forward a view, backward a zero fill and a copy into it
+    NORM_OPS += ("slice", "aten.zeros", "aten.new_zeros", "aten.zero_", "aten.fill_", "aten.copy_")
 seen = collections.Counter()
 class Log(TorchDispatchMode):
     def __torch_dispatch__(self, func, types, args=(), kwargs=None):
@@ -57,4 +69,4 @@ class Log(TorchDispatchMode):
 with Log():
     body()
 torch.cuda.synchronize()
-print("ATen normalisation ops in the step:", dict(seen) if seen else "none")
+print("ATen normalisation ops in the step:" if PRESET != "padded" else "ATen normalisation, slice, fill and copy ops in the step:", dict(seen) if seen else "none")

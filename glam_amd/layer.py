@@ -1181,3 +1181,10 @@ def dot_and_global_pool2_indexed(mol_out, pro_out, mol_batch, pro_sp, pro_of_pai
     ``pro_of_pair[i]`` of ``pro_sp`` (the ``SegmentPtr`` of the encoded proteins; ``ops.pair_index`` for the index).  Inference only;
     widths are handled as there: the rows flow as they are."""
     return ops.pair_pool_indexed(mol_out, pro_out, ops.segment_ptr(mol_batch), pro_sp, pro_of_pair, return_argmax)
+
+
+def dot_and_global_pool2_gather(x1, x2, sp1, sp2, idx1=None, idx2=None, return_argmax=False):
+    """``dot_and_global_pool2`` with BOTH sides held once: pair i is segment ``idx1[i]`` of ``sp1`` against segment ``idx2[i]`` of ``sp2``
+    (the ``SegmentPtr``s of the encoded drugs; ``ops.pair_index`` for the indices) — the fusion of ``ArchitectureDDI.score_pairs``.
+    Inference only; widths are handled as in ``dot_and_global_pool2_indexed``: the rows flow as they are."""
+    return ops.pair_pool_gather(x1, x2, sp1, sp2, idx1, idx2, return_argmax)

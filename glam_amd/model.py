@@ -18,7 +18,7 @@ from ._lib import GlamHipError
 from .layer import _None  # noqa: F401
 from .layer import GlobalPool5, GlobalLAPool, Set2Set  # noqa: F401  (resolved from config strings)
 from .layer import LinearBlock, MessageBlock, dot_and_global_pool2, first_node_spec, flat_then_head, following_dropout, prestage_pass
-from .layer import _BatchNorm, _LayerNorm, _PairNorm, dot_and_global_pool2_indexed
+from .layer import _BatchNorm, _LayerNorm, _PairNorm, dot_and_global_pool2_gather, dot_and_global_pool2_indexed
 
 
 def model_args(args):
@@ -80,6 +80,26 @@ class Architecture(torch.nn.Module):
 
 
 Model = Architecture
+
+
+def _tower_stamp(modules):
+    """Changes whenever a parameter or buffer of ``modules`` is written (version counters; storage addresses for ``.data`` swaps and
+    ``.to()``; ``ops.PARAM_EPOCH`` for the optimizers that write through raw pointers)."""
+    ts = [t for m in modules for t in list(m.parameters()) + list(m.buffers())]
+    return ops.PARAM_EPOCH, sum(t._version for t in ts), tuple(t.data_ptr() for t in ts)
+
+
+def _tower_norms_guard(what, slots, thing, call):
+    """The norm rules of an encoding that stands for every copy of a graph: ``slots`` = (name, block, admitted norm types)."""
+    for name, block, ok in slots:
+        if type(block.norm) not in ok:
+            raise GlamHipError(f"{what}: {name}'s norm {type(block.norm).__name__} is not per graph or per row here — it normalises over "
+                               f"the whole batch (rows of every copy of every {thing}), so its result depends on how often each {thing} "
+                               f"is repeated and one encoding cannot reproduce {call}")
+
+
+_PER_GRAPH_NORMS = (_None, _BatchNorm, _LayerNorm, _PairNorm)      # slots given ``batch``
+_PER_ROW_NORMS = (_None, _BatchNorm)                               # the *_flat slots (no ``batch``)
 
 
 class ProteinEncoding:
@@ -162,8 +182,7 @@ class ArchitectureDTI(torch.nn.Module):
     def _protein_stamp(self):
         """Changes whenever a protein-side parameter or buffer is written (version counters; storage addresses for ``.data`` swaps and
         ``.to()``; ``ops.PARAM_EPOCH`` for the optimizers that write through raw pointers)."""
-        ts = [t for m in self._protein_modules() for t in list(m.parameters()) + list(m.buffers())]
-        return ops.PARAM_EPOCH, sum(t._version for t in ts), tuple(t.data_ptr() for t in ts)
+        return _tower_stamp(self._protein_modules())
 
     def _screen_guard(self, what):
         if self.training:
@@ -172,13 +191,8 @@ class ArchitectureDTI(torch.nn.Module):
         if torch.is_grad_enabled():
             raise GlamHipError(f"{what} is inference only (the indexed fusion has no backward): call it under torch.no_grad(); "
                                "training runs model(data_mol, data_pro) on one protein graph per pair")
-        for name, block, ok in (("pro_lin0", self.pro_lin0, (_None, _BatchNorm, _LayerNorm, _PairNorm)),
-                                ("pro_conv", self.pro_conv, (_None, _BatchNorm, _LayerNorm, _PairNorm)),
-                                ("pro_flat", self.pro_flat, (_None, _BatchNorm))):
-            if type(block.norm) not in ok:
-                raise GlamHipError(f"{what}: {name}'s norm {type(block.norm).__name__} is not per graph or per row here — it normalises over "
-                                   "the whole batch (rows of every copy of every protein), so its result depends on how often each protein "
-                                   "is repeated and one encoding cannot reproduce model(data_mol, data_pro)")
+        _tower_norms_guard(what, (("pro_lin0", self.pro_lin0, _PER_GRAPH_NORMS), ("pro_conv", self.pro_conv, _PER_GRAPH_NORMS),
+                                  ("pro_flat", self.pro_flat, _PER_ROW_NORMS)), "protein", "model(data_mol, data_pro)")
         if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
             raise GlamHipError(f"{what} runs eagerly (a library walk never repeats a batch): not inside a hipGraph capture")
 
@@ -229,6 +243,18 @@ class ArchitectureDTI(torch.nn.Module):
             outp = enc.flat.index_select(0, index.on(enc.flat.device))
             out = self.lin_out1(self.lin_out0(ops.cat_cols([outm, outp] + fusion)))
         return (out, contacts) if return_argmax else out
+
+
+class DrugEncoding:
+    """What ``ArchitectureDDI.encode_drugs`` keeps of ``Q`` molecule graphs for ``score_pairs``: ``rows1[s]`` / ``rows2[s]`` the rows of
+    tower 1 / tower 2 after message step ``s`` (contiguous, as the fusion reads them), ``sp`` their one ``SegmentPtr``, ``flat1`` /
+    ``flat2`` = ``molK_flat(molK_readout(.))`` ``[Q, hid]``, ``num_graphs`` = Q, and the stamp of the tower parameters it was computed
+    from (``model`` is a weak reference)."""
+
+    def __init__(self, model, rows1, rows2, sp, flat1, flat2, stamp):
+        self.model, self.rows1, self.rows2, self.sp = weakref.ref(model), rows1, rows2, sp
+        self.flat1, self.flat2, self.stamp = flat1, flat2, stamp
+        self.num_graphs = sp.B
 
 
 class ArchitectureDDI(torch.nn.Module):
@@ -283,3 +309,84 @@ class ArchitectureDDI(torch.nn.Module):
         o2 = self.mol2_flat(self.mol2_readout(x2, mol2.batch, n2))
         out = ops.cat_cols([o1, o2] + fusion)
         return self.lin_out1(self.lin_out0(out))
+
+    # ---- pair scoring: every drug is encoded once, a pair is two indices -----------------------------------------------------
+    # The reference builds its pairs by looking both drugs up in one dictionary of molecule graphs (src_2gi_ddi/dataset.py:170-176) and
+    # runs both towers on every copy.  Nothing in either tower depends on the partner drug: dot_and_global_pool2 reads both towers'
+    # rows after each step and hands two scalars per pair to the head (src_2gi_ddi/model.py:47-59).  In eval mode nothing in a tower
+    # depends on the other graphs of the batch either, with the exceptions of ``ArchitectureDTI._screen_guard`` — applied here to BOTH
+    # towers.  The head's norms (``end_norm``) see the same [P, .] matrix as ``model(mol1, mol2)`` would: nothing is refused there.
+    def _drug_modules(self):
+        return (self.mol1_lin0, self.mol2_lin0, self.mol1_conv, self.mol2_conv, self.mol1_readout, self.mol2_readout, self.mol1_flat,
+                self.mol2_flat)
+
+    def _drug_stamp(self):
+        """Changes whenever a parameter or buffer of either tower (lin0, conv, readout, flat) is written; the head is not part of it."""
+        return _tower_stamp(self._drug_modules())
+
+    def _pairs_guard(self, what):
+        if self.training:
+            raise GlamHipError(f"{what}: the model is in training mode — Dropout / RReLU noise is drawn per copy of a drug and BatchNorm takes "
+                               "statistics over the replicated rows, so one encoding cannot stand for the copies: call model.eval()")
+        if torch.is_grad_enabled():
+            raise GlamHipError(f"{what} is inference only (the gathered fusion has no backward): call it under torch.no_grad(); "
+                               "training runs model(mol1, mol2) on one graph per pair and side")
+        _tower_norms_guard(what, [(f"mol{t}_{slot}", getattr(self, f"mol{t}_{slot}"), ok) for t in (1, 2)
+                                  for slot, ok in (("lin0", _PER_GRAPH_NORMS), ("conv", _PER_GRAPH_NORMS), ("flat", _PER_ROW_NORMS))],
+                           "drug", "model(mol1, mol2)")
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise GlamHipError(f"{what} runs eagerly (its pair index is validated on the host and differs from call to call): not inside a "
+                               "hipGraph capture")
+
+    def encode_drugs(self, data):
+        """Both towers, once, over the ``Q`` graphs of ``data`` -> ``DrugEncoding`` for ``score_pairs``.  ``eval()`` mode under
+        ``torch.no_grad()``; valid until a parameter or buffer of either tower changes."""
+        self._pairs_guard("encode_drugs")
+        nq = getattr(data, "num_graphs", None) or None
+        with ops.weight_scope():
+            prestage_pass((self.mol1_lin0, self.mol1_conv, data.x, data.edge_attr), (self.mol2_lin0, self.mol2_conv, data.x, data.edge_attr))
+            x1 = self.mol1_lin0(data.x, batch=data.batch)
+            x2 = self.mol2_lin0(data.x, batch=data.batch)
+            h1, h2, rows1, rows2 = None, None, [], []
+            for i in range(self.message_steps):
+                with ops.block_feeds_itself(i + 1 < self.message_steps):      # (the routes of _forward: the rows are its rows bit for bit)
+                    x1, h1 = self.mol1_conv(x1, data.edge_index, data.edge_attr, h=h1, batch=data.batch)
+                    x2, h2 = self.mol2_conv(x2, data.edge_index, data.edge_attr, h=h2, batch=data.batch)
+                rows1.append(x1.contiguous())         # (odd widths flow as [N, C] views of padded rows: compacted here, once)
+                rows2.append(x2.contiguous())
+            sp = ops.segment_ptr(data.batch, nq)
+            flat1 = self.mol1_flat(self.mol1_readout(x1, data.batch, nq))
+            flat2 = self.mol2_flat(self.mol2_readout(x2, data.batch, nq))
+        return DrugEncoding(self, rows1, rows2, sp, flat1, flat2, self._drug_stamp())
+
+    def score_pairs(self, enc, first, second, return_argmax=False):
+        """``model(B1, B2)`` -> ``[P, out_dim]`` for ``B1`` = the drugs ``first`` and ``B2`` = the drugs ``second`` of ``enc``, collated one
+        per pair — without building either batch or running a tower: every step's fusion reads the encoded rows of that step through both
+        indices (``ops.pair_pool_gather``), the two ``flat`` matrices are gathered by them, then the head.  ``first`` / ``second``: host
+        integers in ``[0, enc.num_graphs)``, one per pair (``ops.pair_index``).  The head's norms take their statistics over the ``P``
+        pairs of THIS call, as ``model(B1, B2)`` does over its batch: the equality holds per call, for the P pairs of that call (with
+        ``end_norm="_LayerNorm"`` a chunk scored alone differs from the same pairs scored inside a longer call).
+        ``return_argmax``: also the per-step ``[P, 2]`` int32 contacts (row of ``enc.rows1[s]``, row of ``enc.rows2[s]``)."""
+        self._pairs_guard("score_pairs")
+        if not isinstance(enc, DrugEncoding) or enc.model() is not self:
+            raise GlamHipError("score_pairs: the encoding was made by another model (its rows are that model's): encode_drugs() on this one")
+        if enc.stamp != self._drug_stamp() or len(enc.rows1) != self.message_steps:
+            raise GlamHipError("score_pairs: the encoding is stale — a parameter or buffer of a tower (mol1_* / mol2_* lin0, conv, readout, "
+                               "flat) was written since encode_drugs(): encode again")
+        Q = enc.num_graphs
+        P = first.P if isinstance(first, ops.PairIndex) else len(first)
+        i1 = ops.pair_index(first, P, Q, name="first", over="drugs")               # host-side, before the first launch
+        i2 = ops.pair_index(second, P, Q, name="second", over="drugs")
+        fusion, contacts = [], []
+        for s in range(self.message_steps):
+            f = dot_and_global_pool2_gather(enc.rows1[s], enc.rows2[s], enc.sp, enc.sp, i1, i2, return_argmax)
+            if return_argmax:
+                f, a = f
+                contacts.append(a)
+            fusion.append(f)
+        dev = enc.flat1.device
+        o1 = enc.flat1.index_select(0, i1.on(dev))
+        o2 = enc.flat2.index_select(0, i2.on(dev))
+        with ops.weight_scope():
+            out = self.lin_out1(self.lin_out0(ops.cat_cols([o1, o2] + fusion)))
+        return (out, contacts) if return_argmax else out

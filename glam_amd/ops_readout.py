@@ -641,20 +641,23 @@ class PairIndex:
         return t
 
 
-def pair_index(pro_of_pair, P, Q, default="identity"):
+def pair_index(pro_of_pair, P, Q, default="identity", name="pro_of_pair", over="proteins"):
     """``PairIndex`` of ``pro_of_pair`` for ``P`` pairs over ``Q`` proteins — host only, before anything is launched (the kernel trusts
     the index; the policy of ``data.resident_table``).  A host sequence, numpy array or CPU tensor of integers of length ``P``;
     ``IndexError`` for a wrong length or an entry outside ``[0, Q)``; a device tensor is refused (validating it would be a hidden
     read-back).  ``None``: ``default="identity"`` pairs ligand i with protein i (needs ``Q == P``), ``default="single"`` pairs every
-    ligand with the one protein (needs ``Q == 1``)."""
+    ligand with the one protein (needs ``Q == 1``).  ``name`` / ``over``: what the messages call the index and the things it points
+    into (``ops.pair_pool_gather`` validates ``idx1`` / ``idx2`` over drugs with the same rules)."""
     P, Q = int(P), int(Q)
     if isinstance(pro_of_pair, PairIndex):
         if pro_of_pair.P != P or pro_of_pair.Q != Q:
-            raise IndexError(f"pro_of_pair was validated for {pro_of_pair.P} pairs over {pro_of_pair.Q} proteins, not {P} over {Q}")
+            raise IndexError(f"{name} was validated for {pro_of_pair.P} pairs over {pro_of_pair.Q} {over}, not {P} over {Q}")
         return pro_of_pair
     if pro_of_pair is None:
         if default == "identity":
             if Q != P:
+                if name != "pro_of_pair":
+                    raise IndexError(f"{name}=None takes segment i for pair i: {P} pairs but {Q} {over}")
                 raise IndexError(f"pro_of_pair=None pairs ligand i with protein i: {P} ligands but {Q} proteins")
             return PairIndex(np.arange(P, dtype=np.int32), Q)
         if Q != 1:
@@ -662,18 +665,18 @@ def pair_index(pro_of_pair, P, Q, default="identity"):
         return PairIndex(np.zeros(P, dtype=np.int32), Q)
     if torch.is_tensor(pro_of_pair):
         if pro_of_pair.device.type != "cpu":
-            raise GlamHipError("pro_of_pair lives on a device: it is validated on the host before the launch, which would be a hidden "
+            raise GlamHipError(f"{name} lives on a device: it is validated on the host before the launch, which would be a hidden "
                                "read-back — pass the host sequence / numpy array / CPU tensor it was made from")
         pro_of_pair = pro_of_pair.detach().numpy()
     idx = np.asarray(pro_of_pair)
     if idx.size == 0:
         idx = np.zeros(0, dtype=np.int64)
     if idx.dtype.kind not in "iu":
-        raise IndexError(f"pro_of_pair must hold integers, got {idx.dtype}")
+        raise IndexError(f"{name} must hold integers, got {idx.dtype}")
     if idx.ndim != 1 or idx.shape[0] != P:
-        raise IndexError(f"pro_of_pair must have one entry per pair: shape {tuple(idx.shape)} for {P} pairs")
+        raise IndexError(f"{name} must have one entry per pair: shape {tuple(idx.shape)} for {P} pairs")
     if P and (int(idx.min()) < 0 or int(idx.max()) >= Q):
-        raise IndexError(f"pro_of_pair must lie in [0, {Q}): got {int(idx.min())} .. {int(idx.max())}")
+        raise IndexError(f"{name} must lie in [0, {Q}): got {int(idx.min())} .. {int(idx.max())}")
     return PairIndex(idx.astype(np.int32), Q)
 
 
@@ -698,4 +701,38 @@ def pair_pool_indexed(mol_out, pro_out, msp, psp, pro_of_pair=None, return_argma
     ws = torch.empty(max(lib.glam_pair_pool_workspace_bytes(P, D), 16), dtype=torch.uint8, device=mol.device)
     lib.glam_pair_pool_indexed_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(index.on(mol.device)), P, Q, D, ptr(out), ptr(arg),
                                    ptr(ws), ws.numel(), stream())
+    return (out, arg) if return_argmax else out
+
+
+# --------------------------------------------------------------------------------------
+# drug x drug: the fusion with BOTH sides held once and both indexed (csrc/pairgather.hip, glam_pair_pool_gather_fwd)
+# --------------------------------------------------------------------------------------
+def pair_pool_gather(x1, x2, sp1, sp2, idx1=None, idx2=None, return_argmax=False):
+    """``[max, mean]`` of ``x1[seg_a] @ x2[seg_b].T`` with ``a = idx1[i]``, ``b = idx2[i]`` -> ``[P, 2]``: ``pair_pool`` on two sets of
+    small segments that are each held once (``sp1.B`` / ``sp2.B`` of them) — one wave per pair, one launch.  The max column — and with
+    ``return_argmax`` the ``[P, 2]`` int32 rows of the maximum in ``x1`` / ``x2`` (-1 for an empty pair) — is bit for bit that of
+    ``pair_pool`` on physically gathered rows; the mean is the same bits on every run and within the fp64-twin bound.
+    ``idx1`` / ``idx2``: see ``pair_index``; ``None`` = identity on that side (needs ``sp.B == P``); ``P`` is the length of whichever is
+    given.  Widths 1..128.  Inference only: there is no backward (training is ``ops.pair_pool`` on one graph per pair and side)."""
+    Q1, Q2 = sp1.B, sp2.B
+    given = idx1 if idx1 is not None else idx2
+    P = Q1 if given is None else given.P if isinstance(given, PairIndex) else len(given)
+    i1 = None if idx1 is None and Q1 == P else pair_index(idx1, P, Q1, name="idx1", over="segments of x1")
+    i2 = None if idx2 is None and Q2 == P else pair_index(idx2, P, Q2, name="idx2", over="segments of x2")
+    if torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
+        raise GlamHipError("pair_pool_gather is inference only (no backward): call it under torch.no_grad(); the training route is "
+                           "ops.pair_pool on one graph per pair and side")
+    require_device(x1, x2)
+    if x1.dim() != 2 or x2.dim() != 2 or x1.size(1) != x2.size(1) or x1.size(0) != sp1.N or x2.size(0) != sp2.N:
+        raise GlamHipError(f"pair_pool_gather: the two sides disagree (width / node count): x1 {tuple(x1.shape)} for {sp1.N} rows, "
+                           f"x2 {tuple(x2.shape)} for {sp2.N} rows")
+    x1, x2 = f32c(x1, "x1"), f32c(x2, "x2")
+    D = x1.size(1)
+    lib = _lib.api()
+    if lib.glam_pair_pool_gather_load_bytes(ptr(x1), ptr(x2), D) == 0:
+        raise GlamHipError(f"pair_pool_gather: width {D} is outside the kernel table (1..128)")
+    out = torch.empty(P, 2, dtype=torch.float32, device=x1.device)
+    arg = torch.empty(P, 2, dtype=torch.int32, device=x1.device) if return_argmax else None
+    lib.glam_pair_pool_gather_fwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if i1 is None else i1.on(x1.device)),
+                                  ptr(None if i2 is None else i2.on(x1.device)), P, Q1, Q2, D, ptr(out), ptr(arg), stream())
     return (out, arg) if return_argmax else out

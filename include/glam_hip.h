@@ -587,6 +587,18 @@ int glam_pair_pool_indexed_fwd(const float* mol, const float* pro, const int32_t
                                const int32_t* pro_of_pair, int64_t P, int64_t Q, int D, float* out, int32_t* argmax,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Drug x drug (inference): the fusion with BOTH sides held once and both indexed — pair i takes the rows of segment a = idx1[i] of x1
+ * (ptr1 int32[Q1+1]) and of segment b = idx2[i] of x2 (ptr2 int32[Q2+1]); idx1 / idx2 int32[P], every entry in [0, Q1) / [0, Q2): checked
+ * by the caller, trusted here; either may be NULL = identity (needs Q1 == P / Q2 == P).  out f32[P,2] = [max, mean]; argmax int32[P,2]
+ * (row of x1, row of x2; may be NULL); an empty segment on either side gives 0, 0 and -1, -1.  The max and argmax are bit for bit those of
+ * glam_pair_pool_fwd on physically gathered rows; the mean is the same bits on every run.  One wave per pair, one launch, no workspace
+ * (csrc/pairgather.hip): cut for segments of tens of rows.  D in 1..128, else GLAM_E_UNSUPPORTED.  Forward only.
+ * glam_pair_pool_gather_load_bytes: the width of the loads a call with these matrices uses — 16 (D % 4 == 0 and both matrices 16-byte
+ * aligned), 4 otherwise, 0 for a D outside the table. */
+size_t glam_pair_pool_gather_load_bytes(const float* x1, const float* x2, int D);
+int glam_pair_pool_gather_fwd(const float* x1, const float* x2, const int32_t* ptr1, const int32_t* ptr2, const int32_t* idx1,
+                              const int32_t* idx2, int64_t P, int64_t Q1, int64_t Q2, int D, float* out, int32_t* argmax, void* stream);
+
 /* Training-mode block tails of the reference's DEFAULT configuration (src_1gp/model.py:30-31, run.py:35-37: RReLU activations,
  * Dropout(0.2) in front of every conv) — the same launches as glam_gru_tail_* / glam_bias_res_act_* with two additions:
  *   act = 4: torch.nn.RReLU in training mode, out = y > 0 ? y : a * y with a ~ U(rr_lower, rr_upper) per element;

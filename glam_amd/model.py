@@ -18,7 +18,7 @@ from ._lib import GlamHipError
 from .layer import _None  # noqa: F401
 from .layer import GlobalPool5, GlobalLAPool, Set2Set  # noqa: F401  (resolved from config strings)
 from .layer import LinearBlock, MessageBlock, dot_and_global_pool2, first_node_spec, flat_then_head, following_dropout, prestage_pass
-from .layer import _BatchNorm, _LayerNorm, _PairNorm, dot_and_global_pool2_gather, dot_and_global_pool2_indexed
+from .layer import _BatchNorm, _LayerNorm, _PairNorm, dot_and_global_pool2_gather, dot_and_global_pool2_indexed, dot_and_global_pool2_shared
 
 
 def model_args(args):
@@ -243,6 +243,73 @@ class ArchitectureDTI(torch.nn.Module):
             outp = enc.flat.index_select(0, index.on(enc.flat.device))
             out = self.lin_out1(self.lin_out0(ops.cat_cols([outm, outp] + fusion)))
         return (out, contacts) if return_argmax else out
+
+    # ---- training on shared proteins: the protein tower runs once per DISTINCT protein of the step ----------------------------
+    def _shared_guard(self):
+        slots = (("pro_lin0", self.pro_lin0, _PER_GRAPH_NORMS), ("pro_conv", self.pro_conv, _PER_GRAPH_NORMS),
+                 ("pro_flat", self.pro_flat, _PER_ROW_NORMS))
+        _tower_norms_guard("forward_shared", slots, "protein", "model(data_mol, data_pro)")
+        if self.training:
+            for name, block, _ in slots:
+                if type(block.norm) is _BatchNorm:
+                    raise GlamHipError(f"forward_shared: {name}'s norm _BatchNorm takes its batch statistics over the protein rows of the step, "
+                                       "and in model(data_mol, data_pro) those weigh each protein by how often it is repeated — over "
+                                       "proteins held once they are other statistics: train with model(data_mol, data_pro), or call "
+                                       "forward_shared in eval() (running statistics are per row)")
+
+    def _shared_index(self, pro_of_pair, P, Q, device):
+        if pro_of_pair is not None:
+            return ops.pair_index(pro_of_pair, P, Q)
+        # the defaults are kept per (P, Q, device): the index a later capture of the same step meets already has its device copies
+        cache = self.__dict__.setdefault("_shared_defaults", {})
+        key = (P, Q, str(device))
+        if key not in cache:
+            cache[key] = ops.pair_index(None, P, Q, default="single" if Q == 1 else "identity")
+        return cache[key]
+
+    def forward_shared(self, data_mol, data_pro, pro_of_pair=None):
+        """``model(data_mol, B_pro)`` -> ``[P, out_dim]`` for ``B_pro`` = the proteins ``pro_of_pair`` of ``data_pro`` collated one per
+        ligand — without building ``B_pro``: ``data_pro`` holds ``Q`` DISTINCT protein graphs, the protein tower runs on those, every
+        step's fusion reads their residue rows through the pair -> protein index (``ops.pair_pool_shared``) and ``pro_flat(pro_readout(.))``
+        is gathered by it (``ops.pair_rows``).  Unlike ``screen`` this call has a backward: it trains, with gradients to every parameter
+        of both towers and the head; a protein's gradients are the sums over its pairs, in batch order (no atomics: two runs agree bit
+        for bit).  ``pro_of_pair``: host integers, one per ligand, or a ``PairIndex`` (``ops.pair_index`` — keep ONE across the steps
+        that use it: its device copies are made on the first, eager, visit, and a ``GraphedTrainStep`` capture needs them to exist);
+        ``None`` = ligand i with protein i when ``Q == P``, every ligand with the one protein when ``Q == 1``.
+
+        Contract.  Output and every parameter gradient equal those of ``model(data_mol, B_pro)`` within the fp32 parity bound WHENEVER
+        nothing on the protein side is stochastic or depends on the rest of the batch: ``eval()``, or ``train()`` with ``_None()`` /
+        ``Dropout(0)`` and non-random activations.  In ``train()`` with live Dropout / RReLU on the protein side the noise is drawn ONCE per
+        distinct protein and shared by all its pairs; the reference draws it per copy.  That is another (equally valid) regulariser, not
+        the reference's — which is why this is a call of its own and ``model(data_mol, data_pro)`` is untouched.  Refused, before any
+        launch: the protein-side norms ``encode_proteins`` refuses (``_GraphSizeNorm``; ``_LayerNorm`` / ``_PairNorm`` in ``pro_flat``'s slot),
+        and a protein-side ``_BatchNorm`` while training (batch statistics weigh each protein by how often it is repeated).
+        Always eager by itself (no graphed-call route); inside a ``GraphedTrainStep`` it is captured with the step."""
+        self._shared_guard()
+        nm = getattr(data_mol, "num_graphs", None) or None
+        nq = getattr(data_pro, "num_graphs", None) or None
+        index = None
+        if nm is not None and nq is not None:          # (a collated Batch knows its counts: the index is checked before the first launch)
+            index = self._shared_index(pro_of_pair, nm, nq, data_mol.x.device)
+        msp, psp = ops.segment_ptr(data_mol.batch, nm), ops.segment_ptr(data_pro.batch, nq)
+        if index is None:
+            index = self._shared_index(pro_of_pair, msp.B, psp.B, data_mol.x.device)
+        with ops.weight_scope():
+            prestage_pass((self.mol_lin0, self.mol_conv, data_mol.x, data_mol.edge_attr),
+                          (self.pro_lin0, self.pro_conv, data_pro.x, data_pro.edge_attr))
+            xm = self.mol_lin0(data_mol.x, batch=data_mol.batch)
+            xp = self.pro_lin0(data_pro.x, batch=data_pro.batch)
+            hm, hp, fusion = None, None, []
+            for i in range(self.message_steps):
+                with ops.block_feeds_itself(i + 1 < self.message_steps):
+                    xm, hm = self.mol_conv(xm, data_mol.edge_index, data_mol.edge_attr, h=hm, batch=data_mol.batch)
+                xp, hp = self.pro_conv(xp, data_pro.edge_index, data_pro.edge_attr, h=hp, batch=data_pro.batch)
+                f, xm, xp = dot_and_global_pool2_shared(xm, xp, data_mol.batch, psp, index, with_identity=True)
+                fusion.append(f)
+            outm = self.mol_flat(self.mol_readout(xm, data_mol.batch, nm))
+            outp = ops.pair_rows(self.pro_flat(self.pro_readout(xp, data_pro.batch, nq)), index)
+            out = ops.cat_cols([outm, outp] + fusion)
+            return self.lin_out1(self.lin_out0(out))
 
 
 class DrugEncoding:

@@ -630,14 +630,57 @@ class PairIndex:
     def __init__(self, host, Q):
         self.host, self.P, self.Q = host, int(host.shape[0]), int(Q)
         self._dev = {}
+        self._by_protein = None
 
     def on(self, device):
         device = torch.device(device)
         t = self._dev.get(device)
         if t is None:
-            staged = torch.empty(max(self.P, 1), dtype=torch.int32, pin_memory=True)
-            staged.numpy()[:self.P] = self.host
-            t = self._dev[device] = staged.to(device, non_blocking=True)[:self.P]
+            t = self._dev[device] = _stage_int32(self.host, device, "the pair -> protein index")
+        return t
+
+    def by_protein(self):
+        """The pairs grouped by protein, for the sums of the training call (``ops.pair_pool_shared`` / ``ops.pair_rows``): ``order`` int32
+        ``[P]`` — the stable argsort of the index (the pairs of a protein keep their batch order) — and ``ptr`` int32 ``[Q + 1]``, the
+        offsets of the proteins' runs in it.  Built once, on the host; ``.on(device)`` -> their device copies, made once per device."""
+        if self._by_protein is None:
+            self._by_protein = PairsByProtein(self.host, self.Q)
+        return self._by_protein
+
+
+def _stage_int32(host, device, what):
+    """Device copy of a host int32 vector out of pinned memory (only enqueued).  Not inside a hipGraph capture: the copy would be baked
+    into the graph and the pinned buffer allocated under it — the eager first visit of a batch makes the copies a capture then finds."""
+    if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        raise GlamHipError(f"{what} has no copy on {device} yet and a hipGraph capture cannot make one: keep ONE PairIndex across the "
+                           "steps (ops.pair_index) and run the first step on it eagerly, as GraphedTrainStep does")
+    n = int(host.shape[0])
+    staged = torch.empty(max(n, 1), dtype=torch.int32, pin_memory=True)
+    staged.numpy()[:n] = host
+    return staged.to(device, non_blocking=True)[:n]
+
+
+class PairsByProtein:
+    """``order`` / ``ptr`` of ``PairIndex.by_protein`` (host, int32 numpy) and their device copies."""
+
+    def __init__(self, host, Q):
+        P, Q = int(host.shape[0]), int(Q)
+        if P and (int(host.min()) < 0 or int(host.max()) >= Q):
+            raise IndexError(f"the pair -> protein index must lie in [0, {Q})")
+        self.order = np.argsort(host, kind="stable").astype(np.int32)
+        self.ptr = np.zeros(Q + 1, dtype=np.int32)
+        np.cumsum(np.bincount(host, minlength=Q)[:Q], out=self.ptr[1:])
+        if int(self.ptr[-1]) != P:
+            raise IndexError("the pair -> protein index does not sort into its proteins' runs")
+        self.P, self.Q = P, Q
+        self._dev = {}
+
+    def on(self, device):
+        device = torch.device(device)
+        t = self._dev.get(device)
+        if t is None:
+            both = _stage_int32(np.concatenate([self.order, self.ptr]), device, "the pair list by protein")      # (one copy)
+            t = self._dev[device] = (both[:self.P], both[self.P:])
         return t
 
 
@@ -702,6 +745,113 @@ def pair_pool_indexed(mol_out, pro_out, msp, psp, pro_of_pair=None, return_argma
     lib.glam_pair_pool_indexed_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(index.on(mol.device)), P, Q, D, ptr(out), ptr(arg),
                                    ptr(ws), ws.numel(), stream())
     return (out, arg) if return_argmax else out
+
+
+# --------------------------------------------------------------------------------------
+# training against proteins held once: the indexed fusion with a backward (csrc/pairshared.hip)
+# --------------------------------------------------------------------------------------
+class _PairPoolShared(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mol, pro, msp, psp, index, with_identity=False):
+        mol_in, pro_in = mol, pro
+        mol, pro = f32c(mol, "mol_out"), f32c(pro, "pro_out")
+        P, Q, D, dev = msp.B, psp.B, mol.size(1), mol.device
+        pidx = index.on(dev)
+        order, qptr = index.by_protein().on(dev)
+        out = torch.empty(P, 2, dtype=torch.float32, device=dev)
+        arg = torch.empty(P, 2, dtype=torch.int32, device=dev)
+        sums = torch.empty(P, 2, D, dtype=torch.float32, device=dev)
+        lib = _lib.api()
+        ws = torch.empty(max(lib.glam_pair_pool_workspace_bytes(P, D), 16), dtype=torch.uint8, device=dev)
+        lib.glam_pair_pool_shared_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(pidx), P, Q, D, ptr(out), ptr(arg), ptr(sums),
+                                      ptr(ws), ws.numel(), stream())
+        ctx.save_for_backward(mol, pro, arg, sums, pidx, order, qptr)
+        ctx.sps = (msp, psp)
+        ctx.aliased = bool(with_identity)
+        if ctx.aliased:      # (as _PairPool: what the caller does with the two matrices next sends its gradient HERE)
+            ctx.set_materialize_grads(False)
+            return out, mol_in.view_as(mol_in), pro_in.view_as(pro_in)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, d_ma=None, d_pa=None):
+        mol, pro, arg, sums, pidx, order, qptr = ctx.saved_tensors
+        msp, psp = ctx.sps
+        if d_out is None:
+            return d_ma, d_pa, None, None, None, None
+        d_out = f32c(d_out, "d_out")
+        d_ma = None if d_ma is None else f32c(d_ma, "d_mol (next use)")
+        d_pa = None if d_pa is None else f32c(d_pa, "d_pro (next use)")
+        if msp.B == 0:       # no pair: the entry point writes nothing
+            d_mol = torch.zeros_like(mol) if d_ma is None else d_ma
+            d_pro = torch.zeros_like(pro) if d_pa is None else d_pa
+            return d_mol, d_pro, None, None, None, None
+        d_mol, d_pro = torch.empty_like(mol), torch.empty_like(pro)
+        _lib.api().glam_pair_pool_shared_bwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(pidx), ptr(order), ptr(qptr), ptr(arg),
+                                             ptr(sums), ptr(d_out), msp.B, psp.B, mol.size(1), ptr(d_ma), ptr(d_pa), ptr(d_mol),
+                                             ptr(d_pro), stream())
+        return d_mol, d_pro, None, None, None, None
+
+
+def pair_pool_shared(mol_out, pro_out, msp, psp, pro_of_pair=None, with_identity=False):
+    """``pair_pool_indexed`` WITH a backward: ``[max, mean]`` of ``mol[seg_i] @ pro[seg_q].T`` with ``q = pro_of_pair[i]`` -> ``[P, 2]``
+    against proteins held once (``psp.B`` segments), for training.  The forward is bit for bit ``pair_pool_indexed``; the gradient of a
+    protein's residue rows is the sum over every pair that points at it, taken in batch order without atomics (two runs are
+    bit-equal); a protein no pair references gets zeros.  ``pro_of_pair``: see ``pair_index`` (``None`` = identity; every ligand against
+    the one protein when ``psp.B == 1``).  ``with_identity``:
+    as ``pair_pool`` — ``(out, mol_out, pro_out)`` with the two matrices handed back through the node where its backward launch can
+    add their later gradients itself (``glam_pair_pool_add_supported``), the plain triple otherwise."""
+    P, Q = msp.B, psp.B
+    index = pair_index(pro_of_pair, P, Q, default="single" if Q == 1 and P != 1 else "identity")
+    require_device(mol_out, pro_out)
+    if (mol_out.dim() != 2 or pro_out.dim() != 2 or mol_out.size(1) != pro_out.size(1) or mol_out.size(0) != msp.N
+            or pro_out.size(0) != psp.N):
+        raise GlamHipError("pair_pool_shared: the two batches disagree (width / node count)")
+    if with_identity:
+        D = mol_out.size(1)
+        if (torch.is_grad_enabled() and mol_out.requires_grad and pro_out.requires_grad and mol_out.dtype == torch.float32
+                and pro_out.dtype == torch.float32 and _lib.api().glam_pair_pool_add_supported(D) == 1):
+            return _PairPoolShared.apply(mol_out, pro_out, msp, psp, index, True)
+        return _PairPoolShared.apply(mol_out, pro_out, msp, psp, index), mol_out, pro_out
+    return _PairPoolShared.apply(mol_out, pro_out, msp, psp, index)
+
+
+class _PairRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flat, index):
+        pidx = index.on(flat.device)
+        order, qptr = index.by_protein().on(flat.device)
+        ctx.save_for_backward(order, qptr)
+        ctx.dims = (index.P, index.Q, tuple(flat.shape[1:]))
+        return flat.index_select(0, pidx)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_rows):
+        order, qptr = ctx.saved_tensors
+        P, Q, tail = ctx.dims
+        d_rows = f32c(d_rows, "d_rows")
+        W = int(np.prod(tail, dtype=np.int64))
+        if P == 0 or W == 0:
+            return torch.zeros((Q,) + tail, dtype=torch.float32, device=d_rows.device), None
+        d_flat = torch.empty((Q,) + tail, dtype=torch.float32, device=d_rows.device)
+        _lib.api().glam_pair_rows_bwd(ptr(d_rows), ptr(order), ptr(qptr), P, Q, W, ptr(d_flat), stream())
+        return d_flat, None
+
+
+def pair_rows(flat, index):
+    """``flat[index]`` -> ``[P, ...]``: the rows of a matrix that holds every protein once, one per pair (``index``: a ``PairIndex`` or
+    what ``pair_index`` accepts, over ``flat.size(0)`` rows).  Its backward sums the pairs' rows per protein in batch order
+    (``glam_pair_rows_bwd``): ``index_select``'s own backward is an atomic ``index_add``, whose bits change from run to run."""
+    if not isinstance(index, PairIndex):
+        index = pair_index(index, len(index), flat.size(0))
+    elif index.Q != flat.size(0):
+        raise IndexError(f"pair_rows: the index was validated over {index.Q} rows, the matrix has {flat.size(0)}")
+    require_device(flat)
+    if flat.dtype != torch.float32:
+        raise GlamHipError(f"pair_rows: expected float32, got {flat.dtype}")
+    return _PairRows.apply(flat, index)
 
 
 # --------------------------------------------------------------------------------------

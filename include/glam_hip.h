@@ -587,6 +587,28 @@ int glam_pair_pool_indexed_fwd(const float* mol, const float* pro, const int32_t
                                const int32_t* pro_of_pair, int64_t P, int64_t Q, int D, float* out, int32_t* argmax,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Training against proteins held once (csrc/pairshared.hip): glam_pair_pool_indexed_fwd that ALWAYS writes argmax int32[P,2] (row of mol,
+ * row of pro; -1, -1 for an empty pair) and sums f32[P,2,D] (column sum of the pair's ligand rows, column sum of its protein's residue
+ * rows).  out and argmax are bit for bit those of glam_pair_pool_indexed_fwd on the same inputs. */
+int glam_pair_pool_shared_fwd(const float* mol, const float* pro, const int32_t* mol_ptr, const int32_t* pro_ptr,
+                              const int32_t* pro_of_pair, int64_t P, int64_t Q, int D, float* out, int32_t* argmax, float* sums,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* ... and its backward, one launch.  pair_order int32[P]: the pairs stably sorted by protein; pair_ptr int32[Q+1]: the offsets of the
+ * proteins' runs in it (both built and checked by the caller, trusted here).  With gmean_i = d_out[i,1] / (n_mol n_res):
+ *   d_mol, rows of pair i:  gmean_i * psum_i, + gmax_i * pro[ap_i] on row am_i (the expression of glam_pair_pool_bwd), + add_mol last.
+ *   d_pro, every row b of every protein q (referenced or not):  0, + gmean_i * msum_i for the pairs i of q in pair_order order, then
+ *          fmaf(gmax_i, mol[am_i], .) for the pairs of q with ap_i == b in the same order, + add_pro last.
+ * Empty pairs contribute nothing.  No atomics: the order of every sum depends on pair_order alone, two runs are bit-equal.
+ * add_mol / add_pro may be NULL.  D in 1..256. */
+int glam_pair_pool_shared_bwd(const float* mol, const float* pro, const int32_t* mol_ptr, const int32_t* pro_ptr,
+                              const int32_t* pro_of_pair, const int32_t* pair_order, const int32_t* pair_ptr, const int32_t* argmax,
+                              const float* sums, const float* d_out, int64_t P, int64_t Q, int D, const float* add_mol,
+                              const float* add_pro, float* d_mol, float* d_pro, void* stream);
+/* d_flat f32[Q,W]: row q = the sum of the rows d_rows[i] (f32[P,W]) of q's pairs in pair_order order — the backward of gathering a
+ * [Q, W] matrix by pair, without the atomics of an index_add (same bits on every run).  P == 0: nothing is written. */
+int glam_pair_rows_bwd(const float* d_rows, const int32_t* pair_order, const int32_t* pair_ptr, int64_t P, int64_t Q, int W,
+                       float* d_flat, void* stream);
+
 /* Drug x drug (inference): the fusion with BOTH sides held once and both indexed — pair i takes the rows of segment a = idx1[i] of x1
  * (ptr1 int32[Q1+1]) and of segment b = idx2[i] of x2 (ptr2 int32[Q2+1]); idx1 / idx2 int32[P], every entry in [0, Q1) / [0, Q2): checked
  * by the caller, trusted here; either may be NULL = identity (needs Q1 == P / Q2 == P).  out f32[P,2] = [max, mean]; argmax int32[P,2]

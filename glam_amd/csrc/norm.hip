@@ -433,13 +433,19 @@ static int norm_dims(const char* fn, int64_t N, int64_t B, int D, int mode) {
     return GLAM_OK;
 }
 
+// The float4 forms (wave per graph, block per graph) need D % 4 == 0, D <= 64 and every row pointer on a 16-byte boundary (ld4 / st4);
+// a contiguous view at a 4-byte storage offset takes the generic kernel, which serves every D <= 256.  A null pointer is aligned.
+template <class... P>
+static bool norm_v4(int D, const P*... p) { return (D & 3) == 0 && D <= 64 && (aligned16(p) && ...); }
+
 extern "C" int glam_graph_norm_fwd(const float* x, const int32_t* ptr, int64_t N, int64_t B, int D, int mode, float scale,
                                    float eps, float* y, void* stream) {
     if (int rc = norm_dims("glam_graph_norm_fwd", N, B, D, mode)) return rc;
     if (N == 0 || B == 0) return GLAM_OK;
     GLAM_REQUIRE(x && ptr && y, "glam_graph_norm_fwd: null pointer");
     const dim3 block(kBlock);
-    if (N / B >= 64 && (D & 3) == 0 && D <= 64) {       // large graphs: a block per graph
+    const bool v4 = norm_v4(D, x, y);
+    if (N / B >= 64 && v4) {       // large graphs: a block per graph
         const dim3 grid(grid_for(B, 1));
         if (mode == 0) hipLaunchKernelGGL(k_graph_norm_fwd_block<0>, grid, block, 0, (hipStream_t)stream, x, ptr, (int)B, D, scale, eps, y);
         else hipLaunchKernelGGL(k_graph_norm_fwd_block<1>, grid, block, 0, (hipStream_t)stream, x, ptr, (int)B, D, scale, eps, y);
@@ -447,7 +453,7 @@ extern "C" int glam_graph_norm_fwd(const float* x, const int32_t* ptr, int64_t N
         return GLAM_OK;
     }
     const dim3 grid(grid_for(B, kWavesPerBlockN));
-    if ((D & 3) == 0 && D <= 64) {
+    if (v4) {
         if (mode == 0) hipLaunchKernelGGL((k_graph_norm_fwd_v4<0, false>), grid, block, 0, (hipStream_t)stream, x, ptr, (int)B, D, scale, eps, y, NormDrop{});
         else hipLaunchKernelGGL((k_graph_norm_fwd_v4<1, false>), grid, block, 0, (hipStream_t)stream, x, ptr, (int)B, D, scale, eps, y, NormDrop{});
     } else if (mode == 0) hipLaunchKernelGGL(k_graph_norm_fwd<0>, grid, block, 0, (hipStream_t)stream, x, ptr, (int)B, D, scale, eps, y);
@@ -461,9 +467,9 @@ static int graph_norm_bwd_impl(const float* x, const float* gy, const int32_t* p
     if (int rc = norm_dims("glam_graph_norm_bwd", N, B, D, mode)) return rc;
     if (N == 0 || B == 0) return GLAM_OK;
     GLAM_REQUIRE(x && gy && ptr && dx, "glam_graph_norm_bwd: null pointer");
-    GLAM_REQUIRE(!addend || (D & 3) || aligned16(addend), "glam_graph_norm_bwd_add: addend must be 16-byte aligned");
     const dim3 block(kBlock);
-    if (N / B >= 64 && (D & 3) == 0 && D <= 64) {
+    const bool v4 = norm_v4(D, x, gy, dx, addend);
+    if (N / B >= 64 && v4) {
         const dim3 grid(grid_for(B, 1));
         if (mode == 0) hipLaunchKernelGGL(k_graph_norm_bwd_block<0>, grid, block, 0, (hipStream_t)stream, x, gy, ptr, (int)B, D, scale, eps, dx, addend);
         else hipLaunchKernelGGL(k_graph_norm_bwd_block<1>, grid, block, 0, (hipStream_t)stream, x, gy, ptr, (int)B, D, scale, eps, dx, addend);
@@ -471,7 +477,7 @@ static int graph_norm_bwd_impl(const float* x, const float* gy, const int32_t* p
         return GLAM_OK;
     }
     const dim3 grid(grid_for(B, kWavesPerBlockN));
-    if ((D & 3) == 0 && D <= 64) {
+    if (v4) {
         if (mode == 0) hipLaunchKernelGGL((k_graph_norm_bwd_v4<0, false>), grid, block, 0, (hipStream_t)stream, x, gy, ptr, (int)B, D, scale, eps, dx, addend, NormDropB{});
         else hipLaunchKernelGGL((k_graph_norm_bwd_v4<1, false>), grid, block, 0, (hipStream_t)stream, x, gy, ptr, (int)B, D, scale, eps, dx, addend, NormDropB{});
     } else if (mode == 0) hipLaunchKernelGGL(k_graph_norm_bwd<0>, grid, block, 0, (hipStream_t)stream, x, gy, ptr, (int)B, D, scale, eps, dx, addend);

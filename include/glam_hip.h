@@ -490,7 +490,8 @@ int glam_gru_gates_bwd(const float* gi, const float* gh, const float* h, const f
  * Replaces: PyG PairNorm()(x, batch) behind _PairNorm (src_1gp/layer.py:179-185; mode 0, scale 1, eps 1e-5) and the
  * statistics of PyG's graph LayerNorm(x, batch) behind _LayerNorm (src_1gp/layer.py:170-176; mode 1: y = (x - mean) /
  * sqrt(var + eps) over all nodes x channels of a graph; the per-channel affine stays in the host mirror).
- * D <= 256.  The backward pass recomputes the statistics from x. */
+ * D <= 256.  The backward pass recomputes the statistics from x.  Any 4-byte-aligned pointers: the float4 kernel forms (D % 4 == 0,
+ * D <= 64) are taken when every tensor sits on a 16-byte boundary, the generic kernel otherwise. */
 int glam_graph_norm_fwd(const float* x, const int32_t* ptr, int64_t N, int64_t B, int D, int mode, float scale, float eps,
                         float* y, void* stream);
 int glam_graph_norm_bwd(const float* x, const float* gy, const int32_t* ptr, int64_t N, int64_t B, int D, int mode,

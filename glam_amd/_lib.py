@@ -209,6 +209,8 @@ SIGNATURES = {
     "glam_collate_lds_slots": (_sz, []),
     "glam_collate": (_i32, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
     "glam_collate_padded": (_i32, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "glam_collate_padded_split": (_i32, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
+                                         _vp]),
 }
 
 # An ``int`` return is a status (0 = ok, < 0 = GLAM_E_*) that api() checks — the default, so that a new entry point is safe without

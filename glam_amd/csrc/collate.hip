@@ -162,13 +162,18 @@ __global__ void __launch_bounds__(kBlock) k_collate(const CollateArgs a) {
 // q + (p < rem) of them from E + p * q + min(p, rem) on (q = E_pad / P, rem = E_pad % P): both CSR orders of the padded edge list are
 // then the real ones followed by the runs, an edge's id its own position.  Phantom x rows are zero, phantom edge_attr rows copies of
 // the dataset's edge row 0 (it carries whatever one-hot mark the dataset has), so every phantom activation is finite.
+// glam_collate_padded_split cuts the phantom nodes into K phantom graphs by the same divmod: graph j owns s + (j < r) consecutive nodes
+// from N + j * s + min(j, r) on (s = P / K, r = P % K), so batch and ptr are closed forms of p and j and the edge runs, which are per
+// node, do not move.  K = 1 is the single phantom graph: owner 0 for every p, ptr[B + 1] = N + P.
 struct CollatePadArgs {
     CollateArgs c;              // (c.N / c.E / c.Y are not read: the totals come from the table)
     int N_cap, E_cap;
+    int K;                      // phantom graphs (>= 1; the caller guarantees K <= P, so none is empty)
     int xwo;                    // units per OUTPUT row of x (>= c.xw; the pad units are written as zero)
 };
 
-// phantom node (0-based) that owns phantom edge j, for runs of q + (p < rem) edges
+// phantom node (0-based) that owns phantom edge j, for runs of q + (p < rem) edges — and, over nodes, the phantom graph that owns phantom
+// node j for graphs of q + (g < rem) nodes
 __device__ __forceinline__ int phantom_owner(int j, int q, int rem) {
     const int head = rem * (q + 1);
     return j < head ? j / (q + 1) : rem + (j - head) / q;      // (j >= head only where q >= 1: j < E_pad = head + (P - rem) * q)
@@ -205,6 +210,7 @@ __global__ void __launch_bounds__(kBlock) k_collate_padded(const CollatePadArgs 
     const int N = tn.off[B], E = te.off[B], Y = ty.off[B];
     const int P = pa.N_cap - N, E_pad = pa.E_cap - E;            // (the caller guarantees P >= 1, E_pad >= 0)
     const int q = P > 0 ? E_pad / P : 0, rem = P > 0 ? E_pad % P : 0;
+    const int gs = P > 0 ? P / pa.K : 0, gr = P > 0 ? P % pa.K : 0;  // (phantom graph j: gs + (j < gr) nodes; gs >= 1 as K <= P)
     for (int item = blockIdx.x; item < a.first[6]; item += gridDim.x) {
         int s = 0;
         while (item >= a.first[s + 1]) ++s;                  // (block-uniform)
@@ -258,7 +264,7 @@ __global__ void __launch_bounds__(kBlock) k_collate_padded(const CollatePadArgs 
                 } else {                                     // phantom node: its run of self-loops, the same by target and by source
                     const int p = idx - N;
                     const int start = E + p * q + min(p, rem), len = q + (p < rem);
-                    a.obatch[idx] = B;
+                    a.obatch[idx] = B + phantom_owner(p, gs, gr);
                     a.orowptr[idx] = start;
                     a.ocolptr[idx] = start;
                     const int4 nodes = make_int4(len > 0 ? idx : -1, len > 1 ? idx : -1, len > 2 ? idx : -1, len > 3 ? idx : -1);
@@ -287,9 +293,10 @@ __global__ void __launch_bounds__(kBlock) k_collate_padded(const CollatePadArgs 
                     a.odst[idx] = node;
                     a.oeid_t[idx] = idx;
                 }
-            } else {                                         // slots: the B real graphs, the phantom graph [N, N_cap)
-                if (idx > B + 1) break;
-                const int v = idx <= B ? a.node_off[idx] : pa.N_cap;
+            } else {                                         // slots: the B real graphs, then the K phantom graphs that cut [N, N_cap)
+                if (idx > B + pa.K) break;
+                const int j = idx - B;
+                const int v = j <= 0 ? a.node_off[idx] : N + j * gs + min(j, gr);
                 a.optr64[idx] = v;
                 a.optr32[idx] = v;
             }
@@ -370,12 +377,15 @@ extern "C" int glam_collate(const void* const* ds_host, void* const* out_host, c
     return GLAM_OK;
 }
 
-extern "C" int glam_collate_padded(const void* const* ds_host, void* const* out_host, const int32_t* table, int64_t B, int64_t N_cap,
-                                   int64_t E_cap, int64_t y_rows, int64_t Ed, int32_t x_row_bytes, int32_t x_out_stride_bytes,
-                                   int32_t ea_row_bytes, int32_t y_row_bytes, void* stream) {
+// both entry points of the fixed-capacity collate: K phantom graphs (glam_collate_padded is K = 1)
+static int collate_padded(const void* const* ds_host, void* const* out_host, const int32_t* table, int64_t B, int64_t K, int64_t N_cap,
+                          int64_t E_cap, int64_t y_rows, int64_t Ed, int32_t x_row_bytes, int32_t x_out_stride_bytes,
+                          int32_t ea_row_bytes, int32_t y_row_bytes, void* stream) {
     GLAM_REQUIRE(ds_host && out_host && table, "glam_collate_padded: null pointer (ds_host / out_host / table)");
     GLAM_REQUIRE(B >= 1 && N_cap >= 1 && E_cap >= 0 && Ed >= 0 && B < INT32_MAX - 1 && N_cap < INT32_MAX && E_cap < INT32_MAX && Ed < INT32_MAX,
                  "glam_collate_padded: B / N_cap / E_cap / Ed out of range (B >= 1, N_cap >= 1 for the phantom node, all below 2^31 - 1)");
+    GLAM_REQUIRE(K >= 1 && K <= N_cap && B + K < INT32_MAX - 1,
+                 "glam_collate_padded: K out of range (1 <= K <= N_cap: every phantom graph owns a node; B + K below 2^31 - 1)");
     GLAM_REQUIRE(x_row_bytes >= 0 && ea_row_bytes >= 0 && y_row_bytes >= 0 && ((x_row_bytes | ea_row_bytes | y_row_bytes) & 3) == 0,
                  "glam_collate_padded: row sizes must be multiples of 4 bytes");
     GLAM_REQUIRE(x_out_stride_bytes >= x_row_bytes && x_out_stride_bytes % 16 == 0,
@@ -411,7 +421,7 @@ extern "C" int glam_collate_padded(const void* const* ds_host, void* const* out_
     a.orowptr = (int*)o[7]; a.osrc = (int*)o[8]; a.oeid = (int*)o[9]; a.ocolptr = (int*)o[10]; a.odst = (int*)o[11]; a.oeid_t = (int*)o[12];
     a.oell_src = (int4*)o[13]; a.oell_eid = (int4*)o[14]; a.oell_dst = (int4*)o[15]; a.oell_eid_t = (int4*)o[16];
     a.B = (int)B; a.Ed = (int)Ed;
-    pa.N_cap = (int)N_cap; pa.E_cap = (int)E_cap;
+    pa.N_cap = (int)N_cap; pa.E_cap = (int)E_cap; pa.K = (int)K;
     // units as in glam_collate; the output rows of x are whole 16-byte units by contract, so x moves as units where its input rows are
     const int Y = has_y ? (int)(B * y_rows) : 0;
     a.xvec = x_row_bytes > 0 && x_row_bytes % 16 == 0 && aligned16(d[0]);
@@ -421,7 +431,7 @@ extern "C" int glam_collate_padded(const void* const* ds_host, void* const* out_
     a.eaw = ea_row_bytes / (a.eavec ? 16 : 4);
     a.yvec = has_y && y_row_bytes % 16 == 0 && aligned16(d[3]) && aligned16(o[3]);
     a.yw = has_y ? y_row_bytes / (a.yvec ? 16 : 4) : 0;
-    const int64_t count[6] = {x_row_bytes > 0 ? N_cap * pa.xwo : 0, o[2] ? E_cap * a.eaw : 0, (int64_t)Y * a.yw, N_cap + 1, E_cap, B + 2};
+    const int64_t count[6] = {x_row_bytes > 0 ? N_cap * pa.xwo : 0, o[2] ? E_cap * a.eaw : 0, (int64_t)Y * a.yw, N_cap + 1, E_cap, B + K + 1};
     int64_t items = 0;
     for (int s = 0; s < 6; ++s) {
         if (count[s] >= INT32_MAX - kCollateItem) return fail(GLAM_E_UNSUPPORTED, "glam_collate_padded: a field of the batch has 2^31 elements or more");
@@ -434,4 +444,18 @@ extern "C" int glam_collate_padded(const void* const* ds_host, void* const* out_
     else hipLaunchKernelGGL(k_collate_padded<false>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, pa);
     GLAM_LAUNCH_CHECK("glam_collate_padded");
     return GLAM_OK;
+}
+
+extern "C" int glam_collate_padded(const void* const* ds_host, void* const* out_host, const int32_t* table, int64_t B, int64_t N_cap,
+                                   int64_t E_cap, int64_t y_rows, int64_t Ed, int32_t x_row_bytes, int32_t x_out_stride_bytes,
+                                   int32_t ea_row_bytes, int32_t y_row_bytes, void* stream) {
+    return collate_padded(ds_host, out_host, table, B, 1, N_cap, E_cap, y_rows, Ed, x_row_bytes, x_out_stride_bytes, ea_row_bytes, y_row_bytes,
+                          stream);
+}
+
+extern "C" int glam_collate_padded_split(const void* const* ds_host, void* const* out_host, const int32_t* table, int64_t B, int64_t K,
+                                         int64_t N_cap, int64_t E_cap, int64_t y_rows, int64_t Ed, int32_t x_row_bytes,
+                                         int32_t x_out_stride_bytes, int32_t ea_row_bytes, int32_t y_row_bytes, void* stream) {
+    return collate_padded(ds_host, out_host, table, B, K, N_cap, E_cap, y_rows, Ed, x_row_bytes, x_out_stride_bytes, ea_row_bytes, y_row_bytes,
+                          stream);
 }

@@ -220,46 +220,95 @@ def resident_table(ids, ns, es, y_rows):
     return table.astype(np.int32), int(table[1, B]), int(table[2, B]), int(table[3, B])
 
 
-def padded_capacity(ns, es, batch_size, ell):
+def _phantom_rows(phantom_rows):
+    m = int(phantom_rows)
+    if m != phantom_rows or m < 1:
+        raise ValueError(f"phantom_rows bounds the nodes of a phantom graph: an integer >= 1 or None, got {phantom_rows!r}")
+    return m
+
+
+def _top(v, B):
+    return int(np.partition(v, v.size - B)[v.size - B:].sum())
+
+
+def _bottom(v, B):
+    return int(np.partition(v, B - 1)[:B].sum())
+
+
+def phantom_graphs(ns, batch_size, n_cap, phantom_rows):
+    """``K``, the number of phantom graphs of a bucket of ``n_cap`` nodes: 1 for ``phantom_rows = None`` (the single phantom graph), else the
+    fewest graphs of at most ``phantom_rows`` nodes that hold the largest surplus any ``batch_size`` distinct graphs leave,
+    ``ceil((n_cap - botB(ns)) / phantom_rows)`` with ``botB`` = the sum of the ``batch_size`` smallest entries."""
+    if phantom_rows is None:
+        return 1
+    ns = np.asarray(ns, dtype=np.int64)
+    return max(1, -(-(int(n_cap) - _bottom(ns, int(batch_size))) // _phantom_rows(phantom_rows)))
+
+
+def padded_capacity(ns, es, batch_size, ell, phantom_rows=None):
     """``(N_cap, E_cap)`` of a fixed-capacity batch (``DeviceDataset.padded``) that holds ANY ``batch_size`` distinct graphs of a dataset
     with per-graph node / edge counts ``ns`` / ``es`` (host numpy).  ``topB(v)`` = the sum of the ``batch_size`` largest entries of ``v``:
     ``E_cap = topB(es)``, ``N_cap = topB(ns) + 1`` — one phantom node at least.  ``ell``: the batch carries an ELL form (in- or out-degree
     <= 4 per node), which the phantom nodes must keep: ``N_cap >= ceil((E_cap + topB(4 ns - es)) / 4)`` gives, for every such set S,
-    ``4 (N_cap - N(S)) - (E_cap - E(S)) = 4 N_cap - E_cap - sum_S (4 n - e) >= 4 N_cap - E_cap - topB(4 ns - es) >= 0``."""
+    ``4 (N_cap - N(S)) - (E_cap - E(S)) = 4 N_cap - E_cap - sum_S (4 n - e) >= 4 N_cap - E_cap - topB(4 ns - es) >= 0``.
+
+    ``phantom_rows = m``: the surplus ``P = N_cap - N(S)`` is cut into ``K`` phantom graphs of ``1 .. m`` nodes each, so ``K <= P <= K m`` for
+    every S: ``N_cap = max(topB(ns) + K, the ELL term)`` gives ``P >= N_cap - topB(ns) >= K``, and ``K`` is the smallest integer with
+    ``K m >= N_cap - botB(ns) >= P`` — found by iterating ``K <- ceil((N_cap(K) - botB(ns)) / m)`` from 1, which climbs to the least fixed
+    point.  ``phantom_graphs(ns, batch_size, N_cap, m)`` gives that ``K`` back.  ``ValueError`` for ``m = 1`` over graphs of unequal sizes
+    (``K >= topB - botB + K`` has no solution)."""
     ns, es = np.asarray(ns, dtype=np.int64), np.asarray(es, dtype=np.int64)
     B = int(batch_size)
     if not 1 <= B <= ns.size:
         raise ValueError(f"padded batches hold 1 .. {ns.size} distinct graphs of this dataset, got batch_size = {batch_size}")
-    top = lambda v: int(np.partition(v, v.size - B)[v.size - B:].sum())     # noqa: E731
-    e_cap, n_cap = top(es), top(ns) + 1
-    if ell:
-        n_cap = max(n_cap, -(-(e_cap + top(4 * ns - es)) // 4))
-    return n_cap, e_cap
+    e_cap, n_top = _top(es, B), _top(ns, B)
+    n_ell = -(-(e_cap + _top(4 * ns - es, B)) // 4) if ell else 0
+    if phantom_rows is None:
+        return max(n_top + 1, n_ell), e_cap
+    m = _phantom_rows(phantom_rows)
+    if m == 1 and n_top != _bottom(ns, B):
+        raise ValueError(f"phantom_rows = 1 gives every surplus node a graph of its own, which one fixed count of phantom graphs can do "
+                         f"only where every {B} graphs have the same node count; here it ranges over {_bottom(ns, B)} .. {n_top}")
+    K = 1
+    while True:
+        n_cap = max(n_top + K, n_ell)
+        need = phantom_graphs(ns, B, n_cap, m)
+        if need <= K:
+            return n_cap, e_cap
+        K = need
 
 
-def padded_bucket(ns, es, y_rows, batch_size, capacity, ell):
+def padded_bucket(ns, es, y_rows, batch_size, capacity, ell, phantom_rows=None):
     """The checked ``(N_cap, E_cap, r)`` of ``DeviceDataset.padded``: ``capacity`` (or ``padded_capacity``) and the one constant count of
     ``y`` rows per graph.  ``ValueError`` for ``y`` rows that differ between graphs or are absent, and for a capacity that the dataset's
-    largest graph does not fit with one phantom node beside it."""
+    largest graph does not fit with one phantom node beside it — with ``phantom_rows``, one node for each of the
+    ``phantom_graphs(ns, batch_size, N_cap, phantom_rows)`` phantom graphs."""
     y_rows = np.asarray(y_rows, dtype=np.int64)
     r = int(y_rows[0]) if y_rows.size else 0
     if r < 1 or bool((y_rows != r).any()):
         raise ValueError("padded batches need the same number (>= 1) of y rows for every graph: the loss reads output[:B] against y[B * r]")
-    n_cap, e_cap = padded_capacity(ns, es, batch_size, ell) if capacity is None else (int(capacity[0]), int(capacity[1]))
-    if n_cap - 1 < int(np.max(ns)) or e_cap < int(np.max(es)) or max(n_cap, e_cap) >= 2 ** 31 - 1:
-        raise ValueError(f"capacity ({n_cap}, {e_cap}) does not hold the dataset's largest graph ({int(np.max(ns))} nodes + 1 phantom node, "
-                         f"{int(np.max(es))} edges) or exceeds int32")
+    n_cap, e_cap = padded_capacity(ns, es, batch_size, ell, phantom_rows) if capacity is None else (int(capacity[0]), int(capacity[1]))
+    if phantom_rows is not None and not 1 <= int(batch_size) <= np.size(ns):
+        raise ValueError(f"padded batches hold 1 .. {np.size(ns)} distinct graphs of this dataset, got batch_size = {batch_size}")
+    K = phantom_graphs(ns, batch_size, n_cap, phantom_rows)
+    if n_cap - K < int(np.max(ns)) or e_cap < int(np.max(es)) or max(n_cap, e_cap) >= 2 ** 31 - 1:
+        raise ValueError(f"capacity ({n_cap}, {e_cap}) does not hold the dataset's largest graph ({int(np.max(ns))} nodes + "
+                         f"{'1 phantom node' if K == 1 else f'{K} phantom nodes, one per phantom graph'}, {int(np.max(es))} edges) or exceeds int32")
     return n_cap, e_cap, r
 
 
-def padded_fit(batch_size, B, N, E, n_cap, e_cap, ell):
+def padded_fit(batch_size, B, N, E, n_cap, e_cap, ell, phantoms=1, phantom_rows=None):
     """``ValueError`` unless a table of ``B`` slots with ``N`` nodes and ``E`` edges fits the bucket ``(batch_size, n_cap, e_cap)``: one
     phantom node at least, and phantom degrees <= 4 where the batch carries an ELL form.  Distinct ids always fit the capacity of
-    ``padded_capacity``; repeated ids may not."""
+    ``padded_capacity``; repeated ids may not.  With ``phantoms = K`` graphs of at most ``phantom_rows`` nodes the surplus must satisfy
+    ``K <= n_cap - N <= K * phantom_rows``: no phantom graph empty, none above the bound."""
     if B != batch_size:
         raise ValueError(f"this padded batch holds exactly {batch_size} graphs, got {B} ids")
-    if N > n_cap - 1 or E > e_cap:
-        raise ValueError(f"{N} nodes / {E} edges exceed the capacity ({n_cap} nodes, one of them phantom, {e_cap} edges): repeated ids?")
+    if N > n_cap - phantoms or E > e_cap:
+        raise ValueError(f"{N} nodes / {E} edges exceed the capacity ({n_cap} nodes, {'one' if phantoms == 1 else phantoms} of them phantom, "
+                         f"{e_cap} edges): repeated ids?")
+    if phantom_rows is not None and n_cap - N > phantoms * phantom_rows:
+        raise ValueError(f"{n_cap - N} surplus nodes exceed the {phantoms} phantom graphs of {phantom_rows} nodes of this bucket: repeated ids?")
     if ell and 4 * (n_cap - N) < e_cap - E:
         raise ValueError(f"{e_cap - E} surplus edges on {n_cap - N} phantom nodes exceed degree 4 (the ELL form): repeated ids?")
 
@@ -359,13 +408,15 @@ class DeviceDataset:
         return b
 
 
-    def capacity(self, batch_size):
+    def capacity(self, batch_size, phantom_rows=None):
         """``(N_cap, E_cap)`` that hold any ``batch_size`` distinct graphs of this dataset (``padded_capacity``; pure host numpy)."""
-        return padded_capacity(self.ns, self.es, batch_size, self.ell_ok or self.ell_t_ok)
+        return padded_capacity(self.ns, self.es, batch_size, self.ell_ok or self.ell_t_ok, phantom_rows)
 
-    def padded(self, batch_size, capacity=None):
-        """A ``PaddedBatch`` of ``batch_size`` graphs: every tensor allocated once, filled by ``load(ids)``."""
-        return PaddedBatch(self, batch_size, capacity)
+    def padded(self, batch_size, capacity=None, phantom_rows=None):
+        """A ``PaddedBatch`` of ``batch_size`` graphs: every tensor allocated once, filled by ``load(ids)``.  ``phantom_rows = m``: the
+        surplus rows go to several phantom graphs of at most ``m`` nodes (``int(ds.ns.max())`` keeps them no larger than a real graph),
+        not to one that grows with the batch."""
+        return PaddedBatch(self, batch_size, capacity, phantom_rows)
 
 
 class PaddedBatch(Batch):
@@ -378,14 +429,20 @@ class PaddedBatch(Batch):
     row 0).  No kernel knows about it; a model that treats graphs independently gives the real graphs their usual rows, and a loss over
     ``output[:B]`` (``graphs.padded_loss``) gives the phantom rows a zero gradient.  ``y`` has the real graphs' ``B * r`` rows only.
     ``x`` is the ``[N_cap, F]`` view of a buffer whose rows are zero-padded to 16 bytes: ``ops.pad_cols`` hands the kernels the buffer
-    itself (a cached padded COPY would go stale with the second ``load``: a kernel write does not bump ``_version``)."""
+    itself (a cached padded COPY would go stale with the second ``load``: a kernel write does not bump ``_version``).
 
-    def __init__(self, dataset, batch_size, capacity=None):
+    ``phantom_rows = m``: the surplus nodes are cut into ``num_phantom_graphs = K`` phantom graphs of ``1 .. m`` nodes
+    each (``glam_collate_padded_split``), ``K`` fixed for the bucket, so ``num_graphs = B + K`` and the model's output has ``B + K`` rows.
+    The kernels that give a graph to one wave or block then never meet a graph larger than ``m``.  ``None``: one phantom graph."""
+
+    def __init__(self, dataset, batch_size, capacity=None, phantom_rows=None):
         from . import ops
         ds, B = dataset, int(batch_size)
         self.ell, self.ell_t = ds.ell_ok, ds.ell_t_ok
         has_y = ds.y is not None
-        N_cap, E_cap, r = padded_bucket(ds.ns, ds.es, ds.y_rows if has_y else np.zeros(0), B, capacity, self.ell or self.ell_t)
+        N_cap, E_cap, r = padded_bucket(ds.ns, ds.es, ds.y_rows if has_y else np.zeros(0), B, capacity, self.ell or self.ell_t, phantom_rows)
+        K = phantom_graphs(ds.ns, B, N_cap, phantom_rows)
+        self.num_phantom_graphs, self.phantom_rows = K, None if phantom_rows is None else int(phantom_rows)
         dev = ds.device
         xrb, earb, yrb = ds._row_bytes
         stride = (xrb + 15) & ~15
@@ -396,8 +453,8 @@ class PaddedBatch(Batch):
         new = lambda t, rows: None if t is None else torch.empty((rows,) + t.shape[1:], dtype=t.dtype, device=dev)   # noqa: E731
         ea, y = new(ds.ea, E_cap), new(ds.y, B * r)
         ei = torch.empty(2, E_cap, dtype=torch.int64, device=dev)
-        batch, ptr = torch.empty(N_cap, dtype=torch.int64, device=dev), torch.empty(B + 2, dtype=torch.int64, device=dev)
-        sizes = [B + 2, N_cap + 1, E_cap, E_cap, N_cap + 1, E_cap, E_cap] + [4 * N_cap if self.ell else 0] * 2 + [4 * N_cap if self.ell_t else 0] * 2
+        batch, ptr = torch.empty(N_cap, dtype=torch.int64, device=dev), torch.empty(B + K + 1, dtype=torch.int64, device=dev)
+        sizes = [B + K + 1, N_cap + 1, E_cap, E_cap, N_cap + 1, E_cap, E_cap] + [4 * N_cap if self.ell else 0] * 2 + [4 * N_cap if self.ell_t else 0] * 2
         starts = np.concatenate([[0], np.cumsum([(s + 3) & ~3 for s in sizes])])
         arena = torch.empty(int(starts[-1]), dtype=torch.int32, device=dev)
         ptr32, rowptr, src, eid, colptr, dst, eid_t, *ells = [arena[a:a + s] for a, s in zip(starts[:-1].tolist(), sizes)]
@@ -410,12 +467,12 @@ class PaddedBatch(Batch):
         self._tables = self.totals = None
         self._launched = False
         super().__init__(x=x, edge_index=ei, edge_attr=ea, y=y, batch=batch)
-        self.num_graphs, self.num_real_graphs, self.ptr = B + 1, B, ptr
+        self.num_graphs, self.num_real_graphs, self.ptr = B + K, B, ptr
         self.capacity = (N_cap, E_cap)
         gi = ops.GraphIndex.from_parts(ei, N_cap, rowptr, src, eid, (colptr, dst, eid_t), tuple(ells[:2]) if self.ell else None,
                                        tuple(ells[2:]) if self.ell_t else None)
         ops._GI_CACHE.put(ei, (N_cap, gi))
-        ops._SP_CACHE.put(batch, ops.SegmentPtr.from_parts(ptr32, N_cap, B + 1))
+        ops._SP_CACHE.put(batch, ops.SegmentPtr.from_parts(ptr32, N_cap, B + K))
         self._glam_marks = {"edge_index": ("_glam_trusted", True), "batch": ("_glam_trusted", True)}
         if ds.onehot is not None:
             self._glam_marks["edge_attr"] = ("_glam_onehot", ds.onehot)
@@ -430,7 +487,7 @@ class PaddedBatch(Batch):
         return self
 
     def _fit(self, B, N, E):
-        padded_fit(self.num_real_graphs, B, N, E, *self.capacity, self.ell or self.ell_t)
+        padded_fit(self.num_real_graphs, B, N, E, *self.capacity, self.ell or self.ell_t, self.num_phantom_graphs, self.phantom_rows)
 
     def load(self, ids=None, step=None, launch=True):
         """Put the graphs ``ids`` (exactly ``B`` of them) into this batch: the slot table goes to the device out of pinned memory, not
@@ -493,7 +550,12 @@ class PaddedBatch(Batch):
             self._launched = False
             return
         B, N_cap, E_cap, r, Ed, xrb, stride, earb, yrb = self._launch_args
-        _lib.api().glam_collate_padded(self._ds._ds, self._out, _lib.ptr(self._table), B, N_cap, E_cap, r, Ed, xrb, stride, earb, yrb, _lib.stream())
+        if self.phantom_rows is None:
+            _lib.api().glam_collate_padded(self._ds._ds, self._out, _lib.ptr(self._table), B, N_cap, E_cap, r, Ed, xrb, stride, earb, yrb,
+                                           _lib.stream())
+        else:
+            _lib.api().glam_collate_padded_split(self._ds._ds, self._out, _lib.ptr(self._table), B, self.num_phantom_graphs, N_cap, E_cap, r, Ed,
+                                                 xrb, stride, earb, yrb, _lib.stream())
 
 
 class DataLoader:
@@ -512,15 +574,19 @@ class DataLoader:
     ``padded=True`` (needs ``resident=True``): every FULL batch of an epoch is the SAME ``PaddedBatch`` object, reloaded — same order, same
     shuffle — so that a ``GraphedTrainStep`` captures one graph and replays it for all of them; whoever keeps a yielded batch sees the
     next one in it.  An epoch's tables are uploaded at once (``PaddedBatch.load_many``).  A short last batch comes from the ordinary
-    ``collate``.  ``collate_in_step=True``: the loader uploads the table only and leaves the launch to the stepper's graph."""
+    ``collate``.  ``collate_in_step=True``: the loader uploads the table only and leaves the launch to the stepper's graph.
+    ``phantom_rows``: handed to ``DeviceDataset.padded`` (several bounded phantom graphs; the size to use at large batches)."""
 
     def __init__(self, dataset, batch_size=32, shuffle=False, seed=0, device=None, cache=None, resident=False, padded=False,
-                 collate_in_step=False):
+                 collate_in_step=False, phantom_rows=None):
         self.dataset, self.batch_size, self.shuffle, self.seed = list(dataset), batch_size, shuffle, seed
         self.device = device
         self.padded, self._padded, self.collate_in_step = bool(padded), None, bool(collate_in_step)
         if self.padded and not resident:
             raise ValueError("DataLoader: padded=True reloads one batch of a device-resident dataset: pass resident=True")
+        if phantom_rows is not None and not self.padded:
+            raise ValueError("DataLoader: phantom_rows shapes the phantom graphs of padded batches: pass padded=True")
+        self.phantom_rows = None if phantom_rows is None else _phantom_rows(phantom_rows)
         if self.padded and cache:
             raise ValueError("DataLoader: padded=True hands out one batch object, reloaded: there is nothing to cache")
         self.cache = (not shuffle and not self.padded) if cache is None else bool(cache)
@@ -570,7 +636,7 @@ class DataLoader:
             if self._resident is None:
                 self._resident = DeviceDataset(self._packed, self.device)
             if self._padded is None:
-                self._padded = self._resident.padded(self.batch_size)
+                self._padded = self._resident.padded(self.batch_size, phantom_rows=self.phantom_rows)
             full = self._padded.load_many(order[:len(order) // self.batch_size * self.batch_size].reshape(-1, self.batch_size))
             for i in range(full):
                 yield self._padded.load(step=i, launch=not self.collate_in_step)

@@ -1110,6 +1110,22 @@ int glam_collate_padded(const void* const* ds_host, void* const* out_host, const
                         int64_t y_rows, int64_t Ed, int32_t x_row_bytes, int32_t x_out_stride_bytes, int32_t ea_row_bytes,
                         int32_t y_row_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * glam_collate_padded with the surplus nodes cut into K phantom graphs, so that no phantom graph grows with the batch: the kernels
+ * that give a graph to one wave or block (graph norms, readouts) then see K small graphs where glam_collate_padded hands them one of
+ * P nodes.  Same kernel, same launch, capturable the same way; glam_collate_padded is K = 1.
+ * The output is an ordinary batch of B + K graphs.  With s = P / K and r = P % K, phantom graph j (0 <= j < K) owns the s + (j < r)
+ * consecutive nodes from N + j * s + min(j, r) on: batch[N + p] = B + (p < r (s + 1) ? p / (s + 1) : r + (p - r (s + 1)) / s),
+ * ptr[B + j] = N + j * s + min(j, r) for 0 <= j <= K (ptr[B] = N, ptr[B + K] = N_cap).  Everything else — the real part, the phantom
+ * nodes' self-loop runs, both CSR tails, the ELL records, edge_attr, x, y — is what glam_collate_padded writes: the runs are per node,
+ * so the cut moves no edge.  out_host as for glam_collate_padded except ptr int64 / int32 [B + K + 1].  The K phantom graphs take no
+ * entries of the slot table: glam_collate_lds_slots() bounds B alone.
+ * The caller guarantees what glam_collate_padded asks and K <= P (no phantom graph is empty).
+ * GLAM_E_INVALID as for glam_collate_padded, and for K < 1, N_cap < K or B + K beyond int32 (checked before any device work). */
+int glam_collate_padded_split(const void* const* ds_host, void* const* out_host, const int32_t* table, int64_t B, int64_t K, int64_t N_cap,
+                              int64_t E_cap, int64_t y_rows, int64_t Ed, int32_t x_row_bytes, int32_t x_out_stride_bytes,
+                              int32_t ea_row_bytes, int32_t y_row_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 launches are not listed: tools/bench_model.py --profile names those; the ATen normalisation ops of the step are counted at the end).
 usage: kernel_sequence.py [batch] [preset]      (preset: relu, model_default, colnorm = a norm in every slot, DESIGN.md 4.12;
 padded = relu on a fixed-capacity batch with the loss over output[:B], DESIGN.md 4.16: the collate launch leads the sequence and the ATen
-ops of the output slice are counted at the end)"""
+ops of the output slice are counted at the end; padded_split = the same with phantom_rows = the dataset's largest graph)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -23,10 +23,12 @@ else:
     net = model.Architecture(mol_block="_TripletMessage", message_steps=3, graph_do="_None()", end_do="_None()", pre_act="ReLU", graph_act="ReLU",
                              flat_act="ReLU").to(dev)
 net.graphed_call = False      # (eager launches: every one carries its own events)
-if PRESET == "padded":
+PADDED = PRESET in ("padded", "padded_split")
+if PADDED:
     import numpy as np
     rng = np.random.default_rng(0)
-    b = DeviceDataset([synth_molecule(rng) for _ in range(2 * B)], dev).padded(B)
+    dd = DeviceDataset([synth_molecule(rng) for _ in range(2 * B)], dev)
+    b = dd.padded(B, phantom_rows=int(dd.ns.max()) if PRESET == "padded_split" else None)
     b.load(rng.permutation(2 * B)[:B], launch=False)
 else:
     b = synth_batch(B, seed=0).to(dev)
@@ -35,10 +37,10 @@ opt = optim.Adam(net.parameters(), lr=1e-3)
 ONE = torch.ones((), device=dev)
 
 def body():
-    if PRESET == "padded":
+    if PADDED:
         b.glam_reload()              # (the step's first launch: GraphedTrainStep calls the batch's reload hook)
     opt.zero_grad(set_to_none=True)
-    loss = glam_loss.mse_loss(net(b)[:B].view(-1), y)      # (every preset's output has B rows but the padded one's: B + 1)
+    loss = glam_loss.mse_loss(net(b)[:B].view(-1), y)      # (every preset's output has B rows but the padded ones': B + K)
     loss.backward(gradient=ONE)
     opt.step()
 
@@ -58,7 +60,7 @@ print(f"{i + 1} launches, {tot:.1f} us of kernels")
 import collections
 from torch.utils._python_dispatch import TorchDispatchMode
 NORM_OPS = ("batch_norm", "layer_norm", "aten.mean", "aten.std", "aten.var", "miopen")
-if PRESET == "padded":             # ... and what the slice output[:B] adds: forward a view, backward a zero fill and a copy into it
+if PADDED:                         # ... and what the slice output[:B] adds: forward a view, backward a zero fill and a copy into it
     NORM_OPS += ("slice", "aten.zeros", "aten.new_zeros", "aten.zero_", "aten.fill_", "aten.copy_")
 seen = collections.Counter()
 class Log(TorchDispatchMode):
@@ -69,4 +71,4 @@ class Log(TorchDispatchMode):
 with Log():
     body()
 torch.cuda.synchronize()
-print("ATen normalisation ops in the step:" if PRESET != "padded" else "ATen normalisation, slice, fill and copy ops in the step:", dict(seen) if seen else "none")
+print("ATen normalisation ops in the step:" if not PADDED else "ATen normalisation, slice, fill and copy ops in the step:", dict(seen) if seen else "none")

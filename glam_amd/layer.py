@@ -960,7 +960,7 @@ def _prestage_items(lin_block, block, x, edge_attr):
         M, Kw = lin.weight.shape
         Kx = _ceil4(x.size(1))
         if x.size(1) == Kw and M % 4 == 0 and ops.linear_supported(Kx, M) and not (Kx != Kw and x.requires_grad):
-            images.append(("fwd", ("lin", id(lin.weight)), lin.weight, lin.weight, Kw, 1, Kw, M, Kx))
+            images.append(ops.lin_image(lin.weight, Kx))
     conv = getattr(block, "conv", None)
     tm = getattr(conv, "conv", None) if isinstance(conv, _TripletMessage) else None
     if type(tm) is TripletMessage and tm.heads <= 4 and edge_attr is not None and edge_attr.dim() == 2 \
@@ -971,8 +971,7 @@ def _prestage_items(lin_block, block, x, edge_attr):
         w_ih, w_hh = gru.weight_ih_l0, gru.weight_hh_l0
         C = w_ih.size(1)
         if C % 4 == 0 and w_ih.shape == (3 * C, C) and ops.gru_images_plain(x.size(0), C):
-            images += [("fwd", ("lin", id(w_ih)), w_ih, w_ih, C, 1, C, 3 * C, C), ("fwd", ("lin", id(w_hh)), w_hh, w_hh, C, 1, C, 3 * C, C),
-                       ("bwd", ("lin", id(w_ih)), w_ih, w_ih, C, 0, 3 * C, C, 3 * C), ("bwd", ("lin", id(w_hh)), w_hh, w_hh, C, 0, 3 * C, C, 3 * C)]
+            images += [ops.lin_image(w_ih), ops.lin_image(w_hh), ops.lin_dx_image(w_ih), ops.lin_dx_image(w_hh)]
         elif C % 4 == 0 and w_ih.shape == (3 * C, C) and ops.gru_images_pre(x.size(0), C):
             gru_pre.append((w_ih, w_hh, C))
     return triplet, images, gru_pre

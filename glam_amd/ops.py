@@ -205,10 +205,30 @@ class _WeightScope:
     transposed images made by its backward.  A MessageBlock is applied ``message_steps`` times per forward with the same
     parameters (src_1gp/model.py:53-54), so each re-layout is built once per pass instead of once per application.  The
     scope only lives for one forward (and is kept alive by the autograd nodes for the matching backward): parameters cannot
-    change inside it, so nothing can go stale."""
+    change inside it, so nothing can go stale.
+
+    Three operations on the two tables (``table``: "fwd" / "bwd"; a value sits next to its ``owner``, so an ``id(owner)`` in the key stays
+    unique) are the whole interface: ``lookup``, ``store``, ``build`` (``scope_build``: the scope may be None).  What is filed under which
+    key is written down ONCE: a ``k_ts_gemm`` weight image by the constructor of its ``ImageSpec`` (``lin_image`` ...), which serves the
+    op's lazy build (``scoped_image``) and ``prestage`` alike; any other entry that several sites touch by its key constructor
+    (``triplet_key`` ...).  A new kind of entry adds a constructor, not a string at each site."""
 
     def __init__(self):
         self.fwd, self.bwd = {}, {}
+
+    def lookup(self, table, key, owner):      # None: nothing there, or another object under the same key (a reused ``id()``)
+        hit = (self.fwd if table == "fwd" else self.bwd).get(key)
+        return hit[1] if hit is not None and hit[0] is owner else None
+
+    def store(self, table, key, owner, value):
+        (self.fwd if table == "fwd" else self.bwd)[key] = (owner, value)
+
+    def build(self, table, key, owner, build_fn):      # ``build_fn()`` once per (table, key, owner)
+        val = self.lookup(table, key, owner)
+        if val is None:
+            val = build_fn()
+            self.store(table, key, owner, val)
+        return val
 
 
 _SCOPE = None
@@ -231,71 +251,107 @@ def weight_scope():
         scope.fwd.clear()
 
 
+def scope_build(scope, table, key, owner, build_fn):      # ``scope.build`` for a scope that may be None: ``build_fn()`` every time
+    return build_fn() if scope is None else scope.build(table, key, owner, build_fn)
+
+
 def scoped_weights(key, owner, build):
     """Derived weights (pure functions of parameters: pads, stacks, small matmuls) built once per model forward when a
     ``weight_scope`` is active; their autograd subgraph is then also shared by the applications of the block."""
-    return _scoped(_SCOPE.fwd if _SCOPE else None, key, owner, build)
+    return scope_build(_SCOPE, "fwd", key, owner, build)
 
 
-def _scoped(table, key, owner, build):
-    """``build()`` once per (scope table, key); ``owner`` is pinned next to the value so ``id(owner)`` stays unique."""
-    if table is None:
-        return build()
-    hit = table.get(key)
-    if hit is not None and hit[0] is owner:
-        return hit[1]
-    val = build()
-    table[key] = (owner, val)
-    return val
+# ---- k_ts_gemm weight images: ONE description per image, for the lazy build of its op (scoped_image) and for prestage ------------
+# ``glam_ts_gemm_make_image(W, ldw, transW, K, M, img)`` into an image of ``glam_ts_gemm_image_bytes(Kimg, M)`` bytes, filed in the scope's
+# ``table`` under ``key`` / ``owner``.  ``Kimg > K``: a zero-padded input's linear (15 -> 16 rows), filled from the unpadded weight.
+ImageSpec = collections.namedtuple("ImageSpec", "table key owner W ldw transW K M Kimg")
+
+
+class _ImageKind(collections.namedtuple("_ImageKind", "table name transposed")):
+    """One kind of weight image: its scope table, the name in its key and whether it holds ``W`` as stored (``[K, M]``) or the transpose
+    of the stored ``[M, K]`` matrix.  Calling it gives the ``ImageSpec`` of one matrix ``W`` (default: the owner itself)."""
+
+    def entry(self, owner):      # (table, key, owner): where the image of ``owner`` is filed
+        return self.table, (self.name, id(owner)), owner
+
+    def __call__(self, owner, Kimg=None, W=None):
+        W = owner if W is None else W
+        K, M = W.shape[::-1] if self.transposed else W.shape
+        return ImageSpec(*self.entry(owner), W, W.stride(0), int(self.transposed), K, M, K if Kimg is None else Kimg)
+
+
+# an nn.Linear weight [M, Kw] for an input of Kimg (default: Kw) columns, and its input-gradient product dy[N, M] @ w
+lin_image, lin_dx_image = _ImageKind("fwd", "lin", True), _ImageKind("bwd", "lin", False)
+# the [K, M]-stored operand of _MatmulTall, and dy[N, M] @ w^T
+tall_image, tall_dx_image = _ImageKind("fwd", "tall-fwd", False), _ImageKind("bwd", "tall-dx", True)
+# _TripletLayerWide (owner wn; W: the views Wcat[Cp, HC + 8] / Ws_p[HC, Cp] of its plain staging): x @ Wcat, aggr @ Ws_p, d_out @ Ws_p^T, [d_xw | d_a] @ Wcat^T
+wide_node_image, wide_upd_image = _ImageKind("fwd", "wide-img-node", False), _ImageKind("fwd", "wide-img-upd", False)
+wide_dagg_image, wide_dx_image = _ImageKind("bwd", "wide-img-dagg", True), _ImageKind("bwd", "wide-img-dx", True)
+
+
+def scoped_image(scope, kind, owner, Kimg=None, W=None):
+    """The image ``kind(owner, Kimg, W)``, built on first use and filed in ``scope`` (None: built every time); a hit builds no spec."""
+    img = None if scope is None else scope.lookup(kind.table, (kind.name, id(owner)), owner)
+    if img is None:
+        lib, spec = _lib.api(), kind(owner, Kimg, W)
+        img = torch.empty(lib.glam_ts_gemm_image_bytes(spec.Kimg, spec.M) // 4, dtype=torch.float32, device=spec.W.device)
+        lib.glam_ts_gemm_make_image(ptr(spec.W), spec.ldw, spec.transW, spec.K, spec.M, ptr(img), stream())
+        if scope is not None:
+            scope.store(*kind.entry(owner), img)
+    return img
+
+
+# ---- keys of the other entries that several sites touch (the owner is the first tensor): the staged images of a TripletMessage (plain:
+# the wide layer's staging), the flag that the pass applied it on the ELL route, the pre-split images of a GRU's gate matrices (a
+# gru_pre_buffer: [2, bytes], forward | backward), the gate-padded images of the fp32 fused GRU step, the padded GRU parameters of an odd width
+def triplet_key(wn, we, att, wsc, bias, plain=False): return ("triplet-plain" if plain else "triplet", id(wn), id(we), id(att), id(wsc), id(bias))
+def triplet_ell_key(wn): return ("triplet-ell", id(wn))
+def gru_pre_key(w_ih, w_hh): return ("gru-pre", id(w_ih), id(w_hh))
+def gru_pre_buffer(w_ih): return torch.empty(2, _lib.api().glam_gru_ws_pre_bytes(), dtype=torch.uint8, device=w_ih.device)
+def gru_fused_key(w_ih, w_hh): return ("gru-fused", id(w_ih), id(w_hh))
+def gru_pad_key(w_ih, w_hh, b_ih, b_hh): return ("gru-pad", id(w_ih), id(w_hh), id(b_ih), id(b_hh))
+
 
 def prestage(triplet=None, images=(), gru_pre=()):
     """The derived weights of a model pass in ONE launch (``glam_prestage``) instead of one per module at its first use: the staged
     images of a TripletMessage (``triplet = (wn, we, att, wsc, bias, H, Dp)``) and up to six ``k_ts_gemm`` weight images
-    (``images``: ``(table, key, owner, W, ldw, transW, K, M, K_image)`` with ``table`` in {"fwd", "bwd"} — the scope table and key
-    under which the lazy builder of the op looks the image up).  The entries are put into the active ``weight_scope`` exactly as the
-    lazy builders would put them, so an op whose route differs from the caller's guess just builds its own as before.  Returns the
+    (``images``: ``ImageSpec``s, or plain tuples of their fields, from the constructors that the ops build their images with lazily).
+    The entries are put into the active ``weight_scope`` exactly as the lazy builders would put them, so an op whose route differs
+    from the caller's guess just builds its own as before.  Returns the
     number of entries built (0: no scope, switched off, or everything already there).  ``gru_pre``: ``(w_ih, w_hh, C)`` per GRU whose
     warp-specialised step wants its pre-split images (``glam_gru_ws_make_pre``; four of the six jobs of a launch)."""
     scope = _SCOPE
     if scope is None or not PRESTAGE:
         return 0
     lib = _lib.api()
-    f = None
     args_t = [None] * 5 + [0] * 5 + [None]
     built = 0
+    on_device = lambda *ts: all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts)
     if triplet is not None and not CACHED_STAGING:
         wn, we, att, wsc, bias, H, Dp = triplet
-        key = ("triplet", id(wn), id(we), id(att), id(wsc), id(bias))
-        hit = scope.fwd.get(key)
-        ok = all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (wn, we, att, wsc, bias))
-        if ok and not (hit is not None and hit[0] is wn):
+        key = triplet_key(wn, we, att, wsc, bias)
+        if on_device(wn, we, att, wsc, bias) and scope.lookup("fwd", key, wn) is None:
             C, De = wn.size(0), we.size(0)
             Cp = (C + 3) // 4 * 4
-            f = dict(dtype=torch.float32, device=wn.device)
-            buf = torch.empty(lib.glam_triplet_staged_floats(H, Cp, Dp), **f)
+            buf = torch.empty(lib.glam_triplet_staged_floats(H, Cp, Dp), dtype=torch.float32, device=wn.device)
             args_t = [ptr(wn), ptr(we), ptr(att), ptr(wsc), ptr(bias), C, H, De, Cp, Dp, ptr(buf)]
-            scope.fwd[key] = (wn, buf)
+            scope.store("fwd", key, wn, buf)
             built += 1
     jobs = []
     for table, key, owner, W, ldw, transW, K, M, Kimg in images:
-        tab = scope.fwd if table == "fwd" else scope.bwd
-        hit = tab.get(key)
-        if (hit is not None and hit[0] is owner) or not (W.is_cuda and W.dtype == torch.float32 and W.is_contiguous()) or len(jobs) == 6:
+        if scope.lookup(table, key, owner) is not None or not on_device(W) or len(jobs) == 6:
             continue
-        f = f or dict(dtype=torch.float32, device=W.device)
-        img = torch.empty(lib.glam_ts_gemm_image_bytes(Kimg, M) // 4, **f)
+        img = torch.empty(lib.glam_ts_gemm_image_bytes(Kimg, M) // 4, dtype=torch.float32, device=W.device)
         jobs.append((W, (ldw, transW, K, M), img))
-        tab[key] = (owner, img)
+        scope.store(table, key, owner, img)
         built += 1
     for w_ih, w_hh, C in gru_pre:
-        key = ("gru-pre", id(w_ih), id(w_hh))
-        hit = scope.fwd.get(key)
-        ok = all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (w_ih, w_hh))
-        if (hit is not None and hit[0] is w_ih) or not ok or len(jobs) + 4 > 6:
+        key = gru_pre_key(w_ih, w_hh)
+        if scope.lookup("fwd", key, w_ih) is not None or not on_device(w_ih, w_hh) or len(jobs) + 4 > 6:
             continue
-        buf = torch.empty(2, lib.glam_gru_ws_pre_bytes(), dtype=torch.uint8, device=w_ih.device)
+        buf = gru_pre_buffer(w_ih)
         jobs += [(w_ih, (C, 2, C, 0), buf[0]), (w_hh, (C, 2, C, 1), buf[0]), (w_ih, (C, 3, C, 0), buf[1]), (w_hh, (C, 3, C, 1), buf[1])]
-        scope.fwd[key] = (w_ih, buf)
+        scope.store("fwd", key, w_ih, buf)
         built += 1
     if built == 0:
         return 0
@@ -429,7 +485,7 @@ def pad_cols(x, Cp):
             padded = torch.nn.functional.pad(x, (0, Cp - C))
             _PAD_DATA.put(x, padded)
         return padded
-    return _scoped(_SCOPE.fwd if _SCOPE else None, ("pad-cols", id(x), Cp), x, lambda: torch.nn.functional.pad(x, (0, Cp - C)))
+    return scoped_weights(("pad-cols", id(x), Cp), x, lambda: torch.nn.functional.pad(x, (0, Cp - C)))
 
 
 _PAD_DATA = TensorMemo("id")      # data tensor -> its zero-padded copy
@@ -606,17 +662,17 @@ class _Carry:
 
     def __init__(self, key, params, shapes, order=None):
         self.key, self.owner, self.scope = key, params[0], _SCOPE
-        hit = self.scope.fwd.get(key) if self.scope is not None else None
-        self.first = not (hit is not None and hit[0] is self.owner)
+        prev = self.scope.lookup("fwd", key, self.owner) if self.scope is not None else None
+        self.first = prev is None
         self.tensor = None
         if self.scope is not None and GRAD_CARRY and torch.is_grad_enabled() and any(p.requires_grad for p in params):
             order = tuple(range(len(params))) if order is None else order
-            self.tensor = _ParamBundle.apply(shapes, order, *params) if self.first else hit[1]
+            self.tensor = _ParamBundle.apply(shapes, order, *params) if self.first else prev
 
     def store(self, carry):
         """The node's carry output, for the block's next application."""
         if carry is not None:
-            self.scope.fwd[self.key] = (self.owner, carry)
+            self.scope.store("fwd", self.key, self.owner, carry)
 
 
 def _carried(flat, d_carry, summed=False):
@@ -643,7 +699,7 @@ def _park(scope, kind, owner, first, operands, compat=None):
     first: the caller returns its pass-through gradients.  On the first one it returns all parked sets as the groups to launch: at
     most three sets each, of one ``compat`` key, in parking order.  The list is emptied before anything is launched: a set left
     behind by an interrupted backward would be counted again by a retried one (``retain_graph=True``)."""
-    parked = scope.bwd.setdefault(("parked", kind, id(owner)), (owner, []))[1]
+    parked = scope.build("bwd", ("parked", kind, id(owner)), owner, list)
     if operands is not None:
         parked.append((compat, operands))
     if not first:
@@ -749,7 +805,7 @@ class _TripletLayer(torch.autograd.Function):
         # the same conv is applied message_steps times per model forward: one staging per pass (see _WeightScope); with
         # ops.cached_staging() the staged images additionally survive from pass to pass until a parameter is written
         staged = _staged_cached(("triplet", H, Cp, Dp), (wn, we, att, wsc, bias), build) if CACHED_STAGING else \
-            _scoped(_SCOPE.fwd if _SCOPE else None, ("triplet", id(wn), id(we), id(att), id(wsc), id(bias)), wn, build)
+            scoped_weights(triplet_key(wn, we, att, wsc, bias), wn, build)
         out = torch.empty(N, Cp, **f)
         # molecular graphs with one-hot bond features take the warp-specialised kernels at every size (13.6 vs 16.8 us at B = 1 024,
         # 136 vs 256 us at B = 16 384 against the general fused kernel); everything else the general kernels
@@ -758,7 +814,7 @@ class _TripletLayer(torch.autograd.Function):
         given = take_node_product(x_p, staged) if ell is not None else None
         xw, a_ij = given if given is not None else (torch.empty(N, HC, **f), torch.empty(N, 8, **f))
         if ell is not None and _SCOPE is not None:
-            _SCOPE.fwd[("triplet-ell", id(wn))] = (wn, True)
+            _SCOPE.store("fwd", triplet_ell_key(wn), wn, True)
         # no backward will come (torch.no_grad(): the evaluation passes of src_1gp/trainer.py:306-327): the inference forward, which keeps
         # neither `aggr` nor `stats` (two thirds of what the launch writes)
         # (`no_backward` comes from the caller: inside forward() autograd is off and needs_input_grad ignores torch.no_grad())
@@ -973,37 +1029,30 @@ class _TripletLayerWide(torch.autograd.Function):
             lib.glam_triplet_stage_plain(ptr(wn), ptr(we), ptr(att), ptr(wsc), ptr(bias), C, H, De, Cp, Dp, ptr(buf), stream())
             return buf
 
-        scope = _SCOPE
-        plain = _scoped(scope.fwd if scope else None, ("triplet-plain", id(wn), id(we), id(att), id(wsc), id(bias)), wn, build)
+        scope = ctx.scope = _SCOPE
+        plain = scope_build(scope, "fwd", triplet_key(wn, we, att, wsc, bias, plain=True), wn, build)
         Wcat, Ws_p, We_p, M, bias_p = _plain_views(plain, H, Cp, Dp)
         xw, a_ij = torch.empty(N, HC, **f), torch.empty(N, 8, **f)
         aggr, stats, out = torch.empty(N, HC, **f), torch.empty(N, 8, **f), torch.empty(N, Cp, **f)
-        mfma = _wide_gemms_supported(H, Cp)
+        mfma, tall = _wide_gemms_supported(H, Cp), _wide_tall_supported(H, Cp)
         st = stream()
         if scope is not None and any(ctx.needs_input_grad):
             # the four GEMM images of the pass (two for the forward, two for the backward) from one launch instead of four
-            imgs = []
-            if mfma:
-                imgs += [("fwd", ("wide-img-node", id(wn)), wn, Wcat, Wcat.stride(0), 0, Cp, HC + 8, Cp),
-                         ("bwd", ("wide-img-dagg", id(wn)), wn, Ws_p, Ws_p.stride(0), 1, Cp, HC, Cp)]
-            if _wide_tall_supported(H, Cp):
-                imgs += [("fwd", ("wide-img-upd", id(wn)), wn, Ws_p, Ws_p.stride(0), 0, HC, Cp, HC),
-                         ("bwd", ("wide-img-dx", id(wn)), wn, Wcat, Wcat.stride(0), 1, HC + 8, Cp, HC + 8)]
-            prestage(None, imgs)
+            prestage(None, ([wide_node_image(wn, W=Wcat), wide_dagg_image(wn, W=Ws_p)] if mfma else []) +
+                     ([wide_upd_image(wn, W=Ws_p), wide_dx_image(wn, W=Wcat)] if tall else []))
         if mfma:     # the 120 KB-image k_ts_gemm variant: xw and a_ij in one launch
-            img1 = _scoped(scope.fwd if scope else None, ("wide-img-node", id(wn)), wn, lambda: _ts_image(Wcat, Cp, HC + 8, False))
+            img1 = scoped_image(scope, wide_node_image, wn, W=Wcat)
             lib.glam_ts_gemm(ptr(x_p), Cp, Cp, None, 0, 0, ptr(img1), None, ptr(xw), HC, HC, ptr(a_ij), 8, 8, N, st)
         else:
             torch.matmul(x_p, Wcat[:, :HC], out=xw)                        # layer.py:37
             torch.matmul(x_p, Wcat[:, HC:], out=a_ij)                      # separable attention scalars a_i | a_j
         lib.glam_triplet_fwd(ptr(xw), ptr(a_ij), ptr(ea_p), ptr(We_p), ptr(M), ptr(gi.rowptr), ptr(gi.src), ptr(gi.eid),
                              N, gi.E, H, Cp, Dp, 1, float(slope), ptr(aggr), ptr(stats), st)
-        if _wide_tall_supported(H, Cp):      # layer.py:57-61, 276 -> 92: the long-reduction 3 x bf16 kernel (tall_x3.hip)
-            img2 = _scoped(scope.fwd if scope else None, ("wide-img-upd", id(wn)), wn, lambda: _ts_image(Ws_p, HC, Cp, False))
+        if tall:      # layer.py:57-61, 276 -> 92: the long-reduction 3 x bf16 kernel (tall_x3.hip)
+            img2 = scoped_image(scope, wide_upd_image, wn, W=Ws_p)
             lib.glam_ts_gemm(ptr(aggr), HC, HC, None, 0, 0, ptr(img2), ptr(bias_p), ptr(out), Cp, Cp, None, 0, 0, N, st)
         else:
             torch.addmm(bias_p, aggr, Ws_p, out=out)
-        ctx.scope = scope
         ctx.save_for_backward(x_p, ea_p, wn, we, att, plain, xw, a_ij, aggr, stats)
         ctx.gi, ctx.dims = gi, (C, H, De, Cp, Dp, float(slope))
         return (out, carry.view(-1)) if ctx.carried else out
@@ -1036,7 +1085,7 @@ class _TripletLayerWide(torch.autograd.Function):
         mfma = _wide_gemms_supported(H, Cp)
         scope = ctx.scope
         if mfma:
-            img3 = _scoped(scope.bwd if scope else None, ("wide-img-dagg", id(wn)), wn, lambda: _ts_image(Ws_p, Cp, HC, True))
+            img3 = scoped_image(scope, wide_dagg_image, wn, W=Ws_p)
             d_aggr = torch.empty(N, HC, **f)
             lib.glam_ts_gemm(ptr(d_out), Cp, Cp, None, 0, 0, ptr(img3), None, ptr(d_aggr), HC, HC, None, 0, 0, N, stream())
         else:
@@ -1048,7 +1097,7 @@ class _TripletLayerWide(torch.autograd.Function):
                              ptr(gi.eid), ptr(colptr), ptr(dst), ptr(eid_t), N, E, H, Cp, Dp, 1, slope, ptr(d_xw), ptr(d_a), ptr(dstaged[o_we:]),
                              ptr(dstaged[o_m:]), ptr(d_ea), ptr(ws), ws.numel(), stream())
         if _wide_tall_supported(H, Cp):      # d_x = [d_xw | d_a] @ Wcat^T: both sources in one launch
-            img4 = _scoped(scope.bwd if scope else None, ("wide-img-dx", id(wn)), wn, lambda: _ts_image(Wcat, HC + 8, Cp, True))
+            img4 = scoped_image(scope, wide_dx_image, wn, W=Wcat)
             d_x = torch.empty(N, Cp, **f)
             lib.glam_ts_gemm(ptr(d_xw), HC, HC, ptr(d_a), 8, 8, ptr(img4), None, ptr(d_x), Cp, Cp, None, 0, 0, N, stream())
         else:
@@ -1096,14 +1145,6 @@ def _wide_gemms_supported(H, Cp):
 def _wide_tall_supported(H, Cp):
     """The long-reduction products of the wide layer (H Cp (+ 8) -> Cp) inside tall_x3.hip's table (K <= 288, M <= 96)."""
     return _wide_gemms_supported(H, Cp) and H * Cp + 8 <= 288
-
-
-def _ts_image(W, K, M, transposed):
-    """k_ts_gemm weight image of the logical ``[K, M]`` matrix ``W`` (or ``W^T`` of the stored ``[M, K]`` matrix)."""
-    lib = _lib.api()
-    img = torch.empty(lib.glam_ts_gemm_image_bytes(K, M) // 4, dtype=torch.float32, device=W.device)
-    lib.glam_ts_gemm_make_image(ptr(W), W.stride(0), int(transposed), K, M, ptr(img), stream())
-    return img
 
 
 def _plain_views(plain, H, Cp, Dp):
@@ -1269,12 +1310,12 @@ def first_node_spec(conv, N, edge_index, edge_attr):
     if C % 4 or De != 4 or not (1 <= H <= 4 and fused_layer_supported(C, H, De)) or H * C + 8 <= 64 or N > NODE_IN_GRU_MAX_ROWS or _want_torch_ext(N, H, C):
         return None
     wn = conv.weight_node
-    hit = _SCOPE.fwd.get(("triplet", id(wn), id(conv.weight_edge), id(conv.weight_triplet_att), id(conv.weight_scale), id(conv.bias)))
-    if hit is None or hit[0] is not wn or edge_attr is None or edge_attr.dim() != 2 or edge_attr.size(1) != De or edge_attr.dtype != torch.float32:
+    staged = _SCOPE.lookup("fwd", triplet_key(wn, conv.weight_edge, conv.weight_triplet_att, conv.weight_scale, conv.bias), wn)
+    if staged is None or edge_attr is None or edge_attr.dim() != 2 or edge_attr.size(1) != De or edge_attr.dtype != torch.float32:
         return None
     if not _ws_route(_lib.api(), N, H, C, De, edge_attr) or graph_index(edge_index, N).ell() is None:
         return None
-    return hit[1], H * C
+    return staged, H * C
 
 
 def next_node_spec(conv, N):
@@ -1286,11 +1327,10 @@ def next_node_spec(conv, N):
     if C % 4 or not (1 <= H <= 4 and fused_layer_supported(C, H, De)) or H * C + 8 <= 64 or N > NODE_IN_GRU_MAX_ROWS or _want_torch_ext(N, H, C):
         return None
     wn = conv.weight_node
-    took = _SCOPE.fwd.get(("triplet-ell", id(wn)))
-    hit = _SCOPE.fwd.get(("triplet", id(wn), id(conv.weight_edge), id(conv.weight_triplet_att), id(conv.weight_scale), id(conv.bias)))
-    if took is None or took[0] is not wn or hit is None or hit[0] is not wn:
+    staged = _SCOPE.lookup("fwd", triplet_key(wn, conv.weight_edge, conv.weight_triplet_att, conv.weight_scale, conv.bias), wn)
+    if staged is None or _SCOPE.lookup("fwd", triplet_ell_key(wn), wn) is None:
         return None
-    return hit[1], H * C
+    return staged, H * C
 # the readout MLP's products of few tiles split k across blocks (glam_linear_dense_*_ws; matters at the reference's batch of 32): A/B switch
 DENSE_SPLITK = os.environ.get("GLAM_DENSE_SPLITK", "1") != "0"
 # PairNorm + the Dropout behind it from one launch each way (glam_graph_norm_drop_*): A/B switch

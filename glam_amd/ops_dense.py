@@ -46,14 +46,8 @@ class _Linear(torch.autograd.Function):
         if Kw > K or (Kw < K and ctx.needs_input_grad[0]):
             raise GlamHipError("linear: weight wider than the input / narrow weight with a differentiable input")
         lib, dev = _lib.api(), x.device
-        scope = _o._SCOPE
-
-        def build():
-            img = torch.empty(lib.glam_ts_gemm_image_bytes(K, M) // 4, dtype=torch.float32, device=dev)
-            lib.glam_ts_gemm_make_image(ptr(w), Kw, 1, Kw, M, ptr(img), stream())
-            return img
-
-        img = _o._scoped(scope.fwd if scope else None, ("lin", id(w)), w, build)
+        ctx.scope = _o._SCOPE
+        img = _o.scoped_image(ctx.scope, _o.lin_image, w, K)
         y = torch.empty(N, M, dtype=torch.float32, device=dev)
         ctx.rrelu = None
         nd = None
@@ -76,7 +70,6 @@ class _Linear(torch.autograd.Function):
             ctx.save_for_backward(x, w, y)
             ctx.rrelu, ctx.eff = (lo, hi, p), eff
             ctx.has_bias = b is not None
-            ctx.scope = scope
             return y, y_drop
         if relu and nd is not None:
             lib.glam_ts_gemm_act_node(ptr(x), K, K, ptr(img), ptr(b), M, N, 1, 0.0, 0.0, 0.0, None, None, ptr(y), None, ptr(nd[0]), nd[1],
@@ -89,7 +82,6 @@ class _Linear(torch.autograd.Function):
             lib.glam_ts_gemm(ptr(x), K, K, None, 0, 0, ptr(img), ptr(b), ptr(y), M, M, None, 0, 0, N, stream())
             ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
-        ctx.scope = scope
         return y
 
     @staticmethod
@@ -119,12 +111,7 @@ class _Linear(torch.autograd.Function):
         f = dict(dtype=torch.float32, device=dev)
         dx = None
         if ctx.needs_input_grad[0]:
-            def build():
-                img = torch.empty(lib.glam_ts_gemm_image_bytes(M, K) // 4, **f)
-                lib.glam_ts_gemm_make_image(ptr(w), K, 0, M, K, ptr(img), stream())
-                return img
-
-            img = _o._scoped(ctx.scope.bwd if ctx.scope else None, ("lin", id(w)), w, build)
+            img = _o.scoped_image(ctx.scope, _o.lin_dx_image, w)
             dx = torch.empty(N, K, **f)
             lib.glam_ts_gemm(ptr(dy), M, M, None, 0, 0, ptr(img), None, ptr(dx), K, K, None, 0, 0, N, stream())
         ws = torch.empty(lib.glam_wgrad_workspace_bytes(), dtype=torch.uint8, device=dev)
@@ -225,8 +212,7 @@ class _MatmulTall(torch.autograd.Function):
             # NNConv's [N, 300] x [300, 60] relation product (and any K <= 320 x M <= 64): the long-reduction 3 x bf16 kernel (tall_x3.hip)
             # (an 80 KB-image fp32 k_ts_gemm<4, 20, 4> measured 18.9 us against the library's 15 at N = 20 k and was not kept)
             lib = _lib.api()
-            scope = ctx.scope
-            img = _o._scoped(scope.fwd if scope else None, ("tall-fwd", id(w)), w, lambda: _o._ts_image(w, K, M, False))
+            img = _o.scoped_image(ctx.scope, _o.tall_image, w)
             out = torch.empty(N, M, dtype=torch.float32, device=a.device)
             lib.glam_ts_gemm(ptr(a), K, K, None, 0, 0, ptr(img), ptr(f32c(bias, "bias")) if bias is not None else None, ptr(out), M, M,
                              None, 0, 0, N, stream())
@@ -253,26 +239,20 @@ class _MatmulTall(torch.autograd.Function):
         dy = f32c(dy, "dy")
         da = None
         if ctx.needs_input_grad[0]:
-            if M <= 64 and K <= 64 and M % 4 == 0 and K % 4 == 0 and linear_supported(M, K) and N > 0:
-                # a layer-sized product (GCNConv 60 -> 60): k_ts_gemm, the skip connection's gradient added in its epilogue
+            # a layer-sized product (GCNConv 60 -> 60): k_ts_gemm, the skip connection's gradient added in its epilogue
+            layer_sized = M <= 64 and K <= 64 and M % 4 == 0 and K % 4 == 0 and linear_supported(M, K) and N > 0
+            # dy[N, M] @ w^T[M, K] with a wide output: the 120 KB-image k_ts_gemm variant (the library GEMM picks 16x256
+            # tiles for this shape: 44 us for 60 -> 300 at N = 20 k)
+            if layer_sized or (M <= 96 and K <= 320 and K > 64):
                 lib = _lib.api()
-                scope = ctx.scope
-                img = _o._scoped(scope.bwd if scope else None, ("tall-dx", id(w)), w, lambda: _o._ts_image(w, M, K, True))
+                img = _o.scoped_image(ctx.scope, _o.tall_dx_image, w)
                 da = torch.empty(N, K, dtype=torch.float32, device=a.device)
-                if d_alias is not None:
+                if layer_sized and d_alias is not None:
                     d_alias = f32c(d_alias, "d_identity")
                     lib.glam_ts_gemm_add(ptr(dy), M, M, ptr(img), None, ptr(da), K, K, ptr(d_alias), K, N, stream())
                     d_alias = None
                 else:
                     lib.glam_ts_gemm(ptr(dy), M, M, None, 0, 0, ptr(img), None, ptr(da), K, K, None, 0, 0, N, stream())
-            elif M <= 96 and K <= 320 and K > 64:
-                # dy[N, M] @ w^T[M, K] with a wide output: the 120 KB-image k_ts_gemm variant (the library GEMM picks 16x256
-                # tiles for this shape: 44 us for 60 -> 300 at N = 20 k)
-                lib = _lib.api()
-                scope = ctx.scope
-                img = _o._scoped(scope.bwd if scope else None, ("tall-dx", id(w)), w, lambda: _o._ts_image(w, M, K, True))
-                da = torch.empty(N, K, dtype=torch.float32, device=a.device)
-                lib.glam_ts_gemm(ptr(dy), M, M, None, 0, 0, ptr(img), None, ptr(da), K, K, None, 0, 0, N, stream())
             else:
                 da = torch.matmul(dy, w.t())
             if d_alias is not None:
@@ -386,7 +366,7 @@ class _LinearTall(torch.autograd.Function):
         ctx.save_for_backward(x, w)
         if K <= 96 and M <= 320:       # 92 -> 276: k_tall_x3<3, 4, 5> (15 us at N = 20.4 k; the library 29, the fp32 LDS-image kernel 24)
             lib = _lib.api()
-            img = _o._scoped(_o._SCOPE.fwd if _o._SCOPE else None, ("lin", id(w)), w, lambda: _o._ts_image(w, K, M, True))
+            img = _o.scoped_image(ctx.scope, _o.lin_image, w)
             y = torch.empty(N, M, dtype=torch.float32, device=x.device)
             if ctx.fold:
                 lib.glam_ts_gemm_celu(ptr(x), K, K, 1, ptr(img), ptr(b), ptr(y), M, M, None, 0, N, stream())
@@ -409,8 +389,7 @@ class _LinearTall(torch.autograd.Function):
         f = dict(dtype=torch.float32, device=x.device)
         dx = None
         if ctx.needs_input_grad[0] and M <= 288 and K <= 96 and N > 0:      # dy[N, M] @ w[M, K], long reduction: tall_x3.hip
-            scope = ctx.scope
-            img = _o._scoped(scope.bwd if scope else None, ("lin-t", id(w)), w, lambda: _o._ts_image(w, M, K, False))
+            img = _o.scoped_image(ctx.scope, _o.lin_dx_image, w)
             dx = torch.empty(N, K, **f)
             if ctx.fold:        # ... * celu'(x) in the epilogue
                 lib.glam_ts_gemm_celu(ptr(dy), M, M, 0, ptr(img), None, ptr(dx), K, K, ptr(x), K, N, stream())
@@ -888,36 +867,28 @@ def gru_tail(x, h, identity, w_ih, w_hh, b_ih, b_hh, act="none", slope=0.0, celu
         # node = (staged, H * Cp) of ops.next_node_spec: the launch also writes the node product of the block's next application
         return _gru_block(x, h, identity, w_ih, w_hh, b_ih, b_hh, ACT_CODES[act], slope, celu_in, rng, node)
     Cp = (C + 3) // 4 * 4
+    padded = lambda: _o.scoped_weights(_o.gru_pad_key(w_ih, w_hh, b_ih, b_hh), w_ih, lambda: _gru_padded(w_ih, w_hh, b_ih, b_hh, C, Cp))
     if _gru_padded_supported(C, w_ih, b_ih, b_hh):
         # odd widths: the same node at Cp with gate-wise zero-padded weights (built once per model pass).  Pad channels
         # stay exactly zero through the step: gates r = z = 1/2, n = tanh(0) = 0, h' = z * 0 = 0, act(0 + 0) = 0.
-        def build():
-            return _gru_padded(w_ih, w_hh, b_ih, b_hh, C, Cp)
-        wi, wh, bi, bh = _o.scoped_weights(("gru-pad", id(w_ih), id(w_hh), id(b_ih), id(b_hh)), w_ih, build)
+        wi, wh, bi, bh = padded()
         # (with rng the dropped twin is registered for out_p: layer._apply_dropout finds it through the padded base of the view)
         out_p, hn_p = _gru_block(_o.pad_cols(x, Cp), _o.pad_cols(h, Cp), None if identity is None else _o.pad_cols(identity, Cp),
                                  wi, wh, bi, bh, ACT_CODES[act], slope, celu_in, rng)
         return _o.slice_cols(out_p, C), _o.slice_cols(hn_p, C)
     if b_ih is not None and b_hh is not None and tuple(w_ih.shape) == (3 * C, C) and linear_tall_supported(Cp, 3 * Cp) and h.size(0) >= 64:
         # wide GRU (hid_dim_alpha = 6): library GEMMs for the gate products, k_wgrad for their weight gradients, at Cp
-        def build_wide():
-            return _gru_padded(w_ih, w_hh, b_ih, b_hh, C, Cp)
-        wi, wh, bi, bh = _o.scoped_weights(("gru-pad", id(w_ih), id(w_hh), id(b_ih), id(b_hh)), w_ih, build_wide) if Cp != C else \
-            (w_ih, w_hh, b_ih, b_hh)
+        wi, wh, bi, bh = padded() if Cp != C else (w_ih, w_hh, b_ih, b_hh)
         x_p, h_p = _o.pad_cols(x, Cp), _o.pad_cols(h, Cp)
         if torch.is_grad_enabled() and Cp <= 96:
             # the four images of the two gate linears (forward and input-gradient products) from one launch instead of four
-            Kc, Mc = Cp, 3 * Cp
-            _o.prestage(None, [("fwd", ("lin", id(wi)), wi, wi, Kc, 1, Kc, Mc, Kc), ("fwd", ("lin", id(wh)), wh, wh, Kc, 1, Kc, Mc, Kc),
-                               ("bwd", ("lin-t", id(wi)), wi, wi, Kc, 0, Mc, Kc, Mc), ("bwd", ("lin-t", id(wh)), wh, wh, Kc, 0, Mc, Kc, Mc)])
+            _o.prestage(None, [_o.lin_image(wi), _o.lin_image(wh), _o.lin_dx_image(wi), _o.lin_dx_image(wh)])
         out_p, hn_p = _GruTail.apply(_linear_tall_node(x_p, wi, bi, celu_in), _linear_tall_node(h_p, wh, bh), h_p,
                                      None if identity is None else _o.pad_cols(identity, Cp), ACT_CODES[act], slope)
         return _o.slice_cols(out_p, C), _o.slice_cols(hn_p, C)
     if celu_in:
         x = torch.celu(x)
     return _GruTail.apply(linear(x, w_ih, b_ih), linear(h, w_hh, b_hh), h, identity, ACT_CODES[act], slope)
-
-
 
 
 def _gru_padded(w_ih, w_hh, b_ih, b_hh, C, Cp):
@@ -931,14 +902,14 @@ def _want_gru_ws(lib, N, C):
     return N > 0 and _o.GRU_WS == "1" and _lib.route_enabled("x3") and lib.glam_gru_ws_supported(C) == 1
 
 
-def _gru_pre(lib, scope, w_ih, w_hh, C, dev, st):
+def _gru_pre(lib, scope, w_ih, w_hh, C, st):
     """[2, bytes] uint8: the forward and the backward image of ``glam_gru_ws_make_pre`` for this pair of gate matrices — one launch per
     weight scope (a training step), shared by every application of the block and by its backward."""
     def build():
-        buf = torch.empty(2, lib.glam_gru_ws_pre_bytes(), dtype=torch.uint8, device=dev)
+        buf = _o.gru_pre_buffer(w_ih)
         lib.glam_gru_ws_make_pre(ptr(w_ih), ptr(w_hh), C, ptr(buf[0]), ptr(buf[1]), st)
         return buf
-    return _o._scoped(scope.fwd if scope else None, ("gru-pre", id(w_ih), id(w_hh)), w_ih, build)
+    return _o.scope_build(scope, "fwd", _o.gru_pre_key(w_ih, w_hh), w_ih, build)
 
 
 def gru_images_plain(N, C):
@@ -993,38 +964,30 @@ class _GruBlock(torch.autograd.Function):
         M = 3 * C
         lib, dev = _lib.api(), x.device
         f = dict(dtype=torch.float32, device=dev)
-        scope = _o._SCOPE
-
-        def image(w):
-            def build():
-                img = torch.empty(lib.glam_ts_gemm_image_bytes(C, M) // 4, **f)
-                lib.glam_ts_gemm_make_image(ptr(w), C, 1, C, M, ptr(img), stream())
-                return img
-            return _o._scoped(scope.fwd if scope else None, ("lin", id(w)), w, build)
+        scope = ctx.scope = _o._SCOPE
+        image = lambda w: _o.scoped_image(scope, _o.lin_image, w)
 
         st = stream()
         ws_route = _want_gru_ws(lib, N, C)
         # (the warp-specialised step: gi = the gates [r | z | n | gh_n], no gh — see ops.GRU_GATES)
         gates = bool(ws_route and _o.GRU_GATES)
         gi, gh = (torch.empty(N, 4 * C, **f), None) if gates else (torch.empty(N, M, **f), torch.empty(N, M, **f))
-        pre = _gru_pre(lib, scope, w_ih, w_hh, C, dev, st) if (ws_route and _o.GRU_PRE) else None
+        pre = _gru_pre(lib, scope, w_ih, w_hh, C, st) if (ws_route and _o.GRU_PRE) else None
         if scope is not None and pre is None:
             # all four images of the step (forward and input-gradient images of both gate matrices) in ONE launch, shared by the
             # message_steps applications of the block through the scope tables
-            ka, kb = ("lin", id(w_ih)), ("lin", id(w_hh))
-            ha, hb = scope.fwd.get(ka), scope.fwd.get(kb)
-            if not (ha is not None and ha[0] is w_ih and hb is not None and hb[0] is w_hh):
+            if scope.lookup(*_o.lin_image.entry(w_ih)) is None or scope.lookup(*_o.lin_image.entry(w_hh)) is None:
                 nf, nb = lib.glam_ts_gemm_image_bytes(C, M) // 4, lib.glam_ts_gemm_image_bytes(M, C) // 4
                 ia, ib, ta, tb = torch.empty(nf, **f), torch.empty(nf, **f), torch.empty(nb, **f), torch.empty(nb, **f)
                 if N > 0 and _want_gru_fused(N) and lib.glam_gru_fused_supported(C) and not _want_gru_ws(lib, N, C):
                     # ... and the two gate-padded images of the fused step: six re-layouts of the same two matrices, one launch
                     fused = torch.empty(2, lib.glam_gru_fused_image_bytes() // 4, **f)
                     lib.glam_gru_make_images(ptr(w_ih), ptr(w_hh), C, ptr(ia), ptr(ib), ptr(ta), ptr(tb), ptr(fused[0]), ptr(fused[1]), st)
-                    scope.fwd[("gru-fused", id(w_ih), id(w_hh))] = (w_ih, fused)
+                    scope.store("fwd", _o.gru_fused_key(w_ih, w_hh), w_ih, fused)
                 else:
                     lib.glam_ts_gemm_make_image_quad(ptr(w_ih), ptr(w_hh), C, M, ptr(ia), ptr(ib), ptr(ta), ptr(tb), st)
-                scope.fwd[ka], scope.fwd[kb] = (w_ih, ia), (w_hh, ib)
-                scope.bwd[ka], scope.bwd[kb] = (w_ih, ta), (w_hh, tb)
+                for kind, w, img in ((_o.lin_image, w_ih, ia), (_o.lin_image, w_hh, ib), (_o.lin_dx_image, w_ih, ta), (_o.lin_dx_image, w_hh, tb)):
+                    scope.store(*kind.entry(w), img)
         h_new, out = torch.empty_like(h), torch.empty_like(h)
         out_drop, eff = None, None
         if rng is None and act == ACT_CODES["rrelu"]:
@@ -1081,7 +1044,7 @@ class _GruBlock(torch.autograd.Function):
                 buf = torch.empty(2, nb, **f)
                 lib.glam_gru_fused_make_images(ptr(w_ih), ptr(w_hh), C, ptr(buf[0]), ptr(buf[1]), st)
                 return buf
-            imgs = _o._scoped(scope.fwd if scope else None, ("gru-fused", id(w_ih), id(w_hh)), w_ih, build_fused)
+            imgs = _o.scope_build(scope, "fwd", _o.gru_fused_key(w_ih, w_hh), w_ih, build_fused)
             if rng is None:
                 lib.glam_gru_fused_fwd(ptr(x), ptr(h), ptr(identity), ptr(imgs[0]), ptr(imgs[1]), ptr(b_ih), ptr(b_hh), N, C,
                                        int(celu_in), act, float(slope), ptr(gi), ptr(gh), ptr(h_new), ptr(out), st)
@@ -1113,7 +1076,6 @@ class _GruBlock(torch.autograd.Function):
                          and identity.stride() == h.stride())
         ctx.eff = eff
         ctx.cfg = (act, float(slope), identity is not None, bool(celu_in), None if rng is None else tuple(float(v) for v in rng))
-        ctx.scope = scope
         ctx.carried = carry is not None
         ctx.first_app = bool(first_app)
         return out, h_new, out_drop, (carry.view(-1) if ctx.carried else None)
@@ -1139,12 +1101,7 @@ class _GruBlock(torch.autograd.Function):
         d_id = torch.empty_like(h) if has_res else None
         scope = ctx.scope
 
-        def image_t(w):
-            def build():
-                img = torch.empty(lib.glam_ts_gemm_image_bytes(M, C) // 4, **f)
-                lib.glam_ts_gemm_make_image(ptr(w), C, 0, M, C, ptr(img), stream())
-                return img
-            return _o._scoped(scope.bwd if scope else None, ("lin", id(w)), w, build)
+        image_t = lambda w: _o.scoped_image(scope, _o.lin_dx_image, w)
 
         ws = gates or _want_gru_ws(lib, N, C)
         if ws:

@@ -4110,3 +4110,41 @@ def test_two_input_models_with_triplet_towers_and_node_products(device, monkeypa
     assert len(res[0]) == len(res[1]) > 5
     for i, (u, v) in enumerate(zip(*res)):
         assert torch.equal(u, v), i
+
+
+def test_prestaged_and_lazily_built_images_of_every_spec_are_the_same_bytes(device, monkeypatch):
+    """Every ``ops.ImageSpec`` constructor: the image that ``ops.scoped_image`` builds on first use (``k_ts_make_image``) and the one
+    ``ops.prestage`` builds from the same spec (one ``k_prestage`` launch per batch of at most six) are filed under the same table /
+    key / owner and hold the same bytes — the 15-column input weight in its 16-row image, the gate matrices of a GRU at C = 24 in
+    both directions, NNConv's ``[300, 60]`` relation operand, the four images of the wide layer at H = 3, Cp = 92."""
+    from glam_amd._lib import kernel_timer
+    monkeypatch.setattr(ops, "PRESTAGE", True)
+    torch.manual_seed(3)
+    lib = ops._lib.load()
+    rnd = lambda *shape: torch.randn(*shape, device=device)
+    w15, w_ih, w_hh, rel, wn = rnd(60, 15), rnd(72, 24), rnd(72, 24), rnd(300, 60), rnd(90, 270)
+    H, Cp, Dp = 3, 92, 4
+    Wcat, Ws_p = ops._plain_views(rnd(lib.glam_triplet_plain_floats(H, Cp, Dp)), H, Cp, Dp)[:2]
+    batches = [[ops.lin_image(w15, 16), ops.lin_image(w_ih), ops.lin_image(w_hh), ops.lin_dx_image(w_ih), ops.lin_dx_image(w_hh),
+                ops.tall_image(rel)],
+               [ops.wide_node_image(wn, W=Wcat), ops.wide_upd_image(wn, W=Ws_p), ops.wide_dagg_image(wn, W=Ws_p), ops.wide_dx_image(wn, W=Wcat),
+                ops.tall_dx_image(rel)]]
+    kinds = [[ops.lin_image] * 3 + [ops.lin_dx_image] * 2 + [ops.tall_image],
+             [ops.wide_node_image, ops.wide_upd_image, ops.wide_dagg_image, ops.wide_dx_image, ops.tall_dx_image]]
+    lazily = lambda scope, kind, s: ops.scoped_image(scope, kind, s.owner, s.Kimg, s.W)      # (as the ops call it)
+    with kernel_timer() as kt:
+        for specs, ks in zip(batches, kinds):
+            with ops.weight_scope():
+                assert ops.prestage(None, specs) == len(specs) and ops.prestage(None, specs) == 0
+                pre = [ops._SCOPE.lookup(s.table, s.key, s.owner) for s in specs]
+                assert all(lazily(ops._SCOPE, k, s) is img for k, s, img in zip(ks, specs, pre))       # the op's lookup finds them
+            with ops.weight_scope():
+                lazy = [lazily(ops._SCOPE, k, s) for k, s in zip(ks, specs)]
+                assert all(ops._SCOPE.lookup(s.table, s.key, s.owner) is img for s, img in zip(specs, lazy))
+            for k, s, a, c in zip(ks, specs, pre, lazy):
+                assert a is not c and a.numel() == c.numel() == lib.glam_ts_gemm_image_bytes(s.Kimg, s.M) // 4 > 0
+                assert torch.equal(a, c) and bool((a != 0).any()), s.key
+                assert torch.equal(lazily(None, k, s), a)                                                # no scope: built on the spot
+    names = [r[0] for r in kt.records()]
+    assert sum("k_prestage" in n for n in names) == len(batches), names
+    assert all("k_prestage" in n or "k_ts_make_image" in n for n in names) and len(names) == 2 + 2 * sum(len(b) for b in batches), names

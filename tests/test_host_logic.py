@@ -706,3 +706,78 @@ def test_tensor_side_tables_of_ops_keep_their_hit_conditions(monkeypatch):
     monkeypatch.setattr(ops, "NODE_IN_GRU", True)
     rows.add_(1.0)
     assert ops.take_node_product(rows, staged) is None
+
+
+def test_weight_scope_interface_and_entry_constructors():
+    """ops._WeightScope on CPU tensors with a fake ``build_fn``: ``lookup`` misses when another object sits under the key (a reused
+    ``id()``: what the owner pin is for), ``build`` builds once per (table, key, owner) and every time without a scope, the two tables
+    are separate, ``weight_scope()`` clears "fwd" on exit and keeps "bwd"; every key / image constructor gives equal keys for the same
+    tensors and different keys for different ones."""
+    calls = []
+
+    def build_fn():
+        calls.append(1)
+        return len(calls)
+
+    a, b = torch.zeros(2), torch.zeros(2)
+    scope = ops._WeightScope()
+    assert scope.lookup("fwd", ("k", 7), a) is None
+    scope.store("fwd", ("k", 7), a, "va")
+    assert scope.lookup("fwd", ("k", 7), a) == "va" and scope.lookup("fwd", ("k", 7), b) is None      # same key, another owner
+    assert scope.lookup("bwd", ("k", 7), a) is None                                                   # separate tables
+    assert scope.build("fwd", ("n", 1), a, build_fn) == 1 and scope.build("fwd", ("n", 1), a, build_fn) == 1 and len(calls) == 1
+    assert scope.build("bwd", ("n", 1), a, build_fn) == 2 and scope.build("fwd", ("n", 2), a, build_fn) == 3
+    assert scope.build("fwd", ("n", 1), b, build_fn) == 4 and scope.lookup("fwd", ("n", 1), a) is None       # the new owner took the slot
+    assert ops.scope_build(scope, "bwd", ("n", 1), a, build_fn) == 2 and len(calls) == 4
+    assert ops.scope_build(None, "fwd", ("n", 1), a, build_fn) == 5 and ops.scope_build(None, "fwd", ("n", 1), a, build_fn) == 6
+    assert ops.scoped_weights(("n", 1), a, build_fn) == 7 and ops.scoped_weights(("n", 1), a, build_fn) == 8      # no active scope
+    with ops.weight_scope():
+        inner = ops._SCOPE
+        assert ops.scoped_weights(("n", 1), a, build_fn) == 9 and ops.scoped_weights(("n", 1), a, build_fn) == 9
+        inner.store("bwd", ("t", 1), a, "kept")
+        assert inner.lookup("fwd", ("n", 1), a) == 9
+    assert ops._SCOPE is None and inner.lookup("fwd", ("n", 1), a) is None and inner.lookup("bwd", ("t", 1), a) == "kept"
+
+    t = [torch.zeros(8, 4) for _ in range(6)]
+    keys = []
+    for make, n in ((ops.triplet_key, 5), (lambda *ts: ops.triplet_key(*ts, plain=True), 5), (ops.triplet_ell_key, 1), (ops.gru_pre_key, 2),
+                    (ops.gru_fused_key, 2), (ops.gru_pad_key, 4), (lambda w: ops.lin_image(w)[:2], 1), (lambda w: ops.lin_dx_image(w)[:2], 1),
+                    (lambda w: ops.tall_image(w)[:2], 1), (lambda w: ops.tall_dx_image(w)[:2], 1)) + \
+            tuple((lambda w, k=k: k(w, W=t[5])[:2], 1) for k in (ops.wide_node_image, ops.wide_upd_image, ops.wide_dagg_image, ops.wide_dx_image)):
+        assert make(*t[:n]) == make(*t[:n])
+        for i in range(n):          # any one tensor replaced: another key
+            assert make(*(t[:i] + [t[n]] + t[i + 1:n])) != make(*t[:n])
+        keys.append(make(*t[:n]))
+    assert len(set(keys)) == len(keys)       # no two kinds share a (table, key) for the same tensors
+
+
+def test_image_specs_reproduce_the_tuples_the_ops_and_the_prestage_lists_were_written_with():
+    """The ``ImageSpec`` constructors against the 9-tuples ``(table, key, owner, W, ldw, transW, K, M, K_image)`` written out by hand for
+    the shapes in use: the input linear 15 -> 60 on 16 zero-padded columns, the GRU's gate matrices at C = 60, the four images of
+    the wide layer at H = 3, Cp = 92."""
+    def same(spec, want):
+        return len(spec) == len(want) == 9 and all((a is b) if isinstance(b, torch.Tensor) else (a == b and type(a) is type(b))
+                                                   for a, b in zip(spec, want))
+
+    w = torch.zeros(60, 15)
+    assert same(ops.lin_image(w, 16), ("fwd", ("lin", id(w)), w, w, 15, 1, 15, 60, 16))
+    g = torch.zeros(180, 60)
+    assert same(ops.lin_image(g), ("fwd", ("lin", id(g)), g, g, 60, 1, 60, 180, 60))
+    assert same(ops.lin_dx_image(g), ("bwd", ("lin", id(g)), g, g, 60, 0, 180, 60, 180))
+    r = torch.zeros(300, 60)              # NNConv's relation product, stored [K, M]
+    assert same(ops.tall_image(r), ("fwd", ("tall-fwd", id(r)), r, r, 60, 0, 300, 60, 300))
+    assert same(ops.tall_dx_image(r), ("bwd", ("tall-dx", id(r)), r, r, 60, 1, 60, 300, 60))
+    H, Cp, Dp = 3, 92, 4
+    HC = H * Cp
+    wn = torch.zeros(90, 270)
+    Wcat, Ws_p = ops._plain_views(torch.zeros(Cp * (HC + 8) + HC * Cp + Dp * HC + Dp * 4 + Cp), H, Cp, Dp)[:2]
+    assert (Wcat.stride(0), Ws_p.stride(0)) == (284, 92)
+    node, upd = ops.wide_node_image(wn, W=Wcat), ops.wide_upd_image(wn, W=Ws_p)
+    dagg, dx = ops.wide_dagg_image(wn, W=Ws_p), ops.wide_dx_image(wn, W=Wcat)
+    assert ops.wide_dx_image.entry(wn) == dx[:3] and ops.lin_image.entry(w) == ops.lin_image(w, 16)[:3]      # what a hit looks up
+    assert same(node, ("fwd", ("wide-img-node", id(wn)), wn, Wcat, Wcat.stride(0), 0, Cp, HC + 8, Cp))
+    assert same(dagg, ("bwd", ("wide-img-dagg", id(wn)), wn, Ws_p, Ws_p.stride(0), 1, Cp, HC, Cp))
+    assert same(upd, ("fwd", ("wide-img-upd", id(wn)), wn, Ws_p, Ws_p.stride(0), 0, HC, Cp, HC))
+    assert same(dx, ("bwd", ("wide-img-dx", id(wn)), wn, Wcat, Wcat.stride(0), 1, HC + 8, Cp, HC + 8))
+    # the prestage list of a tower is made of the same specs (CPU tensors stage nothing: see test_launch_saving_hints_are_host_logic)
+    assert isinstance(node, tuple) and node.Kimg == Cp and node.table == "fwd"

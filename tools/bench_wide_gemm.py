@@ -7,7 +7,7 @@ dev = torch.device("cuda")
 N = 20700
 for K, M in [(92, 284), (92, 276), (60, 188), (180, 60)]:   # (276, 92) / (284, 92): no kernel variant (library GEMM wins)
     A = torch.randn(N, K, device=dev); W = torch.randn(K, M, device=dev)
-    img = ops._ts_image(W, K, M, False)
+    img = ops.scoped_image(None, ops.tall_image, W)
     out = torch.empty(N, M, device=dev)
     def f(): _lib.check(lib.glam_ts_gemm(_lib.ptr(A), K, K, None, 0, 0, _lib.ptr(img), None, _lib.ptr(out), M, M, None, 0, 0, N, _lib.stream()), "g")
     def g(): torch.matmul(A, W, out=out)

@@ -1182,6 +1182,13 @@ def dot_and_global_pool2_indexed(mol_out, pro_out, mol_batch, pro_sp, pro_of_pai
     return ops.pair_pool_indexed(mol_out, pro_out, ops.segment_ptr(mol_batch), pro_sp, pro_of_pair, return_argmax)
 
 
+def dot_and_global_pool2_panel(mol_out, pro_out, mol_batch, pro_sp, plan, molsum=None, prosum=None, return_argmax=False):
+    """``dot_and_global_pool2_indexed`` for a PANEL: every ligand of ``mol_batch`` against every protein segment ``plan.sel[j]`` of
+    ``pro_sp`` -> ``[L, Qs, 2]`` from one protein-stationary launch (``ops.pair_pool_panel``; ``ops.panel_plan`` for the plan; ``prosum``:
+    the column sums of the encoded proteins, kept with them).  Inference only; the rows flow as they are."""
+    return ops.pair_pool_panel(mol_out, pro_out, ops.segment_ptr(mol_batch), pro_sp, plan, molsum, prosum, return_argmax)
+
+
 def dot_and_global_pool2_shared(mol_out, pro_out, mol_batch, pro_sp, pro_of_pair=None, with_identity=False):
     """``dot_and_global_pool2_indexed`` for TRAINING: the same forward with a backward (``ops.pair_pool_shared``) — a protein's residue
     rows collect the gradients of every pair that points at it.  ``with_identity`` as in ``dot_and_global_pool2``."""

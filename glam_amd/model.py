@@ -19,6 +19,7 @@ from .layer import _None  # noqa: F401
 from .layer import GlobalPool5, GlobalLAPool, Set2Set  # noqa: F401  (resolved from config strings)
 from .layer import LinearBlock, MessageBlock, dot_and_global_pool2, first_node_spec, flat_then_head, following_dropout, prestage_pass
 from .layer import _BatchNorm, _LayerNorm, _PairNorm, dot_and_global_pool2_gather, dot_and_global_pool2_indexed, dot_and_global_pool2_shared
+from .layer import dot_and_global_pool2_panel
 
 
 def model_args(args):
@@ -105,11 +106,38 @@ _PER_ROW_NORMS = (_None, _BatchNorm)                               # the *_flat 
 class ProteinEncoding:
     """What ``ArchitectureDTI.encode_proteins`` keeps of ``Q`` protein graphs for ``screen``: ``rows[s]`` the residue rows after
     message step ``s`` (contiguous, as the fusion reads them), ``sp`` their ``SegmentPtr``, ``flat`` = ``pro_flat(pro_readout(.))``
-    ``[Q, hid]``, ``num_graphs`` = Q, and the stamp of the protein-side parameters it was computed from (``model`` is a weak reference)."""
+    ``[Q, hid]``, ``num_graphs`` = Q, and the stamp of the protein-side parameters it was computed from (``model`` is a weak reference).
+
+    What the first ``screen_panel`` call on it adds (``panel()``; ``encode_proteins`` and ``screen`` never touch these): ``sizes_host``, the
+    proteins' residue counts on the host — ONE read-back of ``sp.ptr`` per encoding, never per batch; ``prosum[s]`` ``[Q, hid]``, the column
+    sums of ``rows[s]`` per protein (the mean column's protein half); ``plans``, a small cache of ``ops.PanelPlan`` keyed by the selection."""
+
+    _MAX_PLANS = 16
 
     def __init__(self, model, rows, sp, flat, stamp):
         self.model, self.rows, self.sp, self.flat, self.stamp = weakref.ref(model), rows, sp, flat, stamp
         self.num_graphs = sp.B
+        self.sizes_host, self.prosum, self.plans = None, None, {}
+
+    def panel(self, proteins=None):
+        """``ops.PanelPlan`` of the selection ``proteins`` (``ops.panel_plan``: ``None`` = every protein in order) — from the cache when this
+        selection was planned before — after filling ``sizes_host`` (the one read-back) and ``prosum`` (one segment-sum launch per step) if
+        this is the encoding's first panel call.  The selection is validated on the host before anything is launched or read back."""
+        # (validated on the host first — the sizes play no part in that — and before the read-back below)
+        sel = None if proteins is None else ops.panel_plan([0] * self.num_graphs, proteins).sel
+        key = None if sel is None else tuple(sel.tolist())
+        plan = self.plans.get(key)
+        if plan is None:
+            if self.sizes_host is None:
+                ptr = self.sp.ptr.cpu().numpy().astype("int64")
+                self.sizes_host = ptr[1:] - ptr[:-1]
+            plan = ops.panel_plan(self.sizes_host, sel)
+            while len(self.plans) >= self._MAX_PLANS:
+                self.plans.pop(next(iter(self.plans)))
+            self.plans[key] = plan
+        if self.prosum is None:
+            self.prosum = [ops.segment_pool(r, self.sp, "sum") for r in self.rows]
+        return plan
 
 
 class ArchitectureDTI(torch.nn.Module):
@@ -242,6 +270,57 @@ class ArchitectureDTI(torch.nn.Module):
             outm = self.mol_flat(self.mol_readout(xm, data_mol.batch, nm))
             outp = enc.flat.index_select(0, index.on(enc.flat.device))
             out = self.lin_out1(self.lin_out0(ops.cat_cols([outm, outp] + fusion)))
+        return (out, contacts) if return_argmax else out
+
+    def _panel_head_in_one_pass(self):
+        """Whether the head may run once over the ``L * Qs`` rows of a panel: both of its norms are per row in ``eval()`` (``_None``,
+        ``_BatchNorm`` on running statistics).  The batch-less ``_LayerNorm`` / ``_PairNorm`` / ``_GraphSizeNorm`` take statistics (or the
+        row count) over the whole matrix they are given, so they must see one protein column ``[L, .]`` at a time, as in ``screen``."""
+        return type(self.lin_out0.norm) in _PER_ROW_NORMS and type(self.lin_out1.norm) in _PER_ROW_NORMS
+
+    def screen_panel(self, data_mol, enc, proteins=None, return_argmax=False):
+        """``[L, Qs, out_dim]``: column ``j`` is ``screen(data_mol, enc, pro_of_pair=[proteins[j]] * L)`` — every ligand of ``data_mol``
+        against every protein of the selection — from ONE pass of the ligand tower and one protein-stationary fusion per step
+        (``ops.pair_pool_panel`` on ``enc.rows[step]``).  Every step's fusion max and the contacts equal those of the ``screen`` calls
+        bit for bit; the output sits within the fp32 parity bound of ``model(data_mol, B_pro)`` on the expanded batch.
+        ``proteins``: host integers in ``[0, Q)``, any order, duplicates allowed (``ops.panel_plan``); ``None`` = all ``Q`` in order.
+        ``return_argmax``: also the per-step ``[L, Qs, 2]`` int32 contacts (row of ``data_mol.x``, row of the encoded proteins).
+        The first call on an encoding reads the proteins' sizes back once and sums their rows per step (``ProteinEncoding.panel``);
+        after it, a call on the same encoding and selection does no host synchronisation of its own."""
+        self._screen_guard("screen_panel")
+        if not isinstance(enc, ProteinEncoding) or enc.model() is not self:
+            raise GlamHipError("screen_panel: the encoding was made by another model (its residue rows are that model's): encode_proteins() on this one")
+        if enc.stamp != self._protein_stamp() or len(enc.rows) != self.message_steps:
+            raise GlamHipError("screen_panel: the encoding is stale — a protein-side parameter or buffer (pro_lin0 / pro_conv / pro_readout / "
+                               "pro_flat) was written since encode_proteins(): encode again")
+        plan = enc.panel(proteins)                                 # host-side checks, before the first launch
+        nm = getattr(data_mol, "num_graphs", None) or None
+        msp = ops.segment_ptr(data_mol.batch, nm)
+        L, Qs = msp.B, plan.Qs
+        with ops.weight_scope():
+            prestage_pass((self.mol_lin0, self.mol_conv, data_mol.x, data_mol.edge_attr))
+            xm = self.mol_lin0(data_mol.x, batch=data_mol.batch)
+            hm, fusion, contacts = None, [], []
+            for i in range(self.message_steps):
+                with ops.block_feeds_itself(i + 1 < self.message_steps):
+                    xm, hm = self.mol_conv(xm, data_mol.edge_index, data_mol.edge_attr, h=hm, batch=data_mol.batch)
+                f = dot_and_global_pool2_panel(xm, enc.rows[i], data_mol.batch, enc.sp, plan, None, enc.prosum[i], return_argmax)
+                if return_argmax:
+                    f, a = f
+                    contacts.append(a)
+                fusion.append(f)
+            outm = self.mol_flat(self.mol_readout(xm, data_mol.batch, nm))
+            outp = enc.flat.index_select(0, plan.on(enc.flat.device)[0].long())                   # [Qs, hid]
+            if L == 0 or Qs == 0:
+                out = outm.new_zeros(L, Qs, self.lin_out1.linear.out_features)
+            elif self._panel_head_in_one_pass():
+                # ligand-major rows: row l * Qs + j = cat[outm[l], flat[sel[j]], fusion_0[l, j], ...]
+                rows = ops.cat_cols([outm.repeat_interleave(Qs, 0), outp.repeat(L, 1)] + [f.reshape(L * Qs, 2) for f in fusion])
+                out = self.lin_out1(self.lin_out0(rows)).view(L, Qs, -1)
+            else:
+                cols = [self.lin_out1(self.lin_out0(ops.cat_cols([outm, outp[j:j + 1].expand(L, -1).contiguous()]
+                                                                 + [f[:, j].contiguous() for f in fusion]))) for j in range(Qs)]
+                out = torch.stack(cols, 1)
         return (out, contacts) if return_argmax else out
 
     # ---- training on shared proteins: the protein tower runs once per DISTINCT protein of the step ----------------------------

@@ -748,6 +748,139 @@ def pair_pool_indexed(mol_out, pro_out, msp, psp, pro_of_pair=None, return_argma
 
 
 # --------------------------------------------------------------------------------------
+# panel screening: every ligand against every selected protein, protein-stationary (csrc/pairpanel.hip, glam_pair_pool_panel_fwd)
+# --------------------------------------------------------------------------------------
+PANEL_CHUNK = 64      # residue rows per chunk (one per lane of the wave that holds them) = kPanelChunk of csrc/pairpanel.hip
+
+
+class PanelPlan:
+    """The work of one panel call over a validated selection: ``sel`` int32 ``[Qs]`` (every entry in ``[0, Q)``) and ``work`` int32
+    ``[4 * total_chunks + Qs + 1]`` — per chunk of 64 residue rows, in selection order, ``(j, first row of the chunk in the encoding,
+    rows in the chunk, index of its partials in the workspace)``, then ``chunk_ptr[Qs + 1]``, the offsets of the selections' chunk
+    runs (``chunks`` / ``chunk_ptr`` are views of it).  Host numpy; ``on(device)`` -> ``(sel, work)`` on the device, made once per
+    device (one copy out of pinned memory, only enqueued) and shared by every launch that reads them."""
+
+    def __init__(self, sel, sizes):
+        self.sel, self.Qs, self.Q = sel, int(sel.shape[0]), int(sizes.shape[0])
+        first = np.zeros(self.Q + 1, dtype=np.int64)
+        np.cumsum(sizes, out=first[1:])
+        if int(first[-1]) >= 2 ** 31 - 1:
+            raise IndexError("panel_plan: the proteins hold 2^31 residue rows or more")
+        self.N = int(first[-1])
+        n_chunks = (sizes[sel] + PANEL_CHUNK - 1) // PANEL_CHUNK                     # per selection
+        chunk_ptr = np.zeros(self.Qs + 1, dtype=np.int64)
+        np.cumsum(n_chunks, out=chunk_ptr[1:])
+        self.total_chunks = T = int(chunk_ptr[-1])
+        if T >= 2 ** 31 - 1:
+            raise IndexError("panel_plan: the selection has 2^31 chunks or more")
+        j = np.repeat(np.arange(self.Qs, dtype=np.int64), n_chunks)
+        c = np.arange(T, dtype=np.int64) - chunk_ptr[j]                              # chunk inside its protein
+        table = np.empty((T, 4), dtype=np.int32)
+        table[:, 0] = j
+        table[:, 1] = first[sel[j]] + PANEL_CHUNK * c
+        table[:, 2] = np.minimum(sizes[sel[j]] - PANEL_CHUNK * c, PANEL_CHUNK)
+        table[:, 3] = np.arange(T)
+        self.work = np.concatenate([table.reshape(-1), chunk_ptr.astype(np.int32)])
+        self.chunks, self.chunk_ptr = self.work[:4 * T].reshape(T, 4), self.work[4 * T:]
+        self._dev = {}
+
+    def on(self, device):
+        device = torch.device(device)
+        t = self._dev.get(device)
+        if t is None:
+            both = _stage_int32(np.concatenate([self.sel, self.work]), device, "the panel's selection and work table")      # (one copy)
+            t = self._dev[device] = (both[:self.Qs], both[self.Qs:])
+        return t
+
+
+def panel_plan(sizes_host, proteins=None):
+    """``PanelPlan`` of the selection ``proteins`` over ``Q = len(sizes_host)`` proteins of ``sizes_host[q]`` residue rows — host only
+    (numpy), before anything is launched (the kernel trusts the table; the policy of ``pair_index``).  ``proteins``: ``None`` = all
+    ``Q`` in order, or a host sequence / numpy array / CPU tensor of integers in ``[0, Q)``, in any order, duplicates allowed;
+    ``IndexError`` for a wrong dtype or an entry outside ``[0, Q)``; a device tensor is refused (validating it would be a hidden
+    read-back)."""
+    if torch.is_tensor(sizes_host):
+        if sizes_host.device.type != "cpu":
+            raise GlamHipError("panel_plan: the proteins' sizes live on a device: the plan is built on the host — pass their host copy")
+        sizes_host = sizes_host.detach().numpy()
+    sizes = np.asarray(sizes_host)
+    if sizes.size == 0:
+        sizes = np.zeros(0, dtype=np.int64)
+    if sizes.dtype.kind not in "iu" or sizes.ndim != 1 or (sizes.size and int(sizes.min()) < 0):
+        raise IndexError("panel_plan: the proteins' sizes must be a vector of non-negative integers")
+    sizes = sizes.astype(np.int64)
+    Q = int(sizes.shape[0])
+    if proteins is None:
+        return PanelPlan(np.arange(Q, dtype=np.int32), sizes)
+    if torch.is_tensor(proteins):
+        if proteins.device.type != "cpu":
+            raise GlamHipError("proteins lives on a device: it is validated on the host before the launch, which would be a hidden "
+                               "read-back — pass the host sequence / numpy array / CPU tensor it was made from")
+        proteins = proteins.detach().numpy()
+    sel = np.asarray(proteins)
+    if sel.size == 0:
+        sel = np.zeros(0, dtype=np.int64)
+    if sel.dtype.kind not in "iu":
+        raise IndexError(f"proteins must hold integers, got {sel.dtype}")
+    if sel.ndim != 1:
+        raise IndexError(f"proteins must be a vector of protein numbers: shape {tuple(sel.shape)}")
+    if sel.size and (int(sel.min()) < 0 or int(sel.max()) >= Q):
+        raise IndexError(f"proteins must lie in [0, {Q}): got {int(sel.min())} .. {int(sel.max())}")
+    return PanelPlan(sel.astype(np.int32), sizes)
+
+
+def pair_pool_panel(mol_out, pro_out, msp, psp, plan, molsum=None, prosum=None, return_argmax=False, slab=0):
+    """``[max, mean]`` of ``mol[seg_l] @ pro[seg_q].T`` for EVERY ligand ``l`` and every selected protein ``q = plan.sel[j]`` ->
+    ``[L, Qs, 2]``: the panel of ``Qs`` calls of ``pair_pool_indexed`` with ``pro_of_pair = [sel[j]] * L`` from one protein-stationary
+    launch (+ a finish launch).  The max column — and with ``return_argmax`` the ``[L, Qs, 2]`` int32 rows of the maximum in ``mol_out``
+    / ``pro_out`` (-1 for an empty ligand or protein) — is bit for bit that of those calls; the mean is ``<molsum[l], prosum[q]> /
+    (n_l n_q)`` and within the fp64-twin bound.  ``plan``: ``panel_plan`` over the sizes of ``psp``'s segments.  ``molsum`` ``[L, D]``
+    / ``prosum`` ``[Q, D]``: the segments' column sums (``segment_pool(x, sp, "sum")``), computed here when missing — a caller that
+    keeps the proteins keeps ``prosum`` too.  ``slab``: ligands per wave, 0 = the library chooses.  Widths 1..128.  Inference only:
+    there is no backward (training is ``ops.pair_pool`` / ``ops.pair_pool_shared``)."""
+    if not isinstance(plan, PanelPlan):
+        raise GlamHipError("pair_pool_panel: plan must come from ops.panel_plan (the kernel trusts its table)")
+    L, Q, Qs = msp.B, psp.B, plan.Qs
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (mol_out, pro_out, molsum, prosum)):
+        raise GlamHipError("pair_pool_panel is inference only (no backward): call it under torch.no_grad(); the training routes are "
+                           "ops.pair_pool on one protein graph per pair and ops.pair_pool_shared on proteins held once")
+    if plan.Q != Q or plan.N != psp.N:
+        raise GlamHipError(f"pair_pool_panel: the plan was made for {plan.Q} proteins of {plan.N} residue rows, the encoding holds {Q} of {psp.N}")
+    require_device(mol_out, pro_out)
+    if (mol_out.dim() != 2 or pro_out.dim() != 2 or mol_out.size(1) != pro_out.size(1) or mol_out.size(0) != msp.N
+            or pro_out.size(0) != psp.N):
+        raise GlamHipError(f"pair_pool_panel: the two sides disagree (width / node count): mol {tuple(mol_out.shape)} for {msp.N} rows, "
+                           f"pro {tuple(pro_out.shape)} for {psp.N} rows")
+    D = mol_out.size(1)
+    for name, t, rows in (("molsum", molsum, L), ("prosum", prosum, Q)):
+        if t is not None and (t.dim() != 2 or tuple(t.shape) != (rows, D) or t.device != mol_out.device):
+            raise GlamHipError(f"pair_pool_panel: {name} must be the [{rows}, {D}] column sums on {mol_out.device}, got {tuple(t.shape)} on {t.device}")
+    if int(slab) < 0:
+        raise GlamHipError(f"pair_pool_panel: slab must be 0 (choose) or the ligands per wave, got {slab}")
+    lib = _lib.api()
+    if _lib.load().glam_pair_pool_panel_supported(D) != 0:          # (a status: the raw binding hands it back)
+        raise GlamHipError(f"pair_pool_panel: width {D} is outside the kernel table (1..128)")
+    mol, pro = f32c(mol_out, "mol_out"), f32c(pro_out, "pro_out")
+    dev = mol.device
+    out = torch.empty(L, Qs, 2, dtype=torch.float32, device=dev)
+    arg = torch.empty(L, Qs, 2, dtype=torch.int32, device=dev) if return_argmax else None
+    if L == 0 or Qs == 0:
+        return (out, arg) if return_argmax else out
+    if msp.N == 0 or psp.N == 0:          # no row on one side: every pair is empty (and the empty matrix has no address to pass)
+        out.zero_()
+        if return_argmax:
+            arg.fill_(-1)
+        return (out, arg) if return_argmax else out
+    molsum =f32c(molsum, "molsum") if molsum is not None else segment_pool(mol, msp, "sum")
+    prosum = f32c(prosum, "prosum") if prosum is not None else segment_pool(pro, psp, "sum")
+    sel, work = plan.on(dev)
+    ws = torch.empty(max(lib.glam_pair_pool_panel_workspace_bytes(plan.total_chunks, L), 16), dtype=torch.uint8, device=dev)
+    lib.glam_pair_pool_panel_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(work), plan.total_chunks, ptr(sel), Qs, L, Q, D,
+                                 ptr(molsum), ptr(prosum), int(slab), ptr(out), ptr(arg), ptr(ws), ws.numel(), stream())
+    return (out, arg) if return_argmax else out
+
+
+# --------------------------------------------------------------------------------------
 # training against proteins held once: the indexed fusion with a backward (csrc/pairshared.hip)
 # --------------------------------------------------------------------------------------
 class _PairPoolShared(torch.autograd.Function):

@@ -622,6 +622,25 @@ size_t glam_pair_pool_gather_load_bytes(const float* x1, const float* x2, int D)
 int glam_pair_pool_gather_fwd(const float* x1, const float* x2, const int32_t* ptr1, const int32_t* ptr2, const int32_t* idx1,
                               const int32_t* idx2, int64_t P, int64_t Q1, int64_t Q2, int D, float* out, int32_t* argmax, void* stream);
 
+/* Panel screening (inference): EVERY ligand segment l = 0..L-1 of mol (mol_ptr int32[L+1]) against every selected protein segment
+ * sel[j], j = 0..Qs-1 (int32[Qs], entries in [0, Q), any order, duplicates allowed), of pro (pro_ptr int32[Q+1], each protein held once):
+ * out f32[L,Qs,2] = [max, mean]; argmax int32[L,Qs,2] (row of mol, row of pro; may be NULL); an empty ligand or protein gives 0, 0 and
+ * -1, -1.  The max and argmax are bit for bit those of glam_pair_pool_indexed_fwd with pro_of_pair = [sel[j]] * L; the mean is
+ * <molsum[l], prosum[sel[j]]> / (n_l * n_res), one ascending fmaf chain over the D columns (molsum f32[L,D], prosum f32[Q,D]: the column
+ * sums of the segments, computed by the caller).  Protein-stationary grid (csrc/pairpanel.hip): one wave per (chunk of 64 residue rows of
+ * a selected protein, slab of ligands) + a finish launch.  work int32[4 * total_chunks + Qs + 1], built and checked by the caller and
+ * trusted here: per chunk, in selection order, (j, first row of the chunk in pro, rows in the chunk (1..64), index of its partials in
+ * the workspace), then chunk_ptr[Qs+1], the offsets of the selections' chunk runs.  slab: ligands per wave, 0 = choose (about 4 096 waves
+ * where the problem has them, never fewer than 4 ligands per wave).  Workspace: glam_pair_pool_panel_workspace_bytes(total_chunks, L).
+ * D in 1..128, else GLAM_E_UNSUPPORTED; glam_pair_pool_panel_supported(D) is that check alone and returns a STATUS: GLAM_OK when the
+ * width has a kernel, GLAM_E_UNSUPPORTED otherwise.  L == 0 or Qs == 0: GLAM_OK, nothing launched.  Forward only. */
+size_t glam_pair_pool_panel_workspace_bytes(int64_t total_chunks, int64_t L);
+int glam_pair_pool_panel_supported(int D);
+int glam_pair_pool_panel_fwd(const float* mol, const float* pro, const int32_t* mol_ptr, const int32_t* pro_ptr, const int32_t* work,
+                             int64_t total_chunks, const int32_t* sel, int64_t Qs, int64_t L, int64_t Q, int D, const float* molsum,
+                             const float* prosum, int slab, float* out, int32_t* argmax, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
 /* Training-mode block tails of the reference's DEFAULT configuration (src_1gp/model.py:30-31, run.py:35-37: RReLU activations,
  * Dropout(0.2) in front of every conv) — the same launches as glam_gru_tail_* / glam_bias_res_act_* with two additions:
  *   act = 4: torch.nn.RReLU in training mode, out = y > 0 ? y : a * y with a ~ U(rr_lower, rr_upper) per element;

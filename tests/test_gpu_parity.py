@@ -2026,7 +2026,11 @@ def test_rrelu_and_dropout_device_stream_statistics(device):
     """torch.nn.RReLU(1/8, 1/3) in training mode multiplies every non-positive input by a ~ U(lower, upper); Dropout(p) zeroes with
     probability p and scales the rest by 1 / (1 - p).  The HIP ops draw from a device-side Philox stream: the numbers differ
     from torch's generator, so parity is statistical (moments, range, uniformity, independence between launches), the
-    backward must use exactly the numbers of its forward, and a re-seeded stream must replay."""
+    backward must use exactly the numbers of its forward, and a re-seeded stream must replay.
+
+    The exact counterpart: tests/test_gpu_training_noise.py regenerates the stream on the host (tests/philox_twin.py) and holds every
+    training-mode kernel to the slope and the mask of each element, bit for bit; tests/test_philox_twin_host.py asks these statistics of
+    that twin."""
     n = 1 << 20
     x = torch.full((n // 64, 64), -1.0, device=device, requires_grad=True)
     ops.manual_seed(1234)

@@ -587,7 +587,9 @@ _ACTS = {"none": lambda t, s: t, "relu": lambda t, s: F.relu(t), "leaky": lambda
 @pytest.mark.parametrize("act", ["none", "relu", "leaky", "celu"])
 @pytest.mark.parametrize("C", [15, 60, 130])
 def test_bias_res_act(device, C, act, has_bias, has_id):
-    """``k_bias_res_act_fwd/bwd`` (the GCN / GAT block tail ``act(y + bias + identity)``), every activation code but rrelu.  A quarter
+    """``k_bias_res_act_fwd/bwd`` (the GCN / GAT block tail ``act(y + bias + identity)``), the four deterministic activation codes; the
+    rrelu code — and Dropout behind every code — is covered under its exact noise by ``test_elementwise_*`` in
+    tests/test_gpu_training_noise.py (``glam_bias_res_act_rng_fwd / _bwd``).  A quarter
     of the pre-activations are exactly 0 (and -0.0 without bias / identity): the derivative the backward takes from ``out`` must follow
     torch's convention at 0 (ReLU 0, LeakyReLU ``slope``, CELU 1).  Values are multiples of 1/8, so the zeros are exact in any order."""
     torch.manual_seed(C)

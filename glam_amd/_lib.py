@@ -69,6 +69,8 @@ SIGNATURES = {
     "glam_pair_rows_bwd": (_i32, [_vp] * 3 + [_i64, _i64, _i32, _vp, _vp]),
     "glam_pair_pool_gather_load_bytes": (_sz, [_vp, _vp, _i32]),
     "glam_pair_pool_gather_fwd": (_i32, [_vp] * 6 + [_i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "glam_pair_pool_gather_train_fwd": (_i32, [_vp] * 6 + [_i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "glam_pair_pool_gather_bwd": (_i32, [_vp] * 13 + [_i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "glam_pair_pool_panel_workspace_bytes": (_sz, [_i64, _i64]),
     "glam_pair_pool_panel_supported": (_i32, [_i32]),
     "glam_pair_pool_panel_fwd": (_i32, [_vp] * 5 + [_i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),

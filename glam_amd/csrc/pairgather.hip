@@ -18,6 +18,8 @@
 // order: the max column and the argmax are bit for bit those of glam_pair_pool_fwd on physically gathered rows whatever the order of
 // the reduction.  Mean: sum(S) = <sum of rows of segment 1, sum of rows of segment 2>; lane c keeps columns c and c + 64 of both sums
 // (rows added in ascending order), the products are summed by the fixed butterfly of group_sum<64>: the same bits on every run.
+// Training (glam_pair_pool_gather_train_fwd): the same kernel also stores those two column sums (sums[i] = [s1 | s2]) for the backward of
+// pairgather_bwd.hip — a runtime pointer, NULL in the inference call, not a second template axis.
 #include <utility>
 
 #include "common.h"
@@ -69,7 +71,7 @@ template <int D, bool kVec>
 __global__ void __launch_bounds__(kBlock) k_pair_gather(const float* __restrict__ x1, const float* __restrict__ x2,
                                                        const int* __restrict__ ptr1, const int* __restrict__ ptr2,
                                                        const int* __restrict__ idx1, const int* __restrict__ idx2, int P,
-                                                       float* __restrict__ out, int* __restrict__ arg) {
+                                                       float* __restrict__ out, int* __restrict__ arg, float* __restrict__ sums) {
     static_assert(D >= 1 && D <= kGatherMaxD && (!kVec || D % 4 == 0), "k_pair_gather: width");
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * kGatherPairs + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -85,14 +87,17 @@ __global__ void __launch_bounds__(kBlock) k_pair_gather(const float* __restrict_
         return;
     }
     // ---- mean: <column sums of segment 1, column sums of segment 2> ----
+    // (sums, f32[P,2,D] or NULL: the training forward keeps the two column sums for the backward's common term)
     float t = 0.f, s1, s2;
     if (lane < D) {
         gather_colsums<D>(x1, m0, n1, x2, p0, n2, lane, s1, s2);
         t = s1 * s2;
+        if (sums) { sums[(size_t)i * 2 * D + lane] = s1; sums[(size_t)i * 2 * D + D + lane] = s2; }
     }
     if (D > 64 && lane + 64 < D) {
         gather_colsums<D>(x1, m0, n1, x2, p0, n2, lane + 64, s1, s2);
         t = fmaf(s1, s2, t);
+        if (sums) { sums[(size_t)i * 2 * D + lane + 64] = s1; sums[(size_t)i * 2 * D + D + lane + 64] = s2; }
     }
     const float tot = group_sum<64>(t);
     // ---- maximum ----
@@ -152,7 +157,7 @@ __global__ void __launch_bounds__(kBlock) k_pair_gather(const float* __restrict_
     }
 }
 
-typedef void (*gather_kernel)(const float*, const float*, const int*, const int*, const int*, const int*, int, float*, int*);
+typedef void (*gather_kernel)(const float*, const float*, const int*, const int*, const int*, const int*, int, float*, int*, float*);
 
 // [D - 1] -> the dword instantiation of width D;  [D / 4 - 1] -> the 16-byte one
 template <int... I>
@@ -176,24 +181,38 @@ extern "C" size_t glam_pair_pool_gather_load_bytes(const float* x1, const float*
     return (D & 3) == 0 && aligned16(x1) && aligned16(x2) ? 16 : 4;
 }
 
-extern "C" int glam_pair_pool_gather_fwd(const float* x1, const float* x2, const int32_t* ptr1, const int32_t* ptr2,
-                                         const int32_t* idx1, const int32_t* idx2, int64_t P, int64_t Q1, int64_t Q2, int D,
-                                         float* out, int32_t* argmax, void* stream) {
-    GLAM_REQUIRE(P >= 0 && P < INT32_MAX, "glam_pair_pool_gather_fwd: P out of range");
-    GLAM_REQUIRE(Q1 >= 0 && Q1 < INT32_MAX && Q2 >= 0 && Q2 < INT32_MAX, "glam_pair_pool_gather_fwd: Q1 / Q2 out of range");
-    if (D <= 0 || D > kGatherMaxD) return fail(GLAM_E_UNSUPPORTED, "glam_pair_pool_gather_fwd: D=%d not in 1..%d", D, kGatherMaxD);
+// the two entry points: sums == NULL is the inference call (the bits of the kernel before it took the pointer), sums != NULL training
+static int gather_launch(const char* who, const float* x1, const float* x2, const int32_t* ptr1, const int32_t* ptr2, const int32_t* idx1,
+                         const int32_t* idx2, int64_t P, int64_t Q1, int64_t Q2, int D, float* out, int32_t* argmax, float* sums,
+                         bool training, void* stream) {
+    GLAM_REQUIRE(P >= 0 && P < INT32_MAX, "%s: P out of range", who);
+    GLAM_REQUIRE(Q1 >= 0 && Q1 < INT32_MAX && Q2 >= 0 && Q2 < INT32_MAX, "%s: Q1 / Q2 out of range", who);
+    if (D <= 0 || D > kGatherMaxD) return fail(GLAM_E_UNSUPPORTED, "%s: D=%d not in 1..%d", who, D, kGatherMaxD);
     if (P == 0) return GLAM_OK;
-    GLAM_REQUIRE(Q1 > 0 && Q2 > 0, "glam_pair_pool_gather_fwd: pairs but no segment on one side");
-    GLAM_REQUIRE(idx1 || Q1 == P, "glam_pair_pool_gather_fwd: idx1 = NULL pairs i with segment i of x1: needs Q1 == P");
-    GLAM_REQUIRE(idx2 || Q2 == P, "glam_pair_pool_gather_fwd: idx2 = NULL pairs i with segment i of x2: needs Q2 == P");
-    GLAM_REQUIRE(x1 && x2 && ptr1 && ptr2 && out, "glam_pair_pool_gather_fwd: null pointer");
-    GLAM_REQUIRE(((uintptr_t)x1 & 3u) == 0 && ((uintptr_t)x2 & 3u) == 0, "glam_pair_pool_gather_fwd: rows must be 4-byte aligned");
+    GLAM_REQUIRE(Q1 > 0 && Q2 > 0, "%s: pairs but no segment on one side", who);
+    GLAM_REQUIRE(idx1 || Q1 == P, "%s: idx1 = NULL pairs i with segment i of x1: needs Q1 == P", who);
+    GLAM_REQUIRE(idx2 || Q2 == P, "%s: idx2 = NULL pairs i with segment i of x2: needs Q2 == P", who);
+    GLAM_REQUIRE(x1 && x2 && ptr1 && ptr2 && out && (!training || (argmax && sums)), "%s: null pointer", who);
+    GLAM_REQUIRE(((uintptr_t)x1 & 3u) == 0 && ((uintptr_t)x2 & 3u) == 0 && ((uintptr_t)sums & 3u) == 0, "%s: rows must be 4-byte aligned", who);
     const gather_kernel k = glam_pair_pool_gather_load_bytes(x1, x2, D) == 16
                                 ? gather_vec_table(std::make_integer_sequence<int, kGatherMaxD / 4>())[D / 4 - 1]
                                 : gather_dword_table(std::make_integer_sequence<int, kGatherMaxD>())[D - 1];
     GLAM_PROF_LABEL("k_pair_gather");
     hipLaunchKernelGGL(k, dim3((unsigned)((P + kGatherPairs - 1) / kGatherPairs)), dim3(kBlock), 0, (hipStream_t)stream, x1, x2, ptr1,
-                       ptr2, idx1, idx2, (int)P, out, argmax);
-    GLAM_LAUNCH_CHECK("glam_pair_pool_gather_fwd");
+                       ptr2, idx1, idx2, (int)P, out, argmax, sums);
+    GLAM_LAUNCH_CHECK(who);
     return GLAM_OK;
+}
+
+extern "C" int glam_pair_pool_gather_fwd(const float* x1, const float* x2, const int32_t* ptr1, const int32_t* ptr2,
+                                         const int32_t* idx1, const int32_t* idx2, int64_t P, int64_t Q1, int64_t Q2, int D,
+                                         float* out, int32_t* argmax, void* stream) {
+    return gather_launch("glam_pair_pool_gather_fwd", x1, x2, ptr1, ptr2, idx1, idx2, P, Q1, Q2, D, out, argmax, nullptr, false, stream);
+}
+
+// ... for training (csrc/pairgather_bwd.hip): argmax and sums f32[P,2,D] are always written (sums not for an empty pair: nothing reads it)
+extern "C" int glam_pair_pool_gather_train_fwd(const float* x1, const float* x2, const int32_t* ptr1, const int32_t* ptr2,
+                                               const int32_t* idx1, const int32_t* idx2, int64_t P, int64_t Q1, int64_t Q2, int D,
+                                               float* out, int32_t* argmax, float* sums, void* stream) {
+    return gather_launch("glam_pair_pool_gather_train_fwd", x1, x2, ptr1, ptr2, idx1, idx2, P, Q1, Q2, D, out, argmax, sums, true, stream);
 }

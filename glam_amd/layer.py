@@ -1200,3 +1200,9 @@ def dot_and_global_pool2_gather(x1, x2, sp1, sp2, idx1=None, idx2=None, return_a
     (the ``SegmentPtr``s of the encoded drugs; ``ops.pair_index`` for the indices) — the fusion of ``ArchitectureDDI.score_pairs``.
     Inference only; widths are handled as in ``dot_and_global_pool2_indexed``: the rows flow as they are."""
     return ops.pair_pool_gather(x1, x2, sp1, sp2, idx1, idx2, return_argmax)
+
+
+def dot_and_global_pool2_gather_shared(x1, x2, sp1, sp2, idx1=None, idx2=None, with_identity=False):
+    """``dot_and_global_pool2_gather`` for TRAINING: the same forward with a backward (``ops.pair_pool_gather_shared``) — a drug's rows,
+    on either side, collect the gradients of every pair that points at it.  ``with_identity`` as in ``dot_and_global_pool2``."""
+    return ops.pair_pool_gather_shared(x1, x2, sp1, sp2, idx1, idx2, with_identity)

@@ -19,7 +19,7 @@ from .layer import _None  # noqa: F401
 from .layer import GlobalPool5, GlobalLAPool, Set2Set  # noqa: F401  (resolved from config strings)
 from .layer import LinearBlock, MessageBlock, dot_and_global_pool2, first_node_spec, flat_then_head, following_dropout, prestage_pass
 from .layer import _BatchNorm, _LayerNorm, _PairNorm, dot_and_global_pool2_gather, dot_and_global_pool2_indexed, dot_and_global_pool2_shared
-from .layer import dot_and_global_pool2_panel
+from .layer import dot_and_global_pool2_gather_shared, dot_and_global_pool2_panel
 
 
 def model_args(args):
@@ -536,3 +536,76 @@ class ArchitectureDDI(torch.nn.Module):
         with ops.weight_scope():
             out = self.lin_out1(self.lin_out0(ops.cat_cols([o1, o2] + fusion)))
         return (out, contacts) if return_argmax else out
+
+    # ---- training on shared drugs: each tower runs once per DISTINCT drug of its side of the step ----------------------------
+    def _shared_guard(self):
+        slots = [(f"mol{t}_{slot}", getattr(self, f"mol{t}_{slot}"), ok) for t in (1, 2)
+                 for slot, ok in (("lin0", _PER_GRAPH_NORMS), ("conv", _PER_GRAPH_NORMS), ("flat", _PER_ROW_NORMS))]
+        _tower_norms_guard("forward_shared", slots, "drug", "model(mol1, mol2)")
+        if self.training:
+            for name, block, _ in slots:
+                if type(block.norm) is _BatchNorm:
+                    raise GlamHipError(f"forward_shared: {name}'s norm _BatchNorm takes its batch statistics over the drug rows of the step, "
+                                       "and in model(mol1, mol2) those weigh each drug by how often it is repeated — over drugs held "
+                                       "once they are other statistics: train with model(mol1, mol2), or call forward_shared in eval() "
+                                       "(running statistics are per row)")
+
+    def _shared_index(self, given, P, Q, device, name):
+        if given is not None:
+            return ops.pair_index(given, P, Q, name=name, over="drugs")
+        # the defaults are kept per (P, Q, device): the index a later capture of the same step meets already has its device copies
+        cache = self.__dict__.setdefault("_shared_defaults", {})
+        key = (P, Q, str(device))
+        if key not in cache:
+            cache[key] = ops.pair_index(None, P, Q, name=name, over="drugs")
+        return cache[key]
+
+    def forward_shared(self, mol1, mol2, first=None, second=None):
+        """``model(B1, B2)`` -> ``[P, out_dim]`` for ``B1`` = the drugs ``first`` of ``mol1`` and ``B2`` = the drugs ``second`` of ``mol2``
+        collated one per pair — without building either batch: ``mol1`` holds the ``Q1`` DISTINCT first-side drugs of the step, ``mol2`` the
+        ``Q2`` distinct second-side drugs (the same ``Batch`` may be passed for both), tower 1 runs on ``mol1`` and tower 2 on ``mol2``, each
+        once, every step's fusion reads both towers' rows through the two indices (``ops.pair_pool_gather_shared``) and
+        ``mol1_flat(mol1_readout(.))`` / ``mol2_flat(mol2_readout(.))`` are gathered by them (``ops.pair_rows``).  Unlike ``score_pairs`` this
+        call has a backward: it trains, with gradients to every parameter of both towers and the head; a drug's gradients are the sums
+        over its pairs, in batch order (no atomics: two runs agree bit for bit).  ``first`` / ``second``: host integers, one per pair, or a
+        ``PairIndex`` (``ops.pair_index`` — keep ONE per side across the steps that use it: its device copies are made on the first, eager,
+        visit, and a ``GraphedTrainStep`` capture needs them to exist); ``None`` = pair i takes drug i of that side (needs ``Q == P``).
+
+        Contract.  Output and every parameter gradient equal those of ``model(B1, B2)`` within the fp32 parity bound WHENEVER nothing in
+        a tower is stochastic or depends on the rest of the batch: ``eval()``, or ``train()`` with ``_None()`` / ``Dropout(0)`` and
+        non-random activations.  In ``train()`` with live Dropout / RReLU in a tower the noise is drawn ONCE per distinct drug and shared
+        by all its pairs; the reference draws it per copy.  That is another (equally valid) regulariser, not the reference's — which is
+        why this is a call of its own and ``model(mol1, mol2)`` is untouched.  Refused, before any launch: the tower norms ``encode_drugs``
+        refuses, on BOTH towers (``_GraphSizeNorm``; ``_LayerNorm`` / ``_PairNorm`` in a ``molK_flat`` slot), and a ``_BatchNorm`` in a
+        tower slot while training (batch statistics weigh each drug by how often it is repeated).  The head's norms are not refused: they
+        see the same ``[P, .]`` matrix.  Always eager by itself (no graphed-call route); inside a ``GraphedTrainStep`` it is captured with
+        the step."""
+        self._shared_guard()
+        n1 = getattr(mol1, "num_graphs", None) or None
+        n2 = getattr(mol2, "num_graphs", None) or None
+        given = first if first is not None else second
+        P = None if given is None else given.P if isinstance(given, ops.PairIndex) else len(given)
+        dev = mol1.x.device
+        i1 = i2 = None
+        if n1 is not None and n2 is not None:          # (a collated Batch knows its counts: the indices are checked before the first launch)
+            P = n1 if P is None else P
+            i1, i2 = self._shared_index(first, P, n1, dev, "first"), self._shared_index(second, P, n2, dev, "second")
+        sp1, sp2 = ops.segment_ptr(mol1.batch, n1), ops.segment_ptr(mol2.batch, n2)
+        if i1 is None:
+            P = sp1.B if P is None else P
+            i1, i2 = self._shared_index(first, P, sp1.B, dev, "first"), self._shared_index(second, P, sp2.B, dev, "second")
+        with ops.weight_scope():
+            prestage_pass((self.mol1_lin0, self.mol1_conv, mol1.x, mol1.edge_attr), (self.mol2_lin0, self.mol2_conv, mol2.x, mol2.edge_attr))
+            x1 = self.mol1_lin0(mol1.x, batch=mol1.batch)
+            x2 = self.mol2_lin0(mol2.x, batch=mol2.batch)
+            h1, h2, fusion = None, None, []
+            for i in range(self.message_steps):
+                with ops.block_feeds_itself(i + 1 < self.message_steps):      # (the fusion hands the rows back untouched)
+                    x1, h1 = self.mol1_conv(x1, mol1.edge_index, mol1.edge_attr, h=h1, batch=mol1.batch)
+                    x2, h2 = self.mol2_conv(x2, mol2.edge_index, mol2.edge_attr, h=h2, batch=mol2.batch)
+                f, x1, x2 = dot_and_global_pool2_gather_shared(x1, x2, sp1, sp2, i1, i2, with_identity=True)
+                fusion.append(f)
+            o1 = ops.pair_rows(self.mol1_flat(self.mol1_readout(x1, mol1.batch, n1)), i1)
+            o2 = ops.pair_rows(self.mol2_flat(self.mol2_readout(x2, mol2.batch, n2)), i2)
+            out = ops.cat_cols([o1, o2] + fusion)
+            return self.lin_out1(self.lin_out0(out))

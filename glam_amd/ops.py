@@ -293,7 +293,7 @@ def scoped_image(scope, kind, owner, Kimg=None, W=None):
     """The image ``kind(owner, Kimg, W)``, built on first use and filed in ``scope`` (None: built every time); a hit builds no spec."""
     img = None if scope is None else scope.lookup(kind.table, (kind.name, id(owner)), owner)
     if img is None:
-        lib, spec = _lib.api(), kind(owner, Kimg, W)
+        lib, spec = _lib.api(), kind(owner, Kimg, W() if callable(W) else W)      # (a callable W: built on a miss only)
         img = torch.empty(lib.glam_ts_gemm_image_bytes(spec.Kimg, spec.M) // 4, dtype=torch.float32, device=spec.W.device)
         lib.glam_ts_gemm_make_image(ptr(spec.W), spec.ldw, spec.transW, spec.K, spec.M, ptr(img), stream())
         if scope is not None:

@@ -320,6 +320,39 @@ def _matmul_tall_node(a, w, bias, with_identity=False):
     return (res[0], res[1]) if with_identity else res[0]
 
 
+class _MatmulTallRows(torch.autograd.Function):
+    """``a @ w (+ bias)`` on the forward kernel of ``_MatmulTall`` (``glam_ts_gemm``: tiles of 16 rows, any row count) for the calls
+    its weight-gradient route does not take: FEWER than 64 rows, and an output width that is no multiple of 4 (``w`` is padded with zero
+    columns for the launch and the result is the ``[N, M]`` view of the padded rows).  A row's result then has the same bits whatever
+    the length of the batch around it — the towers of a few distinct graphs (``forward_shared``) give the rows of the batch that
+    repeats them, which a library GEMM that picks its kernel by the row count does not.  The gradients stay plain products."""
+
+    @staticmethod
+    def forward(ctx, a, w, bias):
+        require_device(a, w, bias)
+        a, w = f32c(a, "a"), f32c(w, "w")
+        ctx.save_for_backward(a, w)
+        ctx.has_bias = bias is not None
+        N, K = a.shape
+        M = w.size(1)
+        Mp = (M + 3) // 4 * 4
+        img = _o.scoped_image(_o._SCOPE, _o.tall_image, w, None, (lambda: torch.nn.functional.pad(w, (0, Mp - M))) if Mp != M else None)
+        if bias is not None:
+            bias = f32c(bias, "bias")
+            bias = torch.nn.functional.pad(bias, (0, Mp - M)) if Mp != M else bias
+        out = torch.empty(N, Mp, dtype=torch.float32, device=a.device)
+        _lib.api().glam_ts_gemm(ptr(a), K, K, None, 0, 0, ptr(img), ptr(bias), ptr(out), Mp, Mp, None, 0, 0, N, stream())
+        return out if Mp == M else out[:, :M]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        a, w = ctx.saved_tensors
+        da = torch.matmul(dy, w.t()) if ctx.needs_input_grad[0] else None
+        dw = torch.matmul(a.t(), dy) if ctx.needs_input_grad[1] else None
+        return da, dw, (dy.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None)
+
+
 def matmul_tall(a, w, bias=None, with_identity=False):
     """``a @ w (+ bias)`` with the weight gradient on the MFMA reduction kernel when it fits: one of (K, M) <= 320 and the other
     <= 128, multiples of 4 (with a bias: K + 1 <= 320 and M <= 128).  ``with_identity``: returns ``(out, identity)`` with ``identity`` =
@@ -337,6 +370,14 @@ def matmul_tall(a, w, bias=None, with_identity=False):
         r = _matmul_tall_node(a, w, None, alias)
         out, ident = r if alias else (r, None)
         return fin(out if bias is None else out + bias, ident)
+    if (a.dim() == 2 and a.is_cuda and a.dtype == torch.float32 and w.dtype == torch.float32 and a.size(0) > 0 and K % 4 == 0 and K <= 320
+            and M <= 64 and (a.size(0) < 64 or M % 4 != 0) and _lib.route_enabled("x3")):
+        # a short batch or an odd output width: the forward kernel of the products above (the bias in its epilogue exactly where they
+        # put it there), not a library GEMM whose kernel — and roundings — follow the row count
+        if bias is not None and K + 1 <= 320:
+            return fin(_MatmulTallRows.apply(a, w, bias))
+        out = _MatmulTallRows.apply(a, w, None)
+        return fin(out if bias is None else out + bias)
     out = torch.matmul(a, w)
     return fin(out if bias is None else out + bias)
 

@@ -1019,3 +1019,87 @@ def pair_pool_gather(x1, x2, sp1, sp2, idx1=None, idx2=None, return_argmax=False
     lib.glam_pair_pool_gather_fwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if i1 is None else i1.on(x1.device)),
                                   ptr(None if i2 is None else i2.on(x1.device)), P, Q1, Q2, D, ptr(out), ptr(arg), stream())
     return (out, arg) if return_argmax else out
+
+
+# --------------------------------------------------------------------------------------
+# training on drugs held once: the gathered fusion with a backward (csrc/pairgather.hip train_fwd, csrc/pairgather_bwd.hip)
+# --------------------------------------------------------------------------------------
+class _PairPoolGatherShared(torch.autograd.Function):
+    """``i1`` / ``i2``: the validated ``PairIndex`` of each side (an identity side too: its by-drug lists are read by the backward);
+    ``null1`` / ``null2``: hand the kernels a NULL index on that side (identity)."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, sp1, sp2, i1, i2, null1, null2, with_identity=False):
+        x1_in, x2_in = x1, x2
+        x1, x2 = f32c(x1, "x1"), f32c(x2, "x2")
+        P, Q1, Q2, D, dev = i1.P, sp1.B, sp2.B, x1.size(1), x1.device
+        d1, d2 = i1.on(dev), i2.on(dev)
+        order1, lptr1 = i1.by_protein().on(dev)
+        order2, lptr2 = i2.by_protein().on(dev)
+        out = torch.empty(P, 2, dtype=torch.float32, device=dev)
+        arg = torch.empty(P, 2, dtype=torch.int32, device=dev)
+        sums = torch.empty(P, 2, D, dtype=torch.float32, device=dev)
+        ctx.rows = x1.size(0) > 0 and x2.size(0) > 0
+        if ctx.rows:
+            _lib.api().glam_pair_pool_gather_train_fwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if null1 else d1),
+                                                       ptr(None if null2 else d2), P, Q1, Q2, D, ptr(out), ptr(arg), ptr(sums), stream())
+        else:                # no row on one side: every pair is empty (and the empty matrix has no address to pass)
+            out.zero_()
+            arg.fill_(-1)
+        ctx.save_for_backward(x1, x2, arg, sums, d1, d2, order1, lptr1, order2, lptr2)
+        ctx.sps, ctx.null, ctx.P = (sp1, sp2), (bool(null1), bool(null2)), P
+        ctx.aliased = bool(with_identity)
+        if ctx.aliased:      # (as _PairPool: what the caller does with the two matrices next sends its gradient HERE)
+            ctx.set_materialize_grads(False)
+            return out, x1_in.view_as(x1_in), x2_in.view_as(x2_in)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, d_a1=None, d_a2=None):
+        x1, x2, arg, sums, d1, d2, order1, lptr1, order2, lptr2 = ctx.saved_tensors
+        sp1, sp2 = ctx.sps
+        none = (None,) * 7
+        if d_out is None:
+            return (d_a1, d_a2) + none
+        d_out = f32c(d_out, "d_out")
+        d_a1 = None if d_a1 is None else f32c(d_a1, "d_x1 (next use)")
+        d_a2 = None if d_a2 is None else f32c(d_a2, "d_x2 (next use)")
+        if ctx.P == 0 or not ctx.rows:       # no pair, or only empty ones: the entry point writes nothing
+            return (torch.zeros_like(x1) if d_a1 is None else d_a1, torch.zeros_like(x2) if d_a2 is None else d_a2) + none
+        d_x1, d_x2 = torch.empty_like(x1), torch.empty_like(x2)
+        _lib.api().glam_pair_pool_gather_bwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if ctx.null[0] else d1),
+                                             ptr(None if ctx.null[1] else d2), ptr(order1), ptr(lptr1), ptr(order2), ptr(lptr2), ptr(arg),
+                                             ptr(sums), ptr(d_out), ctx.P, sp1.B, sp2.B, x1.size(1), ptr(d_a1), ptr(d_a2), ptr(d_x1),
+                                             ptr(d_x2), stream())
+        return (d_x1, d_x2) + none
+
+
+def pair_pool_gather_shared(x1, x2, sp1, sp2, idx1=None, idx2=None, with_identity=False):
+    """``pair_pool_gather`` WITH a backward: ``[max, mean]`` of ``x1[seg_a] @ x2[seg_b].T`` with ``a = idx1[i]``, ``b = idx2[i]`` ->
+    ``[P, 2]`` on two sets of small segments that are each held once, for training.  The forward is bit for bit ``pair_pool_gather``; the
+    gradient of a segment's rows — on EITHER side — is the sum over every pair that points at it, taken in batch order without atomics
+    (two runs are bit-equal, one launch for both sides); a segment no pair references gets zeros.  ``idx1`` / ``idx2``: as
+    ``pair_pool_gather`` (``pair_index``; ``None`` = identity on that side, needs ``sp.B == P``); keep ONE ``PairIndex`` per side across
+    the steps that use it — its device copies are made on the first, eager, visit and a hipGraph capture needs them to exist.  Widths
+    1..128.  ``with_identity``: as ``pair_pool`` — ``(out, x1, x2)`` with the two matrices handed back through the node (both require
+    grad, fp32): its backward launch then adds their later gradients itself; the plain triple otherwise."""
+    Q1, Q2 = sp1.B, sp2.B
+    given = idx1 if idx1 is not None else idx2
+    P = Q1 if given is None else given.P if isinstance(given, PairIndex) else len(given)
+    i1 = pair_index(idx1, P, Q1, name="idx1", over="segments of x1")
+    i2 = pair_index(idx2, P, Q2, name="idx2", over="segments of x2")
+    require_device(x1, x2)
+    if x1.dim() != 2 or x2.dim() != 2 or x1.size(1) != x2.size(1) or x1.size(0) != sp1.N or x2.size(0) != sp2.N:
+        raise GlamHipError(f"pair_pool_gather_shared: the two sides disagree (width / node count): x1 {tuple(x1.shape)} for {sp1.N} rows, "
+                           f"x2 {tuple(x2.shape)} for {sp2.N} rows")
+    D = x1.size(1)
+    if not 1 <= D <= 128:
+        raise GlamHipError(f"pair_pool_gather_shared: width {D} is outside the kernel table (1..128)")
+    args = (x1, x2, sp1, sp2, i1, i2, idx1 is None, idx2 is None)
+    if with_identity:
+        # (the add runs inside the backward launch for every width of the table: 1 <= D <= 128, checked above)
+        if (torch.is_grad_enabled() and x1.requires_grad and x2.requires_grad and x1.dtype == torch.float32 and x2.dtype == torch.float32):
+            return _PairPoolGatherShared.apply(*args, True)
+        return _PairPoolGatherShared.apply(*args), x1, x2
+    return _PairPoolGatherShared.apply(*args)

@@ -622,6 +622,30 @@ size_t glam_pair_pool_gather_load_bytes(const float* x1, const float* x2, int D)
 int glam_pair_pool_gather_fwd(const float* x1, const float* x2, const int32_t* ptr1, const int32_t* ptr2, const int32_t* idx1,
                               const int32_t* idx2, int64_t P, int64_t Q1, int64_t Q2, int D, float* out, int32_t* argmax, void* stream);
 
+/* Drug x drug, training on drugs held once (csrc/pairgather.hip, csrc/pairgather_bwd.hip).  glam_pair_pool_gather_train_fwd: the launch of
+ * glam_pair_pool_gather_fwd that ALWAYS writes argmax int32[P,2] (-1, -1 for an empty pair) and also sums f32[P,2,D] — the column sums of
+ * segment idx1[i] of x1 and of segment idx2[i] of x2, from the registers that form the mean (not written for an empty pair: nothing reads
+ * them).  out and argmax are bit for bit those of glam_pair_pool_gather_fwd on the same inputs.
+ * glam_pair_pool_gather_bwd: its backward, ONE launch, one wave per (side, drug), ceil((Q1 + Q2) / 4) blocks.  order1 int32[P]: the pairs
+ * stably sorted by idx1; list_ptr1 int32[Q1+1]: the offsets of the drugs' runs in it; order2 / list_ptr2 the same for idx2 (with a NULL
+ * index: the identity lists).  Built and checked by the caller, trusted here.  With n1, n2 the sizes of pair i's segments,
+ * gmax_i = d_out[i,0], gmean_i = d_out[i,1] / (n1 n2) and (am_i, ap_i) = argmax[i]:
+ *   d_x1, every row r of every segment a (referenced or not):  0, + gmean_i * sums[i,1] for the pairs i with idx1[i] == a in order1 order,
+ *         then fmaf(gmax_i, x2[ap_i], .) for those of them with am_i == r in the same order, + add1[r] last;
+ *   d_x2: the same with the sides exchanged (sums[i,0], x1[am_i] on row ap_i, order2, add2).
+ * A pair with an empty segment on either side contributes nothing.  No atomics: the order of every sum depends on the lists alone, two
+ * runs are bit-equal.  add1 / add2 (the gradients of a later use of x1 / x2) may be NULL.  16-byte loads and stores when D % 4 == 0 and
+ * x1, x2, sums, add1, add2, d_x1, d_x2 are 16-byte aligned, dwords otherwise.  Both: D in 1..128, else GLAM_E_UNSUPPORTED; P == 0:
+ * GLAM_OK, nothing launched or written. */
+int glam_pair_pool_gather_train_fwd(const float* x1, const float* x2, const int32_t* ptr1, const int32_t* ptr2, const int32_t* idx1,
+                                    const int32_t* idx2, int64_t P, int64_t Q1, int64_t Q2, int D, float* out, int32_t* argmax,
+                                    float* sums, void* stream);
+int glam_pair_pool_gather_bwd(const float* x1, const float* x2, const int32_t* ptr1, const int32_t* ptr2, const int32_t* idx1,
+                              const int32_t* idx2, const int32_t* order1, const int32_t* list_ptr1, const int32_t* order2,
+                              const int32_t* list_ptr2, const int32_t* argmax, const float* sums, const float* d_out, int64_t P,
+                              int64_t Q1, int64_t Q2, int D, const float* add1, const float* add2, float* d_x1, float* d_x2,
+                              void* stream);
+
 /* Panel screening (inference): EVERY ligand segment l = 0..L-1 of mol (mol_ptr int32[L+1]) against every selected protein segment
  * sel[j], j = 0..Qs-1 (int32[Qs], entries in [0, Q), any order, duplicates allowed), of pro (pro_ptr int32[Q+1], each protein held once):
  * out f32[L,Qs,2] = [max, mean]; argmax int32[L,Qs,2] (row of mol, row of pro; may be NULL); an empty ligand or protein gives 0, 0 and

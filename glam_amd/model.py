@@ -63,24 +63,74 @@ class Architecture(torch.nn.Module):
         return out
 
     def _forward(self, data_mol):
-        prestage_pass((self.mol_lin0, self.mol_conv, data_mol.x, data_mol.edge_attr))  # (the pass's weight re-layouts from one launch)
+        m = _Tower(self, "mol", data_mol)
+        prestage_pass(m.stage())                                                   # (the pass's weight re-layouts from one launch)
         # (next_dropout: the block behind applies Dropout to this output first — the activation's launch writes the dropped twin)
         # (... and next_node: that block's TripletMessage reads this output — the embedding's launch writes its node product too)
-        xm = self.mol_lin0(data_mol.x, batch=data_mol.batch, next_dropout=following_dropout(self.mol_conv),     # model.py:49
-                           next_node=first_node_spec(self.mol_conv, data_mol.x.size(0), data_mol.edge_index, data_mol.edge_attr))
-        hm = None
+        m.x = self.mol_lin0(data_mol.x, batch=data_mol.batch, next_dropout=following_dropout(self.mol_conv),    # model.py:49
+                            next_node=first_node_spec(self.mol_conv, data_mol.x.size(0), data_mol.edge_index, data_mol.edge_attr))
         for i in range(self.message_steps):                                        # model.py:53-54
             with ops.block_feeds_itself(i + 1 < self.message_steps):      # (its output is the same block's next input)
-                xm, hm = self.mol_conv(xm, data_mol.edge_index, data_mol.edge_attr, h=hm, batch=data_mol.batch)
-        # PyG's pools read the graph count back from ``batch``; a collated Batch already knows it
-        num_graphs = getattr(data_mol, "num_graphs", None) or None
-        outm = self.mol_readout(xm, data_mol.batch, num_graphs)                    # model.py:57
-        # model.py:60-61 — in the default configuration in training mode the head applies mol_flat's RReLU and its own Dropout to
+                m.step()
+        # model.py:57, 60-61 — in the default configuration in training mode the head applies mol_flat's RReLU and its own Dropout to
         # the elements it reads (layer.flat_then_head)
-        return flat_then_head(self.mol_flat, self.lin_out1, outm)
+        return flat_then_head(self.mol_flat, self.lin_out1, m.pooled())
 
 
 Model = Architecture
+
+
+class _Tower:
+    """One graph tower of one pass — ``model.<name>_lin0 / _conv / _readout / _flat`` over the batch ``data``: ``x`` the rows after the
+    last ``step()`` (a fusion that hands them back writes them here), ``n`` the graph count a collated Batch already knows (PyG's pools
+    would read it back from ``batch``), else None."""
+
+    def __init__(self, model, name, data):
+        self.lin0, self.conv = getattr(model, name + "_lin0"), getattr(model, name + "_conv")
+        self.readout, self.flat = getattr(model, name + "_readout"), getattr(model, name + "_flat")
+        self.data, self.n, self.x, self.h = data, getattr(data, "num_graphs", None) or None, None, None
+
+    def stage(self):
+        return self.lin0, self.conv, self.data.x, self.data.edge_attr
+
+    def step(self):
+        """One application of the MessageBlock -> its rows."""
+        d = self.data
+        self.x, self.h = self.conv(self.x, d.edge_index, d.edge_attr, h=self.h, batch=d.batch)
+        return self.x
+
+    def pooled(self):
+        return self.readout(self.x, self.data.batch, self.n)
+
+    def flat_out(self):
+        return self.flat(self.pooled())
+
+
+def _embed(*towers):
+    """The start of a pass: its weight re-layouts from as few launches as possible (``prestage_pass``, every tower in ONE call), then
+    each tower's input LinearBlock, in the order given."""
+    prestage_pass(*[t.stage() for t in towers])
+    for t in towers:
+        t.x = t.lin0(t.data.x, batch=t.data.batch)
+
+
+def _fused_walk(steps, a, b, b_feeds_itself, fuse):
+    """Both towers step by step, and after every step ``fuse(a.x, b.x)`` -> ``(f, a.x, b.x)``, the fusion that hands the rows back (every
+    step's outputs feed the fusion AND the next step / the readouts: both gradients then meet inside its backward launch instead of in
+    an add launch per tower) -> the steps' ``f``.  ``b_feeds_itself``: ``b``'s block too runs under ``block_feeds_itself``
+    (``ArchitectureDDI`` wraps both blocks, ``ArchitectureDTI`` the ligand's alone)."""
+    _embed(a, b)
+    fusion = []
+    for i in range(steps):
+        with ops.block_feeds_itself(i + 1 < steps):      # (its output is the same block's next input)
+            a.step()
+            if b_feeds_itself:
+                b.step()
+        if not b_feeds_itself:
+            b.step()
+        f, a.x, b.x = fuse(a.x, b.x)
+        fusion.append(f)
+    return fusion
 
 
 def _tower_stamp(modules):
@@ -90,17 +140,78 @@ def _tower_stamp(modules):
     return ops.PARAM_EPOCH, sum(t._version for t in ts), tuple(t.data_ptr() for t in ts)
 
 
-def _tower_norms_guard(what, slots, thing, call):
-    """The norm rules of an encoding that stands for every copy of a graph: ``slots`` = (name, block, admitted norm types)."""
-    for name, block, ok in slots:
-        if type(block.norm) not in ok:
-            raise GlamHipError(f"{what}: {name}'s norm {type(block.norm).__name__} is not per graph or per row here — it normalises over "
-                               f"the whole batch (rows of every copy of every {thing}), so its result depends on how often each {thing} "
-                               f"is repeated and one encoding cannot reproduce {call}")
-
-
 _PER_GRAPH_NORMS = (_None, _BatchNorm, _LayerNorm, _PairNorm)      # slots given ``batch``
 _PER_ROW_NORMS = (_None, _BatchNorm)                               # the *_flat slots (no ``batch``)
+
+# What the guards of a model that holds graphs once call its things: ``slots`` (block, admitted norm types) of the towers held once,
+# ``thing`` one graph of them, ``call`` the reference call an encoding stands for, ``copy`` / ``fusion`` / ``train`` / ``eager`` the words of the inference
+# guard, ``rows`` / ``encode`` / ``written`` those of the encoding check.
+def _slots(*towers):
+    return tuple((f"{t}_{s}", ok) for t in towers for s, ok in (("lin0", _PER_GRAPH_NORMS), ("conv", _PER_GRAPH_NORMS), ("flat", _PER_ROW_NORMS)))
+
+
+_DTI_WORDS = dict(slots=_slots("pro"), thing="protein", call="model(data_mol, data_pro)", copy="protein copy", fusion="indexed",
+                  train="model(data_mol, data_pro) on one protein graph per pair", eager="a library walk never repeats a batch",
+                  rows="residue rows", encode="encode_proteins",
+                  written="a protein-side parameter or buffer (pro_lin0 / pro_conv / pro_readout / pro_flat)")
+_DDI_WORDS = dict(slots=_slots("mol1", "mol2"), thing="drug", call="model(mol1, mol2)", copy="copy of a drug", fusion="gathered",
+                  train="model(mol1, mol2) on one graph per pair and side",
+                  eager="its pair index is validated on the host and differs from call to call", rows="rows", encode="encode_drugs",
+                  written="a parameter or buffer of a tower (mol1_* / mol2_* lin0, conv, readout, flat)")
+
+
+def _tower_norms_guard(model, what, w):
+    """The norm rules of an encoding that stands for every copy of a graph."""
+    for name, ok in w["slots"]:
+        norm = getattr(model, name).norm
+        if type(norm) not in ok:
+            raise GlamHipError(f"{what}: {name}'s norm {type(norm).__name__} is not per graph or per row here — it normalises over "
+                               f"the whole batch (rows of every copy of every {w['thing']}), so its result depends on how often each "
+                               f"{w['thing']} is repeated and one encoding cannot reproduce {w['call']}")
+
+
+def _inference_guard(model, what, w):
+    """The guard of the calls that make or read an encoding: ``eval()``, no grad, per-graph norms, not under a capture."""
+    if model.training:
+        raise GlamHipError(f"{what}: the model is in training mode — Dropout / RReLU noise is drawn per {w['copy']} and BatchNorm takes "
+                           "statistics over the replicated rows, so one encoding cannot stand for the copies: call model.eval()")
+    if torch.is_grad_enabled():
+        raise GlamHipError(f"{what} is inference only (the {w['fusion']} fusion has no backward): call it under torch.no_grad(); "
+                           f"training runs {w['train']}")
+    _tower_norms_guard(model, what, w)
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise GlamHipError(f"{what} runs eagerly ({w['eager']}): not inside a hipGraph capture")
+
+
+def _shared_guard(model, w):
+    """The guard of ``forward_shared``: the norms an encoding refuses, and a ``_BatchNorm`` in their slots while training."""
+    thing, call = w["thing"], w["call"]
+    _tower_norms_guard(model, "forward_shared", w)
+    for name, _ in w["slots"] if model.training else ():
+        if type(getattr(model, name).norm) is _BatchNorm:
+            raise GlamHipError(f"forward_shared: {name}'s norm _BatchNorm takes its batch statistics over the {thing} rows of the step, "
+                               f"and in {call} those weigh each {thing} by how often it is repeated — over {thing}s held once they are "
+                               f"other statistics: train with {call}, or call forward_shared in eval() (running statistics are per row)")
+
+
+def _check_encoding(model, what, enc, cls, stamp, rows, w):
+    """``enc`` is this model's (``cls``) and as fresh as ``stamp``, with one entry of ``rows`` (the attribute) per message step."""
+    if not isinstance(enc, cls) or enc.model() is not model:
+        raise GlamHipError(f"{what}: the encoding was made by another model (its {w['rows']} are that model's): {w['encode']}() on this one")
+    if enc.stamp != stamp or len(getattr(enc, rows)) != model.message_steps:
+        raise GlamHipError(f"{what}: the encoding is stale — {w['written']} was written since {w['encode']}(): encode again")
+
+
+def _shared_index(model, given, P, Q, device, **words):
+    """``ops.pair_index`` of ``given``; the default of ``None`` is kept per (P, Q, device): the index a later capture of the same step
+    meets already has its device copies.  ``words``: ``pair_index``'s own (``default``, ``name``, ``over``)."""
+    if given is not None:
+        return ops.pair_index(given, P, Q, **words)
+    cache = model.__dict__.setdefault("_shared_defaults", {})
+    key = (P, Q, str(device))
+    if key not in cache:
+        cache[key] = ops.pair_index(None, P, Q, **words)
+    return cache[key]
 
 
 class ProteinEncoding:
@@ -175,26 +286,11 @@ class ArchitectureDTI(torch.nn.Module):
             return self._forward(data_mol, data_pro)
 
     def _forward(self, data_mol, data_pro):
-        prestage_pass((self.mol_lin0, self.mol_conv, data_mol.x, data_mol.edge_attr),
-                      (self.pro_lin0, self.pro_conv, data_pro.x, data_pro.edge_attr))
-        xm = self.mol_lin0(data_mol.x, batch=data_mol.batch)
-        xp = self.pro_lin0(data_pro.x, batch=data_pro.batch)
-        hm, hp = None, None
-        fusion = []
-        for i in range(self.message_steps):
-            with ops.block_feeds_itself(i + 1 < self.message_steps):      # (its output is the same block's next input)
-                xm, hm = self.mol_conv(xm, data_mol.edge_index, data_mol.edge_attr, h=hm, batch=data_mol.batch)
-            xp, hp = self.pro_conv(xp, data_pro.edge_index, data_pro.edge_attr, h=hp, batch=data_pro.batch)
-            # (every step's outputs feed this fusion AND the next step / the readouts: they come back from the fusion node, so that both
-            #  gradients meet inside its backward launch instead of in an add launch per tower)
-            f, xm, xp = dot_and_global_pool2(xm, xp, data_mol.batch, data_pro.batch, with_identity=True)
-            fusion.append(f)
-        nm = getattr(data_mol, "num_graphs", None) or None
-        np_ = getattr(data_pro, "num_graphs", None) or None
-        outm = self.mol_flat(self.mol_readout(xm, data_mol.batch, nm))
-        outp = self.pro_flat(self.pro_readout(xp, data_pro.batch, np_))
-        out = ops.cat_cols([outm, outp] + fusion)      # (model.py:74-75; contiguous gradients for every piece from one launch)
-        return self.lin_out1(self.lin_out0(out))
+        m, p = _Tower(self, "mol", data_mol), _Tower(self, "pro", data_pro)
+        fusion = _fused_walk(self.message_steps, m, p, False,
+                             lambda xm, xp: dot_and_global_pool2(xm, xp, data_mol.batch, data_pro.batch, with_identity=True))
+        # (model.py:74-75; contiguous gradients for every piece from one launch)
+        return self.lin_out1(self.lin_out0(ops.cat_cols([m.flat_out(), p.flat_out()] + fusion)))
 
     # ---- screening: a protein is encoded once, ligand batches stream against it ---------------------------------------------
     # The reference's screening set scores a whole library against ONE protein (src_2gi_dti_scr/dataset.py:297-318) and still
@@ -213,31 +309,19 @@ class ArchitectureDTI(torch.nn.Module):
         return _tower_stamp(self._protein_modules())
 
     def _screen_guard(self, what):
-        if self.training:
-            raise GlamHipError(f"{what}: the model is in training mode — Dropout / RReLU noise is drawn per protein copy and BatchNorm takes "
-                               "statistics over the replicated rows, so one encoding cannot stand for the copies: call model.eval()")
-        if torch.is_grad_enabled():
-            raise GlamHipError(f"{what} is inference only (the indexed fusion has no backward): call it under torch.no_grad(); "
-                               "training runs model(data_mol, data_pro) on one protein graph per pair")
-        _tower_norms_guard(what, (("pro_lin0", self.pro_lin0, _PER_GRAPH_NORMS), ("pro_conv", self.pro_conv, _PER_GRAPH_NORMS),
-                                  ("pro_flat", self.pro_flat, _PER_ROW_NORMS)), "protein", "model(data_mol, data_pro)")
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise GlamHipError(f"{what} runs eagerly (a library walk never repeats a batch): not inside a hipGraph capture")
+        _inference_guard(self, what, _DTI_WORDS)
 
     def encode_proteins(self, data_pro):
         """The protein tower, once, over the ``Q`` graphs of ``data_pro`` -> ``ProteinEncoding`` for ``screen``.  ``eval()`` mode under
         ``torch.no_grad()``; valid until a protein-side parameter or buffer changes."""
         self._screen_guard("encode_proteins")
+        p = _Tower(self, "pro", data_pro)
         with ops.weight_scope():
-            prestage_pass((self.pro_lin0, self.pro_conv, data_pro.x, data_pro.edge_attr))
-            xp = self.pro_lin0(data_pro.x, batch=data_pro.batch)
-            hp, rows = None, []
-            for _ in range(self.message_steps):
-                xp, hp = self.pro_conv(xp, data_pro.edge_index, data_pro.edge_attr, h=hp, batch=data_pro.batch)
-                rows.append(xp.contiguous())          # (odd widths flow as [N, C] views of padded rows: compacted here, once)
-            nq = getattr(data_pro, "num_graphs", None) or None
-            sp = ops.segment_ptr(data_pro.batch, nq)
-            flat = self.pro_flat(self.pro_readout(xp, data_pro.batch, nq))
+            _embed(p)
+            # (odd widths flow as [N, C] views of padded rows: compacted here, once)
+            rows = [p.step().contiguous() for _ in range(self.message_steps)]
+            sp = ops.segment_ptr(data_pro.batch, p.n)
+            flat = p.flat_out()
         return ProteinEncoding(self, rows, sp, flat, self._protein_stamp())
 
     def screen(self, data_mol, enc, pro_of_pair=None, return_argmax=False):
@@ -247,30 +331,31 @@ class ArchitectureDTI(torch.nn.Module):
         ``pro_of_pair``: host integers, one per ligand (``ops.pair_index``); ``None`` when ``enc`` holds one protein.
         ``return_argmax``: also the per-step ``[P, 2]`` int32 contacts (row of ``data_mol.x``, row of the encoded proteins)."""
         self._screen_guard("screen")
-        if not isinstance(enc, ProteinEncoding) or enc.model() is not self:
-            raise GlamHipError("screen: the encoding was made by another model (its residue rows are that model's): encode_proteins() on this one")
-        if enc.stamp != self._protein_stamp() or len(enc.rows) != self.message_steps:
-            raise GlamHipError("screen: the encoding is stale — a protein-side parameter or buffer (pro_lin0 / pro_conv / pro_readout / "
-                               "pro_flat) was written since encode_proteins(): encode again")
-        nm = getattr(data_mol, "num_graphs", None) or None
-        msp = ops.segment_ptr(data_mol.batch, nm)
+        _check_encoding(self, "screen", enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
+        m = _Tower(self, "mol", data_mol)
+        msp = ops.segment_ptr(data_mol.batch, m.n)
         index = ops.pair_index(pro_of_pair, msp.B, enc.num_graphs, default="single")       # host-side, before the first launch
         with ops.weight_scope():
-            prestage_pass((self.mol_lin0, self.mol_conv, data_mol.x, data_mol.edge_attr))
-            xm = self.mol_lin0(data_mol.x, batch=data_mol.batch)
-            hm, fusion, contacts = None, [], []
-            for i in range(self.message_steps):
-                with ops.block_feeds_itself(i + 1 < self.message_steps):
-                    xm, hm = self.mol_conv(xm, data_mol.edge_index, data_mol.edge_attr, h=hm, batch=data_mol.batch)
-                f = dot_and_global_pool2_indexed(xm, enc.rows[i], data_mol.batch, enc.sp, index, return_argmax)
-                if return_argmax:
-                    f, a = f
-                    contacts.append(a)
-                fusion.append(f)
-            outm = self.mol_flat(self.mol_readout(xm, data_mol.batch, nm))
+            fusion, contacts = self._ligand_walk(m, return_argmax, lambda x, i: dot_and_global_pool2_indexed(
+                x, enc.rows[i], data_mol.batch, enc.sp, index, return_argmax))
+            outm = m.flat_out()
             outp = enc.flat.index_select(0, index.on(enc.flat.device))
             out = self.lin_out1(self.lin_out0(ops.cat_cols([outm, outp] + fusion)))
         return (out, contacts) if return_argmax else out
+
+    def _ligand_walk(self, m, return_argmax, fuse):
+        """The ligand tower ``m`` against an encoding: ``fuse(rows, step)`` after every step -> the steps' fusions and contacts."""
+        _embed(m)
+        fusion, contacts = [], []
+        for i in range(self.message_steps):
+            with ops.block_feeds_itself(i + 1 < self.message_steps):
+                m.step()
+            f = fuse(m.x, i)
+            if return_argmax:
+                f, a = f
+                contacts.append(a)
+            fusion.append(f)
+        return fusion, contacts
 
     def _panel_head_in_one_pass(self):
         """Whether the head may run once over the ``L * Qs`` rows of a panel: both of its norms are per row in ``eval()`` (``_None``,
@@ -288,28 +373,15 @@ class ArchitectureDTI(torch.nn.Module):
         The first call on an encoding reads the proteins' sizes back once and sums their rows per step (``ProteinEncoding.panel``);
         after it, a call on the same encoding and selection does no host synchronisation of its own."""
         self._screen_guard("screen_panel")
-        if not isinstance(enc, ProteinEncoding) or enc.model() is not self:
-            raise GlamHipError("screen_panel: the encoding was made by another model (its residue rows are that model's): encode_proteins() on this one")
-        if enc.stamp != self._protein_stamp() or len(enc.rows) != self.message_steps:
-            raise GlamHipError("screen_panel: the encoding is stale — a protein-side parameter or buffer (pro_lin0 / pro_conv / pro_readout / "
-                               "pro_flat) was written since encode_proteins(): encode again")
+        _check_encoding(self, "screen_panel", enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
         plan = enc.panel(proteins)                                 # host-side checks, before the first launch
-        nm = getattr(data_mol, "num_graphs", None) or None
-        msp = ops.segment_ptr(data_mol.batch, nm)
+        m = _Tower(self, "mol", data_mol)
+        msp = ops.segment_ptr(data_mol.batch, m.n)
         L, Qs = msp.B, plan.Qs
         with ops.weight_scope():
-            prestage_pass((self.mol_lin0, self.mol_conv, data_mol.x, data_mol.edge_attr))
-            xm = self.mol_lin0(data_mol.x, batch=data_mol.batch)
-            hm, fusion, contacts = None, [], []
-            for i in range(self.message_steps):
-                with ops.block_feeds_itself(i + 1 < self.message_steps):
-                    xm, hm = self.mol_conv(xm, data_mol.edge_index, data_mol.edge_attr, h=hm, batch=data_mol.batch)
-                f = dot_and_global_pool2_panel(xm, enc.rows[i], data_mol.batch, enc.sp, plan, None, enc.prosum[i], return_argmax)
-                if return_argmax:
-                    f, a = f
-                    contacts.append(a)
-                fusion.append(f)
-            outm = self.mol_flat(self.mol_readout(xm, data_mol.batch, nm))
+            fusion, contacts = self._ligand_walk(m, return_argmax, lambda x, i: dot_and_global_pool2_panel(
+                x, enc.rows[i], data_mol.batch, enc.sp, plan, None, enc.prosum[i], return_argmax))
+            outm = m.flat_out()
             outp = enc.flat.index_select(0, plan.on(enc.flat.device)[0].long())                   # [Qs, hid]
             if L == 0 or Qs == 0:
                 out = outm.new_zeros(L, Qs, self.lin_out1.linear.out_features)
@@ -324,27 +396,8 @@ class ArchitectureDTI(torch.nn.Module):
         return (out, contacts) if return_argmax else out
 
     # ---- training on shared proteins: the protein tower runs once per DISTINCT protein of the step ----------------------------
-    def _shared_guard(self):
-        slots = (("pro_lin0", self.pro_lin0, _PER_GRAPH_NORMS), ("pro_conv", self.pro_conv, _PER_GRAPH_NORMS),
-                 ("pro_flat", self.pro_flat, _PER_ROW_NORMS))
-        _tower_norms_guard("forward_shared", slots, "protein", "model(data_mol, data_pro)")
-        if self.training:
-            for name, block, _ in slots:
-                if type(block.norm) is _BatchNorm:
-                    raise GlamHipError(f"forward_shared: {name}'s norm _BatchNorm takes its batch statistics over the protein rows of the step, "
-                                       "and in model(data_mol, data_pro) those weigh each protein by how often it is repeated — over "
-                                       "proteins held once they are other statistics: train with model(data_mol, data_pro), or call "
-                                       "forward_shared in eval() (running statistics are per row)")
-
     def _shared_index(self, pro_of_pair, P, Q, device):
-        if pro_of_pair is not None:
-            return ops.pair_index(pro_of_pair, P, Q)
-        # the defaults are kept per (P, Q, device): the index a later capture of the same step meets already has its device copies
-        cache = self.__dict__.setdefault("_shared_defaults", {})
-        key = (P, Q, str(device))
-        if key not in cache:
-            cache[key] = ops.pair_index(None, P, Q, default="single" if Q == 1 else "identity")
-        return cache[key]
+        return _shared_index(self, pro_of_pair, P, Q, device, default="single" if Q == 1 else "identity")
 
     def forward_shared(self, data_mol, data_pro, pro_of_pair=None):
         """``model(data_mol, B_pro)`` -> ``[P, out_dim]`` for ``B_pro`` = the proteins ``pro_of_pair`` of ``data_pro`` collated one per
@@ -364,31 +417,19 @@ class ArchitectureDTI(torch.nn.Module):
         launch: the protein-side norms ``encode_proteins`` refuses (``_GraphSizeNorm``; ``_LayerNorm`` / ``_PairNorm`` in ``pro_flat``'s slot),
         and a protein-side ``_BatchNorm`` while training (batch statistics weigh each protein by how often it is repeated).
         Always eager by itself (no graphed-call route); inside a ``GraphedTrainStep`` it is captured with the step."""
-        self._shared_guard()
-        nm = getattr(data_mol, "num_graphs", None) or None
-        nq = getattr(data_pro, "num_graphs", None) or None
+        _shared_guard(self, _DTI_WORDS)
+        m, p = _Tower(self, "mol", data_mol), _Tower(self, "pro", data_pro)
         index = None
-        if nm is not None and nq is not None:          # (a collated Batch knows its counts: the index is checked before the first launch)
-            index = self._shared_index(pro_of_pair, nm, nq, data_mol.x.device)
-        msp, psp = ops.segment_ptr(data_mol.batch, nm), ops.segment_ptr(data_pro.batch, nq)
+        if m.n is not None and p.n is not None:          # (a collated Batch knows its counts: the index is checked before the first launch)
+            index = self._shared_index(pro_of_pair, m.n, p.n, data_mol.x.device)
+        msp, psp = ops.segment_ptr(data_mol.batch, m.n), ops.segment_ptr(data_pro.batch, p.n)
         if index is None:
             index = self._shared_index(pro_of_pair, msp.B, psp.B, data_mol.x.device)
         with ops.weight_scope():
-            prestage_pass((self.mol_lin0, self.mol_conv, data_mol.x, data_mol.edge_attr),
-                          (self.pro_lin0, self.pro_conv, data_pro.x, data_pro.edge_attr))
-            xm = self.mol_lin0(data_mol.x, batch=data_mol.batch)
-            xp = self.pro_lin0(data_pro.x, batch=data_pro.batch)
-            hm, hp, fusion = None, None, []
-            for i in range(self.message_steps):
-                with ops.block_feeds_itself(i + 1 < self.message_steps):
-                    xm, hm = self.mol_conv(xm, data_mol.edge_index, data_mol.edge_attr, h=hm, batch=data_mol.batch)
-                xp, hp = self.pro_conv(xp, data_pro.edge_index, data_pro.edge_attr, h=hp, batch=data_pro.batch)
-                f, xm, xp = dot_and_global_pool2_shared(xm, xp, data_mol.batch, psp, index, with_identity=True)
-                fusion.append(f)
-            outm = self.mol_flat(self.mol_readout(xm, data_mol.batch, nm))
-            outp = ops.pair_rows(self.pro_flat(self.pro_readout(xp, data_pro.batch, nq)), index)
-            out = ops.cat_cols([outm, outp] + fusion)
-            return self.lin_out1(self.lin_out0(out))
+            fusion = _fused_walk(self.message_steps, m, p, False,
+                                 lambda xm, xp: dot_and_global_pool2_shared(xm, xp, data_mol.batch, psp, index, with_identity=True))
+            outm = m.flat_out()
+            return self.lin_out1(self.lin_out0(ops.cat_cols([outm, ops.pair_rows(p.flat_out(), index)] + fusion)))
 
 
 class DrugEncoding:
@@ -438,23 +479,10 @@ class ArchitectureDDI(torch.nn.Module):
             return self._forward(mol1, mol2)
 
     def _forward(self, mol1, mol2):
-        prestage_pass((self.mol1_lin0, self.mol1_conv, mol1.x, mol1.edge_attr), (self.mol2_lin0, self.mol2_conv, mol2.x, mol2.edge_attr))
-        x1 = self.mol1_lin0(mol1.x, batch=mol1.batch)
-        x2 = self.mol2_lin0(mol2.x, batch=mol2.batch)
-        h1, h2 = None, None
-        fusion = []
-        for i in range(self.message_steps):
-            with ops.block_feeds_itself(i + 1 < self.message_steps):      # (the fusion hands the rows back untouched)
-                x1, h1 = self.mol1_conv(x1, mol1.edge_index, mol1.edge_attr, h=h1, batch=mol1.batch)
-                x2, h2 = self.mol2_conv(x2, mol2.edge_index, mol2.edge_attr, h=h2, batch=mol2.batch)
-            f, x1, x2 = dot_and_global_pool2(x1, x2, mol1.batch, mol2.batch, with_identity=True)
-            fusion.append(f)
-        n1 = getattr(mol1, "num_graphs", None) or None
-        n2 = getattr(mol2, "num_graphs", None) or None
-        o1 = self.mol1_flat(self.mol1_readout(x1, mol1.batch, n1))
-        o2 = self.mol2_flat(self.mol2_readout(x2, mol2.batch, n2))
-        out = ops.cat_cols([o1, o2] + fusion)
-        return self.lin_out1(self.lin_out0(out))
+        t1, t2 = _Tower(self, "mol1", mol1), _Tower(self, "mol2", mol2)
+        fusion = _fused_walk(self.message_steps, t1, t2, True,
+                             lambda x1, x2: dot_and_global_pool2(x1, x2, mol1.batch, mol2.batch, with_identity=True))
+        return self.lin_out1(self.lin_out0(ops.cat_cols([t1.flat_out(), t2.flat_out()] + fusion)))
 
     # ---- pair scoring: every drug is encoded once, a pair is two indices -----------------------------------------------------
     # The reference builds its pairs by looking both drugs up in one dictionary of molecule graphs (src_2gi_ddi/dataset.py:170-176) and
@@ -471,38 +499,24 @@ class ArchitectureDDI(torch.nn.Module):
         return _tower_stamp(self._drug_modules())
 
     def _pairs_guard(self, what):
-        if self.training:
-            raise GlamHipError(f"{what}: the model is in training mode — Dropout / RReLU noise is drawn per copy of a drug and BatchNorm takes "
-                               "statistics over the replicated rows, so one encoding cannot stand for the copies: call model.eval()")
-        if torch.is_grad_enabled():
-            raise GlamHipError(f"{what} is inference only (the gathered fusion has no backward): call it under torch.no_grad(); "
-                               "training runs model(mol1, mol2) on one graph per pair and side")
-        _tower_norms_guard(what, [(f"mol{t}_{slot}", getattr(self, f"mol{t}_{slot}"), ok) for t in (1, 2)
-                                  for slot, ok in (("lin0", _PER_GRAPH_NORMS), ("conv", _PER_GRAPH_NORMS), ("flat", _PER_ROW_NORMS))],
-                           "drug", "model(mol1, mol2)")
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise GlamHipError(f"{what} runs eagerly (its pair index is validated on the host and differs from call to call): not inside a "
-                               "hipGraph capture")
+        _inference_guard(self, what, _DDI_WORDS)
 
     def encode_drugs(self, data):
         """Both towers, once, over the ``Q`` graphs of ``data`` -> ``DrugEncoding`` for ``score_pairs``.  ``eval()`` mode under
         ``torch.no_grad()``; valid until a parameter or buffer of either tower changes."""
         self._pairs_guard("encode_drugs")
-        nq = getattr(data, "num_graphs", None) or None
+        t1, t2 = _Tower(self, "mol1", data), _Tower(self, "mol2", data)
         with ops.weight_scope():
-            prestage_pass((self.mol1_lin0, self.mol1_conv, data.x, data.edge_attr), (self.mol2_lin0, self.mol2_conv, data.x, data.edge_attr))
-            x1 = self.mol1_lin0(data.x, batch=data.batch)
-            x2 = self.mol2_lin0(data.x, batch=data.batch)
-            h1, h2, rows1, rows2 = None, None, [], []
+            _embed(t1, t2)
+            rows1, rows2 = [], []
             for i in range(self.message_steps):
                 with ops.block_feeds_itself(i + 1 < self.message_steps):      # (the routes of _forward: the rows are its rows bit for bit)
-                    x1, h1 = self.mol1_conv(x1, data.edge_index, data.edge_attr, h=h1, batch=data.batch)
-                    x2, h2 = self.mol2_conv(x2, data.edge_index, data.edge_attr, h=h2, batch=data.batch)
-                rows1.append(x1.contiguous())         # (odd widths flow as [N, C] views of padded rows: compacted here, once)
-                rows2.append(x2.contiguous())
-            sp = ops.segment_ptr(data.batch, nq)
-            flat1 = self.mol1_flat(self.mol1_readout(x1, data.batch, nq))
-            flat2 = self.mol2_flat(self.mol2_readout(x2, data.batch, nq))
+                    t1.step()
+                    t2.step()
+                rows1.append(t1.x.contiguous())       # (odd widths flow as [N, C] views of padded rows: compacted here, once)
+                rows2.append(t2.x.contiguous())
+            sp = ops.segment_ptr(data.batch, t1.n)
+            flat1, flat2 = t1.flat_out(), t2.flat_out()
         return DrugEncoding(self, rows1, rows2, sp, flat1, flat2, self._drug_stamp())
 
     def score_pairs(self, enc, first, second, return_argmax=False):
@@ -514,13 +528,9 @@ class ArchitectureDDI(torch.nn.Module):
         ``end_norm="_LayerNorm"`` a chunk scored alone differs from the same pairs scored inside a longer call).
         ``return_argmax``: also the per-step ``[P, 2]`` int32 contacts (row of ``enc.rows1[s]``, row of ``enc.rows2[s]``)."""
         self._pairs_guard("score_pairs")
-        if not isinstance(enc, DrugEncoding) or enc.model() is not self:
-            raise GlamHipError("score_pairs: the encoding was made by another model (its rows are that model's): encode_drugs() on this one")
-        if enc.stamp != self._drug_stamp() or len(enc.rows1) != self.message_steps:
-            raise GlamHipError("score_pairs: the encoding is stale — a parameter or buffer of a tower (mol1_* / mol2_* lin0, conv, readout, "
-                               "flat) was written since encode_drugs(): encode again")
+        _check_encoding(self, "score_pairs", enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
         Q = enc.num_graphs
-        P = first.P if isinstance(first, ops.PairIndex) else len(first)
+        P = ops.pair_count(first)
         i1 = ops.pair_index(first, P, Q, name="first", over="drugs")               # host-side, before the first launch
         i2 = ops.pair_index(second, P, Q, name="second", over="drugs")
         fusion, contacts = [], []
@@ -538,27 +548,8 @@ class ArchitectureDDI(torch.nn.Module):
         return (out, contacts) if return_argmax else out
 
     # ---- training on shared drugs: each tower runs once per DISTINCT drug of its side of the step ----------------------------
-    def _shared_guard(self):
-        slots = [(f"mol{t}_{slot}", getattr(self, f"mol{t}_{slot}"), ok) for t in (1, 2)
-                 for slot, ok in (("lin0", _PER_GRAPH_NORMS), ("conv", _PER_GRAPH_NORMS), ("flat", _PER_ROW_NORMS))]
-        _tower_norms_guard("forward_shared", slots, "drug", "model(mol1, mol2)")
-        if self.training:
-            for name, block, _ in slots:
-                if type(block.norm) is _BatchNorm:
-                    raise GlamHipError(f"forward_shared: {name}'s norm _BatchNorm takes its batch statistics over the drug rows of the step, "
-                                       "and in model(mol1, mol2) those weigh each drug by how often it is repeated — over drugs held "
-                                       "once they are other statistics: train with model(mol1, mol2), or call forward_shared in eval() "
-                                       "(running statistics are per row)")
-
     def _shared_index(self, given, P, Q, device, name):
-        if given is not None:
-            return ops.pair_index(given, P, Q, name=name, over="drugs")
-        # the defaults are kept per (P, Q, device): the index a later capture of the same step meets already has its device copies
-        cache = self.__dict__.setdefault("_shared_defaults", {})
-        key = (P, Q, str(device))
-        if key not in cache:
-            cache[key] = ops.pair_index(None, P, Q, name=name, over="drugs")
-        return cache[key]
+        return _shared_index(self, given, P, Q, device, name=name, over="drugs")
 
     def forward_shared(self, mol1, mol2, first=None, second=None):
         """``model(B1, B2)`` -> ``[P, out_dim]`` for ``B1`` = the drugs ``first`` of ``mol1`` and ``B2`` = the drugs ``second`` of ``mol2``
@@ -580,12 +571,9 @@ class ArchitectureDDI(torch.nn.Module):
         tower slot while training (batch statistics weigh each drug by how often it is repeated).  The head's norms are not refused: they
         see the same ``[P, .]`` matrix.  Always eager by itself (no graphed-call route); inside a ``GraphedTrainStep`` it is captured with
         the step."""
-        self._shared_guard()
-        n1 = getattr(mol1, "num_graphs", None) or None
-        n2 = getattr(mol2, "num_graphs", None) or None
-        given = first if first is not None else second
-        P = None if given is None else given.P if isinstance(given, ops.PairIndex) else len(given)
-        dev = mol1.x.device
+        _shared_guard(self, _DDI_WORDS)
+        t1, t2 = _Tower(self, "mol1", mol1), _Tower(self, "mol2", mol2)
+        n1, n2, P, dev = t1.n, t2.n, ops.pair_count(first, second), mol1.x.device
         i1 = i2 = None
         if n1 is not None and n2 is not None:          # (a collated Batch knows its counts: the indices are checked before the first launch)
             P = n1 if P is None else P
@@ -595,17 +583,8 @@ class ArchitectureDDI(torch.nn.Module):
             P = sp1.B if P is None else P
             i1, i2 = self._shared_index(first, P, sp1.B, dev, "first"), self._shared_index(second, P, sp2.B, dev, "second")
         with ops.weight_scope():
-            prestage_pass((self.mol1_lin0, self.mol1_conv, mol1.x, mol1.edge_attr), (self.mol2_lin0, self.mol2_conv, mol2.x, mol2.edge_attr))
-            x1 = self.mol1_lin0(mol1.x, batch=mol1.batch)
-            x2 = self.mol2_lin0(mol2.x, batch=mol2.batch)
-            h1, h2, fusion = None, None, []
-            for i in range(self.message_steps):
-                with ops.block_feeds_itself(i + 1 < self.message_steps):      # (the fusion hands the rows back untouched)
-                    x1, h1 = self.mol1_conv(x1, mol1.edge_index, mol1.edge_attr, h=h1, batch=mol1.batch)
-                    x2, h2 = self.mol2_conv(x2, mol2.edge_index, mol2.edge_attr, h=h2, batch=mol2.batch)
-                f, x1, x2 = dot_and_global_pool2_gather_shared(x1, x2, sp1, sp2, i1, i2, with_identity=True)
-                fusion.append(f)
-            o1 = ops.pair_rows(self.mol1_flat(self.mol1_readout(x1, mol1.batch, n1)), i1)
-            o2 = ops.pair_rows(self.mol2_flat(self.mol2_readout(x2, mol2.batch, n2)), i2)
-            out = ops.cat_cols([o1, o2] + fusion)
-            return self.lin_out1(self.lin_out0(out))
+            fusion = _fused_walk(self.message_steps, t1, t2, True,
+                                 lambda x1, x2: dot_and_global_pool2_gather_shared(x1, x2, sp1, sp2, i1, i2, with_identity=True))
+            o1 = ops.pair_rows(t1.flat_out(), i1)
+            o2 = ops.pair_rows(t2.flat_out(), i2)
+            return self.lin_out1(self.lin_out0(ops.cat_cols([o1, o2] + fusion)))

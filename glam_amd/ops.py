@@ -1348,10 +1348,10 @@ RELU_IN_WGRAD = True
 INFER_FWD = os.environ.get("GLAM_INFER_FWD", "1") != "0"
 
 
-# ---- the dense, readout and column-norm operator families live in their own modules; their names are part of this namespace ----
-from . import ops_dense as _ops_dense, ops_norm as _ops_norm, ops_readout as _ops_readout     # noqa: E402  (they read this module's state at call time)
+# ---- the dense, readout, pair-fusion and column-norm operator families live in their own modules; their names are part of this namespace ----
+from . import ops_dense as _ops_dense, ops_norm as _ops_norm, ops_pair as _ops_pair, ops_readout as _ops_readout     # noqa: E402  (they read this module's state at call time)
 
-for _m in (_ops_dense, _ops_readout, _ops_norm):
+for _m in (_ops_dense, _ops_readout, _ops_pair, _ops_norm):
     for _k, _v in vars(_m).items():
         if not _k.startswith("__") and _k != "_o" and _k not in globals():
             globals()[_k] = _v

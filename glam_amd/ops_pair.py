@@ -1,0 +1,572 @@
+"""Per-pair fusion pools (src_2gi_dti_scr/layer.py:270-283) and their held-once forms: indexed, panel, shared, gathered.
+
+Part of ``glam_amd.ops`` (every public name here is re-exported there: ``from glam_amd import ops; ops.pair_pool(...)``).
+
+The next fusion call is built from the helpers of this file, not from a copy of the call before it: ``host_ints`` validates a host
+vector of integers, ``_Staged`` keeps its per-device copies, ``_operands`` checks the two matrices, ``_outputs`` allocates what a launch
+writes, ``pair_count`` is "P of whichever index is given", and a Function that hands its inputs back is ``_alias_fwd`` /
+``_alias_bwd`` under a wrapper that ends in ``_apply_aliasing``."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import GlamHipError, f32c, ptr, require_device, stream
+from .ops_readout import segment_pool
+
+
+# --------------------------------------------------------------------------------------
+# what every call of the family shares
+# --------------------------------------------------------------------------------------
+def host_ints(v, name, entries, n=None, below=None, on_device=None, wrong=None):
+    """``v`` — a host sequence, numpy array or CPU tensor — as a 1-D integer numpy array (empty: ``int64[0]``), or the refusal: a device
+    tensor (``GlamHipError``: validating it would be a hidden read-back), a non-integer dtype, another shape than a vector (of ``n``
+    entries, if given), an entry below 0 or not below ``below`` (``IndexError``).  ``name`` / ``entries``: what the messages call the
+    vector and its shape ("have one entry per pair"); ``on_device`` / ``wrong``: a caller's own text for the device refusal / for every
+    other one."""
+    if torch.is_tensor(v):
+        if v.device.type != "cpu":
+            raise GlamHipError(on_device or f"{name} lives on a device: it is validated on the host before the launch, which would be a "
+                               "hidden read-back — pass the host sequence / numpy array / CPU tensor it was made from")
+        v = v.detach().numpy()
+    a = np.asarray(v)
+    if a.size == 0:
+        a = np.zeros(0, dtype=np.int64)
+    if a.dtype.kind not in "iu":
+        raise IndexError(wrong or f"{name} must hold integers, got {a.dtype}")
+    if a.ndim != 1 or (n is not None and a.shape[0] != n):
+        raise IndexError(wrong or f"{name} must {entries}: shape {tuple(a.shape)}" + ("" if n is None else f" for {n} pairs"))
+    if a.size and (int(a.min()) < 0 or (below is not None and int(a.max()) >= below)):
+        raise IndexError(wrong or f"{name} must lie in [0, {below}): got {int(a.min())} .. {int(a.max())}")
+    return a
+
+
+def _stage_int32(host, device, what):
+    """Device copy of a host int32 vector out of pinned memory (only enqueued).  Not inside a hipGraph capture: the copy would be baked
+    into the graph and the pinned buffer allocated under it — the eager first visit of a batch makes the copies a capture then finds."""
+    if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        raise GlamHipError(f"{what} has no copy on {device} yet and a hipGraph capture cannot make one: keep ONE PairIndex across the "
+                           "steps (ops.pair_index) and run the first step on it eagerly, as GraphedTrainStep does")
+    n = int(host.shape[0])
+    staged = torch.empty(max(n, 1), dtype=torch.int32, pin_memory=True)
+    staged.numpy()[:n] = host
+    return staged.to(device, non_blocking=True)[:n]
+
+
+class _Staged:
+    """Host int32 vectors — one, or two that travel together — and their device copies: ``on(device)`` is the copy (the pair of
+    copies), made once per device (ONE copy out of pinned memory, only enqueued) and shared by every launch that reads it."""
+
+    def __init__(self, what, *parts):
+        self._what, self._parts = what, parts
+        self._dev = {}
+
+    def on(self, device):
+        device = torch.device(device)
+        t = self._dev.get(device)
+        if t is None:
+            if len(self._parts) == 1:
+                t = _stage_int32(self._parts[0], device, self._what)
+            else:
+                n = int(self._parts[0].shape[0])
+                both = _stage_int32(np.concatenate(self._parts), device, self._what)      # (one copy)
+                t = (both[:n], both[n:])
+            self._dev[device] = t
+        return t
+
+
+def _operands(who, a, b, spa, spb, na, nb):
+    """The two matrices of a fusion call: on the device, 2-D, of one width, ``sp.N`` rows each -> both as contiguous fp32."""
+    require_device(a, b)
+    if a.dim() != 2 or b.dim() != 2 or a.size(1) != b.size(1) or a.size(0) != spa.N or b.size(0) != spb.N:
+        raise GlamHipError(f"{who}: the two sides disagree (width / node count): {na} {tuple(a.shape)} for {spa.N} rows, "
+                           f"{nb} {tuple(b.shape)} for {spb.N} rows")
+    return f32c(a, na), f32c(b, nb)
+
+
+def _outputs(shape, dev, arg=True, D=None, ws_bytes=None):
+    """What a fusion launch writes: ``out`` fp32 ``[*shape, 2]``, ``arg`` int32 ``[*shape, 2]`` (or None), ``sums`` fp32 ``[*shape, 2, D]``
+    (with ``D``: what a backward reads again) and the workspace of ``ws_bytes`` (never an empty one: it has no address)."""
+    return (torch.empty(*shape, 2, dtype=torch.float32, device=dev),
+            torch.empty(*shape, 2, dtype=torch.int32, device=dev) if arg else None,
+            None if D is None else torch.empty(*shape, 2, D, dtype=torch.float32, device=dev),
+            None if ws_bytes is None else torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev))
+
+
+def _alias_fwd(ctx, out, a_in, b_in, with_identity):
+    """What a fusion Function returns.  ``with_identity``: the two inputs come back as outputs — what the caller does with them next
+    sends its gradient HERE, into the backward launch of this node."""
+    ctx.aliased = bool(with_identity)
+    if ctx.aliased:
+        ctx.set_materialize_grads(False)
+        return out, a_in.view_as(a_in), b_in.view_as(b_in)
+    return out
+
+
+def _alias_bwd(d_out, d_a, d_b, a, b, na, nb, nothing_written=False):
+    """The incoming gradients of such a node -> ``(launch, d_out, d_a, d_b)``.  ``launch``: the three are ready for the entry point
+    (contiguous fp32; ``d_a`` / ``d_b``, the gradients of the inputs' next use, may be None).  Not ``launch``: ``d_a, d_b`` ARE the
+    input gradients — the fusion values were not used (``d_out`` is None: only with the aliases), or the entry point writes nothing
+    (``nothing_written``) and the gradients are those of the next use, or zeros."""
+    if d_out is None:
+        return False, None, d_a, d_b
+    d_out = f32c(d_out, "d_out")
+    d_a = None if d_a is None else f32c(d_a, f"d_{na} (next use)")
+    d_b = None if d_b is None else f32c(d_b, f"d_{nb} (next use)")
+    if nothing_written:
+        return False, None, torch.zeros_like(a) if d_a is None else d_a, torch.zeros_like(b) if d_b is None else d_b
+    return True, d_out, d_a, d_b
+
+
+def _apply_aliasing(fn, args, a, b, with_identity, add_width=None):
+    """``fn.apply(*args)``; ``with_identity``: ``(out, a, b)`` — through the node where its backward launch can take the gradients of
+    their next use (both require grad, fp32), the plain inputs appended otherwise.  ``add_width``: ask the library whether that width
+    has the adding backward (None: every width of the entry point's table has it)."""
+    if not with_identity:
+        return fn.apply(*args)
+    # (is_cuda: a CPU operand goes on to require_device's refusal in the forward, not to a query of the library)
+    if (torch.is_grad_enabled() and a.requires_grad and b.requires_grad and a.is_cuda and a.dtype == torch.float32
+            and b.dtype == torch.float32 and (add_width is None or _lib.api().glam_pair_pool_add_supported(add_width) == 1)):
+        return fn.apply(*args, True)
+    return fn.apply(*args), a, b
+
+
+# --------------------------------------------------------------------------------------
+# one graph per pair and side (csrc/pairpool.hip)
+# --------------------------------------------------------------------------------------
+class _PairPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mol, pro, msp, psp, with_identity=False):
+        mol_in, pro_in = mol, pro
+        mol, pro = _operands("pair_pool", mol, pro, msp, psp, "mol_out", "pro_out")
+        if msp.B != psp.B:
+            raise GlamHipError(f"pair_pool: the two batches disagree (pair count): {msp.B} ligand graphs, {psp.B} protein graphs")
+        P, D = msp.B, mol.size(1)
+        lib = _lib.api()
+        out, arg, sums, ws = _outputs((P,), mol.device, D=D, ws_bytes=lib.glam_pair_pool_workspace_bytes(P, D))
+        lib.glam_pair_pool_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), P, D, ptr(out), ptr(arg), ptr(sums), ptr(ws), ws.numel(), stream())
+        ctx.save_for_backward(mol, pro, arg, sums)
+        ctx.sps = (msp, psp)
+        return _alias_fwd(ctx, out, mol_in, pro_in, with_identity)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, d_ma=None, d_pa=None):
+        mol, pro, arg, sums = ctx.saved_tensors
+        msp, psp = ctx.sps
+        launch, d_out, d_ma, d_pa = _alias_bwd(d_out, d_ma, d_pa, mol, pro, "mol", "pro")
+        if not launch:
+            return d_ma, d_pa, None, None, None
+        d_mol, d_pro = torch.empty_like(mol), torch.empty_like(pro)
+        lib = _lib.api()
+        if d_ma is not None or d_pa is not None:      # (two entry points: the library's choice)
+            lib.glam_pair_pool_bwd_add(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(arg), ptr(sums), ptr(d_out), msp.B, mol.size(1),
+                                       ptr(d_ma), ptr(d_pa), ptr(d_mol), ptr(d_pro), stream())
+        else:
+            lib.glam_pair_pool_bwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(arg), ptr(sums), ptr(d_out), msp.B,
+                                   mol.size(1), ptr(d_mol), ptr(d_pro), stream())
+        return d_mol, d_pro, None, None, None
+
+
+def pair_pool(mol_out, pro_out, msp, psp, with_identity=False):
+    """``[max, mean]`` of ``mol[seg_i] @ pro[seg_i].T`` per pair -> ``[P, 2]`` (dot_and_global_pool2).  ``with_identity``: returns
+    ``(out, mol_out, pro_out)`` with the two matrices handed back through this node where that saves the add launches of their second
+    use (the next message step): its gradient is then added inside this node's backward launch."""
+    # (add_width: glam_pair_pool_bwd_add exists for the widths the library names)
+    return _apply_aliasing(_PairPool, (mol_out, pro_out, msp, psp), mol_out, pro_out, with_identity,
+                           add_width=mol_out.size(1) if with_identity else None)
+
+
+class _PairPool5(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mol, pro, msp, psp):
+        require_device(mol, pro)
+        mol, pro = f32c(mol, "mol_out"), f32c(pro, "pro_out")
+        if msp.B != psp.B or mol.size(1) != pro.size(1) or mol.size(0) != msp.N or pro.size(0) != psp.N:
+            raise GlamHipError("pair_pool5: the two batches disagree (pair count / width / node count)")
+        P, D = msp.B, mol.size(1)
+        out = torch.empty(P, 5, dtype=torch.float32, device=mol.device)
+        arg = torch.empty(P, 6, dtype=torch.int32, device=mol.device)
+        _lib.api().glam_pair_pool5_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), P, D, ptr(out), ptr(arg), stream())
+        ctx.save_for_backward(mol, pro, out, arg)
+        ctx.sps = (msp, psp)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        mol, pro, out, arg = ctx.saved_tensors
+        msp, psp = ctx.sps
+        d_out = f32c(d_out, "d_out")
+        d_mol, d_pro = torch.empty_like(mol), torch.empty_like(pro)
+        _lib.api().glam_pair_pool5_bwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(out), ptr(arg), ptr(d_out), msp.B,
+                                       mol.size(1), ptr(d_mol), ptr(d_pro), stream())
+        return d_mol, d_pro, None, None
+
+
+def pair_pool5(mol_out, pro_out, msp, psp):
+    """``[max, mean, median, min, std]`` of ``mol[seg_i] @ pro[seg_i].T`` per pair -> ``[P, 5]`` (dot_and_global_pool5);
+    widths that are multiples of 4 up to 128 (``pad_cols`` the operands first: zero columns do not change a score)."""
+    return _PairPool5.apply(mol_out, pro_out, msp, psp)
+
+
+# --------------------------------------------------------------------------------------
+# screening: the fusion against proteins that are held once (csrc/pairpool.hip, glam_pair_pool_indexed_fwd)
+# --------------------------------------------------------------------------------------
+class PairIndex(_Staged):
+    """A validated pair -> protein index: ``host`` int32 ``[P]`` (numpy) with every entry in ``[0, Q)``.  ``on(device)`` is its device
+    copy, made once per device (out of pinned memory, only enqueued) and shared by every launch that reads it."""
+
+    def __init__(self, host, Q):
+        _Staged.__init__(self, "the pair -> protein index", host)
+        self.host, self.P, self.Q = host, int(host.shape[0]), int(Q)
+        self._by_protein = None
+
+    def by_protein(self):
+        """The pairs grouped by protein, for the sums of the training call (``ops.pair_pool_shared`` / ``ops.pair_rows``): ``order`` int32
+        ``[P]`` — the stable argsort of the index (the pairs of a protein keep their batch order) — and ``ptr`` int32 ``[Q + 1]``, the
+        offsets of the proteins' runs in it.  Built once, on the host; ``.on(device)`` -> their device copies, made once per device."""
+        if self._by_protein is None:
+            self._by_protein = PairsByProtein(self.host, self.Q)
+        return self._by_protein
+
+
+class PairsByProtein(_Staged):
+    """``order`` / ``ptr`` of ``PairIndex.by_protein`` (host, int32 numpy) and their device copies."""
+
+    def __init__(self, host, Q):
+        P, Q = int(host.shape[0]), int(Q)
+        if P and (int(host.min()) < 0 or int(host.max()) >= Q):
+            raise IndexError(f"the pair -> protein index must lie in [0, {Q})")
+        self.order = np.argsort(host, kind="stable").astype(np.int32)
+        self.ptr = np.zeros(Q + 1, dtype=np.int32)
+        np.cumsum(np.bincount(host, minlength=Q)[:Q], out=self.ptr[1:])
+        if int(self.ptr[-1]) != P:
+            raise IndexError("the pair -> protein index does not sort into its proteins' runs")
+        self.P, self.Q = P, Q
+        _Staged.__init__(self, "the pair list by protein", self.order, self.ptr)
+
+
+def pair_index(pro_of_pair, P, Q, default="identity", name="pro_of_pair", over="proteins"):
+    """``PairIndex`` of ``pro_of_pair`` for ``P`` pairs over ``Q`` proteins — host only, before anything is launched (the kernel trusts
+    the index; the policy of ``data.resident_table``).  A host sequence, numpy array or CPU tensor of integers of length ``P``;
+    ``IndexError`` for a wrong length or an entry outside ``[0, Q)``; a device tensor is refused (validating it would be a hidden
+    read-back).  ``None``: ``default="identity"`` pairs ligand i with protein i (needs ``Q == P``), ``default="single"`` pairs every
+    ligand with the one protein (needs ``Q == 1``).  ``name`` / ``over``: what the messages call the index and the things it points
+    into (``ops.pair_pool_gather`` validates ``idx1`` / ``idx2`` over drugs with the same rules)."""
+    P, Q = int(P), int(Q)
+    if isinstance(pro_of_pair, PairIndex):
+        if pro_of_pair.P != P or pro_of_pair.Q != Q:
+            raise IndexError(f"{name} was validated for {pro_of_pair.P} pairs over {pro_of_pair.Q} {over}, not {P} over {Q}")
+        return pro_of_pair
+    if pro_of_pair is None:
+        if default == "identity":
+            if Q != P:
+                if name != "pro_of_pair":
+                    raise IndexError(f"{name}=None takes segment i for pair i: {P} pairs but {Q} {over}")
+                raise IndexError(f"pro_of_pair=None pairs ligand i with protein i: {P} ligands but {Q} proteins")
+            return PairIndex(np.arange(P, dtype=np.int32), Q)
+        if Q != 1:
+            raise IndexError(f"pro_of_pair=None screens against the one encoded protein, but the encoding holds {Q}: pass the index")
+        return PairIndex(np.zeros(P, dtype=np.int32), Q)
+    return PairIndex(host_ints(pro_of_pair, name, "have one entry per pair", n=P, below=Q).astype(np.int32), Q)
+
+
+def pair_count(idx1, idx2=None, default=None):
+    """``P`` of whichever index is given — a ``PairIndex`` or a host vector; ``default`` when neither is."""
+    given = idx1 if idx1 is not None else idx2
+    return default if given is None else given.P if isinstance(given, PairIndex) else len(given)
+
+
+def pair_pool_indexed(mol_out, pro_out, msp, psp, pro_of_pair=None, return_argmax=False):
+    """``[max, mean]`` of ``mol[seg_i] @ pro[seg_q].T`` with ``q = pro_of_pair[i]`` -> ``[P, 2]``: ``pair_pool`` against proteins that are
+    held once (``psp.B`` segments) instead of once per pair.  The max column — and with ``return_argmax`` the ``[P, 2]`` int32 rows of
+    the maximum in ``mol_out`` / ``pro_out`` (-1 for an empty pair) — is bit for bit that of ``pair_pool`` on replicated residue rows.
+    ``pro_of_pair``: see ``pair_index`` (``None`` = identity).  Inference only: there is no backward (training is ``ops.pair_pool``)."""
+    P, Q = msp.B, psp.B
+    index = pair_index(pro_of_pair, P, Q)
+    if torch.is_grad_enabled() and (mol_out.requires_grad or pro_out.requires_grad):
+        raise GlamHipError("pair_pool_indexed is inference only (no backward): call it under torch.no_grad(); the training route is "
+                           "ops.pair_pool on one protein graph per pair")
+    mol, pro = _operands("pair_pool_indexed", mol_out, pro_out, msp, psp, "mol_out", "pro_out")
+    D = mol.size(1)
+    lib = _lib.api()
+    out, arg, _, ws = _outputs((P,), mol.device, arg=return_argmax, ws_bytes=lib.glam_pair_pool_workspace_bytes(P, D))
+    lib.glam_pair_pool_indexed_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(index.on(mol.device)), P, Q, D, ptr(out), ptr(arg),
+                                   ptr(ws), ws.numel(), stream())
+    return (out, arg) if return_argmax else out
+
+
+# --------------------------------------------------------------------------------------
+# panel screening: every ligand against every selected protein, protein-stationary (csrc/pairpanel.hip, glam_pair_pool_panel_fwd)
+# --------------------------------------------------------------------------------------
+PANEL_CHUNK = 64      # residue rows per chunk (one per lane of the wave that holds them) = kPanelChunk of csrc/pairpanel.hip
+
+
+class PanelPlan(_Staged):
+    """The work of one panel call over a validated selection: ``sel`` int32 ``[Qs]`` (every entry in ``[0, Q)``) and ``work`` int32
+    ``[4 * total_chunks + Qs + 1]`` — per chunk of 64 residue rows, in selection order, ``(j, first row of the chunk in the encoding,
+    rows in the chunk, index of its partials in the workspace)``, then ``chunk_ptr[Qs + 1]``, the offsets of the selections' chunk
+    runs (``chunks`` / ``chunk_ptr`` are views of it).  Host numpy; ``on(device)`` -> ``(sel, work)`` on the device, made once per
+    device (one copy out of pinned memory, only enqueued) and shared by every launch that reads them."""
+
+    def __init__(self, sel, sizes):
+        self.sel, self.Qs, self.Q = sel, int(sel.shape[0]), int(sizes.shape[0])
+        first = np.zeros(self.Q + 1, dtype=np.int64)
+        np.cumsum(sizes, out=first[1:])
+        if int(first[-1]) >= 2 ** 31 - 1:
+            raise IndexError("panel_plan: the proteins hold 2^31 residue rows or more")
+        self.N = int(first[-1])
+        n_chunks = (sizes[sel] + PANEL_CHUNK - 1) // PANEL_CHUNK                     # per selection
+        chunk_ptr = np.zeros(self.Qs + 1, dtype=np.int64)
+        np.cumsum(n_chunks, out=chunk_ptr[1:])
+        self.total_chunks = T = int(chunk_ptr[-1])
+        if T >= 2 ** 31 - 1:
+            raise IndexError("panel_plan: the selection has 2^31 chunks or more")
+        j = np.repeat(np.arange(self.Qs, dtype=np.int64), n_chunks)
+        c = np.arange(T, dtype=np.int64) - chunk_ptr[j]                              # chunk inside its protein
+        table = np.empty((T, 4), dtype=np.int32)
+        table[:, 0] = j
+        table[:, 1] = first[sel[j]] + PANEL_CHUNK * c
+        table[:, 2] = np.minimum(sizes[sel[j]] - PANEL_CHUNK * c, PANEL_CHUNK)
+        table[:, 3] = np.arange(T)
+        self.work = np.concatenate([table.reshape(-1), chunk_ptr.astype(np.int32)])
+        self.chunks, self.chunk_ptr = self.work[:4 * T].reshape(T, 4), self.work[4 * T:]
+        _Staged.__init__(self, "the panel's selection and work table", self.sel, self.work)
+
+
+def panel_plan(sizes_host, proteins=None):
+    """``PanelPlan`` of the selection ``proteins`` over ``Q = len(sizes_host)`` proteins of ``sizes_host[q]`` residue rows — host only
+    (numpy), before anything is launched (the kernel trusts the table; the policy of ``pair_index``).  ``proteins``: ``None`` = all
+    ``Q`` in order, or a host sequence / numpy array / CPU tensor of integers in ``[0, Q)``, in any order, duplicates allowed;
+    ``IndexError`` for a wrong dtype or an entry outside ``[0, Q)``; a device tensor is refused (validating it would be a hidden
+    read-back)."""
+    sizes = host_ints(sizes_host, "sizes", None, wrong="panel_plan: the proteins' sizes must be a vector of non-negative integers",
+                      on_device="panel_plan: the proteins' sizes live on a device: the plan is built on the host — pass their host copy")
+    sizes = sizes.astype(np.int64)
+    Q = int(sizes.shape[0])
+    if proteins is None:
+        return PanelPlan(np.arange(Q, dtype=np.int32), sizes)
+    return PanelPlan(host_ints(proteins, "proteins", "be a vector of protein numbers", below=Q).astype(np.int32), sizes)
+
+
+def pair_pool_panel(mol_out, pro_out, msp, psp, plan, molsum=None, prosum=None, return_argmax=False, slab=0):
+    """``[max, mean]`` of ``mol[seg_l] @ pro[seg_q].T`` for EVERY ligand ``l`` and every selected protein ``q = plan.sel[j]`` ->
+    ``[L, Qs, 2]``: the panel of ``Qs`` calls of ``pair_pool_indexed`` with ``pro_of_pair = [sel[j]] * L`` from one protein-stationary
+    launch (+ a finish launch).  The max column — and with ``return_argmax`` the ``[L, Qs, 2]`` int32 rows of the maximum in ``mol_out``
+    / ``pro_out`` (-1 for an empty ligand or protein) — is bit for bit that of those calls; the mean is ``<molsum[l], prosum[q]> /
+    (n_l n_q)`` and within the fp64-twin bound.  ``plan``: ``panel_plan`` over the sizes of ``psp``'s segments.  ``molsum`` ``[L, D]``
+    / ``prosum`` ``[Q, D]``: the segments' column sums (``segment_pool(x, sp, "sum")``), computed here when missing — a caller that
+    keeps the proteins keeps ``prosum`` too.  ``slab``: ligands per wave, 0 = the library chooses.  Widths 1..128.  Inference only:
+    there is no backward (training is ``ops.pair_pool`` / ``ops.pair_pool_shared``)."""
+    if not isinstance(plan, PanelPlan):
+        raise GlamHipError("pair_pool_panel: plan must come from ops.panel_plan (the kernel trusts its table)")
+    L, Q, Qs = msp.B, psp.B, plan.Qs
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (mol_out, pro_out, molsum, prosum)):
+        raise GlamHipError("pair_pool_panel is inference only (no backward): call it under torch.no_grad(); the training routes are "
+                           "ops.pair_pool on one protein graph per pair and ops.pair_pool_shared on proteins held once")
+    if plan.Q != Q or plan.N != psp.N:
+        raise GlamHipError(f"pair_pool_panel: the plan was made for {plan.Q} proteins of {plan.N} residue rows, the encoding holds {Q} of {psp.N}")
+    mol, pro = _operands("pair_pool_panel", mol_out, pro_out, msp, psp, "mol_out", "pro_out")
+    D, dev = mol.size(1), mol.device
+    for name, t, rows in (("molsum", molsum, L), ("prosum", prosum, Q)):
+        if t is not None and (t.dim() != 2 or tuple(t.shape) != (rows, D) or t.device != dev):
+            raise GlamHipError(f"pair_pool_panel: {name} must be the [{rows}, {D}] column sums on {dev}, got {tuple(t.shape)} on {t.device}")
+    if int(slab) < 0:
+        raise GlamHipError(f"pair_pool_panel: slab must be 0 (choose) or the ligands per wave, got {slab}")
+    lib = _lib.api()
+    if _lib.load().glam_pair_pool_panel_supported(D) != 0:          # (a status: the raw binding hands it back)
+        raise GlamHipError(f"pair_pool_panel: width {D} is outside the kernel table (1..128)")
+    out, arg, _, _ = _outputs((L, Qs), dev, arg=return_argmax)
+    if L and Qs and (msp.N == 0 or psp.N == 0):          # no row on one side: every pair is empty (and the empty matrix has no address to pass)
+        out.zero_()
+        if return_argmax:
+            arg.fill_(-1)
+    elif L and Qs:
+        molsum = f32c(molsum, "molsum") if molsum is not None else segment_pool(mol, msp, "sum")
+        prosum = f32c(prosum, "prosum") if prosum is not None else segment_pool(pro, psp, "sum")
+        sel, work = plan.on(dev)
+        ws = torch.empty(max(lib.glam_pair_pool_panel_workspace_bytes(plan.total_chunks, L), 16), dtype=torch.uint8, device=dev)
+        lib.glam_pair_pool_panel_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(work), plan.total_chunks, ptr(sel), Qs, L, Q, D,
+                                     ptr(molsum), ptr(prosum), int(slab), ptr(out), ptr(arg), ptr(ws), ws.numel(), stream())
+    return (out, arg) if return_argmax else out
+
+
+# --------------------------------------------------------------------------------------
+# training against proteins held once: the indexed fusion with a backward (csrc/pairshared.hip)
+# --------------------------------------------------------------------------------------
+class _PairPoolShared(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mol, pro, msp, psp, index, with_identity=False):
+        mol_in, pro_in = mol, pro
+        mol, pro = _operands("pair_pool_shared", mol, pro, msp, psp, "mol_out", "pro_out")
+        P, Q, D, dev = msp.B, psp.B, mol.size(1), mol.device
+        pidx = index.on(dev)
+        order, qptr = index.by_protein().on(dev)
+        lib = _lib.api()
+        out, arg, sums, ws = _outputs((P,), dev, D=D, ws_bytes=lib.glam_pair_pool_workspace_bytes(P, D))
+        lib.glam_pair_pool_shared_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(pidx), P, Q, D, ptr(out), ptr(arg), ptr(sums),
+                                      ptr(ws), ws.numel(), stream())
+        ctx.save_for_backward(mol, pro, arg, sums, pidx, order, qptr)
+        ctx.sps = (msp, psp)
+        return _alias_fwd(ctx, out, mol_in, pro_in, with_identity)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, d_ma=None, d_pa=None):
+        mol, pro, arg, sums, pidx, order, qptr = ctx.saved_tensors
+        msp, psp = ctx.sps
+        # (no pair: the entry point writes nothing)
+        launch, d_out, d_ma, d_pa = _alias_bwd(d_out, d_ma, d_pa, mol, pro, "mol", "pro", nothing_written=msp.B == 0)
+        if not launch:
+            return d_ma, d_pa, None, None, None, None
+        d_mol, d_pro = torch.empty_like(mol), torch.empty_like(pro)
+        _lib.api().glam_pair_pool_shared_bwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(pidx), ptr(order), ptr(qptr), ptr(arg),
+                                             ptr(sums), ptr(d_out), msp.B, psp.B, mol.size(1), ptr(d_ma), ptr(d_pa), ptr(d_mol),
+                                             ptr(d_pro), stream())
+        return d_mol, d_pro, None, None, None, None
+
+
+def pair_pool_shared(mol_out, pro_out, msp, psp, pro_of_pair=None, with_identity=False):
+    """``pair_pool_indexed`` WITH a backward: ``[max, mean]`` of ``mol[seg_i] @ pro[seg_q].T`` with ``q = pro_of_pair[i]`` -> ``[P, 2]``
+    against proteins held once (``psp.B`` segments), for training.  The forward is bit for bit ``pair_pool_indexed``; the gradient of a
+    protein's residue rows is the sum over every pair that points at it, taken in batch order without atomics (two runs are
+    bit-equal); a protein no pair references gets zeros.  ``pro_of_pair``: see ``pair_index`` (``None`` = identity; every ligand against
+    the one protein when ``psp.B == 1``).  ``with_identity``:
+    as ``pair_pool`` — ``(out, mol_out, pro_out)`` with the two matrices handed back through the node where its backward launch can
+    add their later gradients itself (``glam_pair_pool_add_supported``), the plain triple otherwise."""
+    P, Q = msp.B, psp.B
+    index = pair_index(pro_of_pair, P, Q, default="single" if Q == 1 and P != 1 else "identity")
+    # (add_width: the adding form of glam_pair_pool_shared_bwd covers the widths of glam_pair_pool_bwd_add)
+    return _apply_aliasing(_PairPoolShared, (mol_out, pro_out, msp, psp, index), mol_out, pro_out, with_identity,
+                           add_width=mol_out.size(1) if with_identity else None)
+
+
+class _PairRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flat, index):
+        pidx = index.on(flat.device)
+        order, qptr = index.by_protein().on(flat.device)
+        ctx.save_for_backward(order, qptr)
+        ctx.dims = (index.P, index.Q, tuple(flat.shape[1:]))
+        return flat.index_select(0, pidx)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_rows):
+        order, qptr = ctx.saved_tensors
+        P, Q, tail = ctx.dims
+        d_rows = f32c(d_rows, "d_rows")
+        W = int(np.prod(tail, dtype=np.int64))
+        if P == 0 or W == 0:
+            return torch.zeros((Q,) + tail, dtype=torch.float32, device=d_rows.device), None
+        d_flat = torch.empty((Q,) + tail, dtype=torch.float32, device=d_rows.device)
+        _lib.api().glam_pair_rows_bwd(ptr(d_rows), ptr(order), ptr(qptr), P, Q, W, ptr(d_flat), stream())
+        return d_flat, None
+
+
+def pair_rows(flat, index):
+    """``flat[index]`` -> ``[P, ...]``: the rows of a matrix that holds every protein once, one per pair (``index``: a ``PairIndex`` or
+    what ``pair_index`` accepts, over ``flat.size(0)`` rows).  Its backward sums the pairs' rows per protein in batch order
+    (``glam_pair_rows_bwd``): ``index_select``'s own backward is an atomic ``index_add``, whose bits change from run to run."""
+    if not isinstance(index, PairIndex):
+        index = pair_index(index, len(index), flat.size(0))
+    elif index.Q != flat.size(0):
+        raise IndexError(f"pair_rows: the index was validated over {index.Q} rows, the matrix has {flat.size(0)}")
+    require_device(flat)
+    if flat.dtype != torch.float32:
+        raise GlamHipError(f"pair_rows: expected float32, got {flat.dtype}")
+    return _PairRows.apply(flat, index)
+
+
+# --------------------------------------------------------------------------------------
+# drug x drug: the fusion with BOTH sides held once and both indexed (csrc/pairgather.hip, glam_pair_pool_gather_fwd)
+# --------------------------------------------------------------------------------------
+def pair_pool_gather(x1, x2, sp1, sp2, idx1=None, idx2=None, return_argmax=False):
+    """``[max, mean]`` of ``x1[seg_a] @ x2[seg_b].T`` with ``a = idx1[i]``, ``b = idx2[i]`` -> ``[P, 2]``: ``pair_pool`` on two sets of
+    small segments that are each held once (``sp1.B`` / ``sp2.B`` of them) — one wave per pair, one launch.  The max column — and with
+    ``return_argmax`` the ``[P, 2]`` int32 rows of the maximum in ``x1`` / ``x2`` (-1 for an empty pair) — is bit for bit that of
+    ``pair_pool`` on physically gathered rows; the mean is the same bits on every run and within the fp64-twin bound.
+    ``idx1`` / ``idx2``: see ``pair_index``; ``None`` = identity on that side (needs ``sp.B == P``); ``P`` is the length of whichever is
+    given.  Widths 1..128.  Inference only: there is no backward (training is ``ops.pair_pool`` on one graph per pair and side)."""
+    Q1, Q2 = sp1.B, sp2.B
+    P = pair_count(idx1, idx2, Q1)
+    i1 = None if idx1 is None and Q1 == P else pair_index(idx1, P, Q1, name="idx1", over="segments of x1")
+    i2 = None if idx2 is None and Q2 == P else pair_index(idx2, P, Q2, name="idx2", over="segments of x2")
+    if torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
+        raise GlamHipError("pair_pool_gather is inference only (no backward): call it under torch.no_grad(); the training route is "
+                           "ops.pair_pool on one graph per pair and side")
+    x1, x2 = _operands("pair_pool_gather", x1, x2, sp1, sp2, "x1", "x2")
+    D = x1.size(1)
+    lib = _lib.api()
+    if lib.glam_pair_pool_gather_load_bytes(ptr(x1), ptr(x2), D) == 0:
+        raise GlamHipError(f"pair_pool_gather: width {D} is outside the kernel table (1..128)")
+    out, arg, _, _ = _outputs((P,), x1.device, arg=return_argmax)
+    lib.glam_pair_pool_gather_fwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if i1 is None else i1.on(x1.device)),
+                                  ptr(None if i2 is None else i2.on(x1.device)), P, Q1, Q2, D, ptr(out), ptr(arg), stream())
+    return (out, arg) if return_argmax else out
+
+
+# --------------------------------------------------------------------------------------
+# training on drugs held once: the gathered fusion with a backward (csrc/pairgather.hip train_fwd, csrc/pairgather_bwd.hip)
+# --------------------------------------------------------------------------------------
+class _PairPoolGatherShared(torch.autograd.Function):
+    """``i1`` / ``i2``: the validated ``PairIndex`` of each side (an identity side too: its by-drug lists are read by the backward);
+    ``null1`` / ``null2``: hand the kernels a NULL index on that side (identity)."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, sp1, sp2, i1, i2, null1, null2, with_identity=False):
+        x1_in, x2_in = x1, x2
+        x1, x2 = _operands("pair_pool_gather_shared", x1, x2, sp1, sp2, "x1", "x2")
+        P, Q1, Q2, D, dev = i1.P, sp1.B, sp2.B, x1.size(1), x1.device
+        # (the table in Python: the training entry points have no query, and their dword form takes every alignment)
+        if not 1 <= D <= 128:
+            raise GlamHipError(f"pair_pool_gather_shared: width {D} is outside the kernel table (1..128)")
+        d1, d2 = i1.on(dev), i2.on(dev)
+        order1, lptr1 = i1.by_protein().on(dev)
+        order2, lptr2 = i2.by_protein().on(dev)
+        out, arg, sums, _ = _outputs((P,), dev, D=D)
+        ctx.rows = x1.size(0) > 0 and x2.size(0) > 0
+        if ctx.rows:
+            _lib.api().glam_pair_pool_gather_train_fwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if null1 else d1),
+                                                       ptr(None if null2 else d2), P, Q1, Q2, D, ptr(out), ptr(arg), ptr(sums), stream())
+        else:                # no row on one side: every pair is empty (and the empty matrix has no address to pass)
+            out.zero_()
+            arg.fill_(-1)
+        ctx.save_for_backward(x1, x2, arg, sums, d1, d2, order1, lptr1, order2, lptr2)
+        ctx.sps, ctx.null, ctx.P = (sp1, sp2), (bool(null1), bool(null2)), P
+        return _alias_fwd(ctx, out, x1_in, x2_in, with_identity)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, d_a1=None, d_a2=None):
+        x1, x2, arg, sums, d1, d2, order1, lptr1, order2, lptr2 = ctx.saved_tensors
+        sp1, sp2 = ctx.sps
+        none = (None,) * 7
+        # (no pair, or only empty ones: the entry point writes nothing)
+        launch, d_out, d_a1, d_a2 = _alias_bwd(d_out, d_a1, d_a2, x1, x2, "x1", "x2", nothing_written=ctx.P == 0 or not ctx.rows)
+        if not launch:
+            return (d_a1, d_a2) + none
+        d_x1, d_x2 = torch.empty_like(x1), torch.empty_like(x2)
+        _lib.api().glam_pair_pool_gather_bwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if ctx.null[0] else d1),
+                                             ptr(None if ctx.null[1] else d2), ptr(order1), ptr(lptr1), ptr(order2), ptr(lptr2), ptr(arg),
+                                             ptr(sums), ptr(d_out), ctx.P, sp1.B, sp2.B, x1.size(1), ptr(d_a1), ptr(d_a2), ptr(d_x1),
+                                             ptr(d_x2), stream())
+        return (d_x1, d_x2) + none
+
+
+def pair_pool_gather_shared(x1, x2, sp1, sp2, idx1=None, idx2=None, with_identity=False):
+    """``pair_pool_gather`` WITH a backward: ``[max, mean]`` of ``x1[seg_a] @ x2[seg_b].T`` with ``a = idx1[i]``, ``b = idx2[i]`` ->
+    ``[P, 2]`` on two sets of small segments that are each held once, for training.  The forward is bit for bit ``pair_pool_gather``; the
+    gradient of a segment's rows — on EITHER side — is the sum over every pair that points at it, taken in batch order without atomics
+    (two runs are bit-equal, one launch for both sides); a segment no pair references gets zeros.  ``idx1`` / ``idx2``: as
+    ``pair_pool_gather`` (``pair_index``; ``None`` = identity on that side, needs ``sp.B == P``); keep ONE ``PairIndex`` per side across
+    the steps that use it — its device copies are made on the first, eager, visit and a hipGraph capture needs them to exist.  Widths
+    1..128.  ``with_identity``: as ``pair_pool`` — ``(out, x1, x2)`` with the two matrices handed back through the node (both require
+    grad, fp32): its backward launch then adds their later gradients itself; the plain triple otherwise."""
+    P = pair_count(idx1, idx2, sp1.B)
+    i1 = pair_index(idx1, P, sp1.B, name="idx1", over="segments of x1")
+    i2 = pair_index(idx2, P, sp2.B, name="idx2", over="segments of x2")
+    # (no add_width: glam_pair_pool_gather_bwd adds inside its launch for every width of its table)
+    return _apply_aliasing(_PairPoolGatherShared, (x1, x2, sp1, sp2, i1, i2, idx1 is None, idx2 is None), x1, x2, with_identity)

@@ -1,13 +1,10 @@
-"""Readouts, segment reductions, graph norms, block tails and per-pair fusion pools (src_1gp/layer.py:161-220, 270-283;
-src_1gp/model.py:41).
+"""Readouts, segment reductions, graph norms and block tails (src_1gp/layer.py:161-220; src_1gp/model.py:41); the per-pair fusion
+pools live in ``glam_amd/ops_pair.py``.
 
 Part of ``glam_amd.ops`` (every public name here is re-exported there: ``from glam_amd import ops; ops.pool5(...)``).  Knobs, the weight
 scope, the padded-column bookkeeping and the index staging live in ``glam_amd/ops.py`` and are read through ``_o`` at call time."""
 from __future__ import annotations
 
-import os
-
-import numpy as np
 import torch
 
 from . import _lib
@@ -527,579 +524,3 @@ def nnconv_edge_conditioned(x, edge_attr, gi, w0, b0, w1, b1, root, bias, mean=T
             return _NNConvEC.apply(x, edge_attr, gi, w0, b0, wstack, bias, mean, True)
         return _NNConvEC.apply(x, edge_attr, gi, w0, b0, wstack, bias, mean), x
     return _NNConvEC.apply(x, edge_attr, gi, w0, b0, wstack, bias, mean)
-
-
-class _PairPool(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mol, pro, msp, psp, with_identity=False):
-        require_device(mol, pro)
-        mol_in, pro_in = mol, pro
-        mol, pro = f32c(mol, "mol_out"), f32c(pro, "pro_out")
-        if msp.B != psp.B or mol.size(1) != pro.size(1) or mol.size(0) != msp.N or pro.size(0) != psp.N:
-            raise GlamHipError("pair_pool: the two batches disagree (pair count / width / node count)")
-        P, D = msp.B, mol.size(1)
-        out = torch.empty(P, 2, dtype=torch.float32, device=mol.device)
-        arg = torch.empty(P, 2, dtype=torch.int32, device=mol.device)
-        sums = torch.empty(P, 2, D, dtype=torch.float32, device=mol.device)
-        lib = _lib.api()
-        ws = torch.empty(max(lib.glam_pair_pool_workspace_bytes(P, D), 16), dtype=torch.uint8, device=mol.device)
-        lib.glam_pair_pool_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), P, D, ptr(out), ptr(arg), ptr(sums), ptr(ws), ws.numel(), stream())
-        ctx.save_for_backward(mol, pro, arg, sums)
-        ctx.sps = (msp, psp)
-        ctx.aliased = bool(with_identity)
-        if ctx.aliased:      # the two inputs come back as outputs: what the caller does with them next sends its gradient HERE
-            ctx.set_materialize_grads(False)
-            return out, mol_in.view_as(mol_in), pro_in.view_as(pro_in)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_out, d_ma=None, d_pa=None):
-        mol, pro, arg, sums = ctx.saved_tensors
-        msp, psp = ctx.sps
-        if d_out is None:                    # (only with the aliases: the fusion values themselves were not used)
-            return d_ma, d_pa, None, None, None
-        d_out = f32c(d_out, "d_out")
-        d_mol, d_pro = torch.empty_like(mol), torch.empty_like(pro)
-        lib = _lib.api()
-        if d_ma is not None or d_pa is not None:
-            d_ma = None if d_ma is None else f32c(d_ma, "d_mol (next use)")
-            d_pa = None if d_pa is None else f32c(d_pa, "d_pro (next use)")
-            lib.glam_pair_pool_bwd_add(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(arg), ptr(sums), ptr(d_out), msp.B, mol.size(1),
-                                       ptr(d_ma), ptr(d_pa), ptr(d_mol), ptr(d_pro), stream())
-        else:
-            lib.glam_pair_pool_bwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(arg), ptr(sums), ptr(d_out), msp.B,
-                                   mol.size(1), ptr(d_mol), ptr(d_pro), stream())
-        return d_mol, d_pro, None, None, None
-
-
-def pair_pool(mol_out, pro_out, msp, psp, with_identity=False):
-    """``[max, mean]`` of ``mol[seg_i] @ pro[seg_i].T`` per pair -> ``[P, 2]`` (dot_and_global_pool2).  ``with_identity``: returns
-    ``(out, mol_out, pro_out)`` with the two matrices handed back through this node where that saves the add launches of their second
-    use (the next message step): its gradient is then added inside this node's backward launch."""
-    if with_identity:
-        D = mol_out.size(1)
-        if (torch.is_grad_enabled() and mol_out.requires_grad and pro_out.requires_grad and mol_out.is_cuda
-                and mol_out.dtype == torch.float32 and pro_out.dtype == torch.float32 and mol_out.size(1) == pro_out.size(1)
-                and _lib.api().glam_pair_pool_add_supported(D) == 1):
-            return _PairPool.apply(mol_out, pro_out, msp, psp, True)
-        return _PairPool.apply(mol_out, pro_out, msp, psp), mol_out, pro_out
-    return _PairPool.apply(mol_out, pro_out, msp, psp)
-
-
-class _PairPool5(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mol, pro, msp, psp):
-        require_device(mol, pro)
-        mol, pro = f32c(mol, "mol_out"), f32c(pro, "pro_out")
-        if msp.B != psp.B or mol.size(1) != pro.size(1) or mol.size(0) != msp.N or pro.size(0) != psp.N:
-            raise GlamHipError("pair_pool5: the two batches disagree (pair count / width / node count)")
-        P, D = msp.B, mol.size(1)
-        out = torch.empty(P, 5, dtype=torch.float32, device=mol.device)
-        arg = torch.empty(P, 6, dtype=torch.int32, device=mol.device)
-        _lib.api().glam_pair_pool5_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), P, D, ptr(out), ptr(arg), stream())
-        ctx.save_for_backward(mol, pro, out, arg)
-        ctx.sps = (msp, psp)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_out):
-        mol, pro, out, arg = ctx.saved_tensors
-        msp, psp = ctx.sps
-        d_out = f32c(d_out, "d_out")
-        d_mol, d_pro = torch.empty_like(mol), torch.empty_like(pro)
-        _lib.api().glam_pair_pool5_bwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(out), ptr(arg), ptr(d_out), msp.B,
-                                       mol.size(1), ptr(d_mol), ptr(d_pro), stream())
-        return d_mol, d_pro, None, None
-
-
-def pair_pool5(mol_out, pro_out, msp, psp):
-    """``[max, mean, median, min, std]`` of ``mol[seg_i] @ pro[seg_i].T`` per pair -> ``[P, 5]`` (dot_and_global_pool5);
-    widths that are multiples of 4 up to 128 (``pad_cols`` the operands first: zero columns do not change a score)."""
-    return _PairPool5.apply(mol_out, pro_out, msp, psp)
-
-
-# --------------------------------------------------------------------------------------
-# screening: the fusion against proteins that are held once (csrc/pairpool.hip, glam_pair_pool_indexed_fwd)
-# --------------------------------------------------------------------------------------
-class PairIndex:
-    """A validated pair -> protein index: ``host`` int32 ``[P]`` (numpy) with every entry in ``[0, Q)``.  ``on(device)`` is its device
-    copy, made once per device (out of pinned memory, only enqueued) and shared by every launch that reads it."""
-
-    def __init__(self, host, Q):
-        self.host, self.P, self.Q = host, int(host.shape[0]), int(Q)
-        self._dev = {}
-        self._by_protein = None
-
-    def on(self, device):
-        device = torch.device(device)
-        t = self._dev.get(device)
-        if t is None:
-            t = self._dev[device] = _stage_int32(self.host, device, "the pair -> protein index")
-        return t
-
-    def by_protein(self):
-        """The pairs grouped by protein, for the sums of the training call (``ops.pair_pool_shared`` / ``ops.pair_rows``): ``order`` int32
-        ``[P]`` — the stable argsort of the index (the pairs of a protein keep their batch order) — and ``ptr`` int32 ``[Q + 1]``, the
-        offsets of the proteins' runs in it.  Built once, on the host; ``.on(device)`` -> their device copies, made once per device."""
-        if self._by_protein is None:
-            self._by_protein = PairsByProtein(self.host, self.Q)
-        return self._by_protein
-
-
-def _stage_int32(host, device, what):
-    """Device copy of a host int32 vector out of pinned memory (only enqueued).  Not inside a hipGraph capture: the copy would be baked
-    into the graph and the pinned buffer allocated under it — the eager first visit of a batch makes the copies a capture then finds."""
-    if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-        raise GlamHipError(f"{what} has no copy on {device} yet and a hipGraph capture cannot make one: keep ONE PairIndex across the "
-                           "steps (ops.pair_index) and run the first step on it eagerly, as GraphedTrainStep does")
-    n = int(host.shape[0])
-    staged = torch.empty(max(n, 1), dtype=torch.int32, pin_memory=True)
-    staged.numpy()[:n] = host
-    return staged.to(device, non_blocking=True)[:n]
-
-
-class PairsByProtein:
-    """``order`` / ``ptr`` of ``PairIndex.by_protein`` (host, int32 numpy) and their device copies."""
-
-    def __init__(self, host, Q):
-        P, Q = int(host.shape[0]), int(Q)
-        if P and (int(host.min()) < 0 or int(host.max()) >= Q):
-            raise IndexError(f"the pair -> protein index must lie in [0, {Q})")
-        self.order = np.argsort(host, kind="stable").astype(np.int32)
-        self.ptr = np.zeros(Q + 1, dtype=np.int32)
-        np.cumsum(np.bincount(host, minlength=Q)[:Q], out=self.ptr[1:])
-        if int(self.ptr[-1]) != P:
-            raise IndexError("the pair -> protein index does not sort into its proteins' runs")
-        self.P, self.Q = P, Q
-        self._dev = {}
-
-    def on(self, device):
-        device = torch.device(device)
-        t = self._dev.get(device)
-        if t is None:
-            both = _stage_int32(np.concatenate([self.order, self.ptr]), device, "the pair list by protein")      # (one copy)
-            t = self._dev[device] = (both[:self.P], both[self.P:])
-        return t
-
-
-def pair_index(pro_of_pair, P, Q, default="identity", name="pro_of_pair", over="proteins"):
-    """``PairIndex`` of ``pro_of_pair`` for ``P`` pairs over ``Q`` proteins — host only, before anything is launched (the kernel trusts
-    the index; the policy of ``data.resident_table``).  A host sequence, numpy array or CPU tensor of integers of length ``P``;
-    ``IndexError`` for a wrong length or an entry outside ``[0, Q)``; a device tensor is refused (validating it would be a hidden
-    read-back).  ``None``: ``default="identity"`` pairs ligand i with protein i (needs ``Q == P``), ``default="single"`` pairs every
-    ligand with the one protein (needs ``Q == 1``).  ``name`` / ``over``: what the messages call the index and the things it points
-    into (``ops.pair_pool_gather`` validates ``idx1`` / ``idx2`` over drugs with the same rules)."""
-    P, Q = int(P), int(Q)
-    if isinstance(pro_of_pair, PairIndex):
-        if pro_of_pair.P != P or pro_of_pair.Q != Q:
-            raise IndexError(f"{name} was validated for {pro_of_pair.P} pairs over {pro_of_pair.Q} {over}, not {P} over {Q}")
-        return pro_of_pair
-    if pro_of_pair is None:
-        if default == "identity":
-            if Q != P:
-                if name != "pro_of_pair":
-                    raise IndexError(f"{name}=None takes segment i for pair i: {P} pairs but {Q} {over}")
-                raise IndexError(f"pro_of_pair=None pairs ligand i with protein i: {P} ligands but {Q} proteins")
-            return PairIndex(np.arange(P, dtype=np.int32), Q)
-        if Q != 1:
-            raise IndexError(f"pro_of_pair=None screens against the one encoded protein, but the encoding holds {Q}: pass the index")
-        return PairIndex(np.zeros(P, dtype=np.int32), Q)
-    if torch.is_tensor(pro_of_pair):
-        if pro_of_pair.device.type != "cpu":
-            raise GlamHipError(f"{name} lives on a device: it is validated on the host before the launch, which would be a hidden "
-                               "read-back — pass the host sequence / numpy array / CPU tensor it was made from")
-        pro_of_pair = pro_of_pair.detach().numpy()
-    idx = np.asarray(pro_of_pair)
-    if idx.size == 0:
-        idx = np.zeros(0, dtype=np.int64)
-    if idx.dtype.kind not in "iu":
-        raise IndexError(f"{name} must hold integers, got {idx.dtype}")
-    if idx.ndim != 1 or idx.shape[0] != P:
-        raise IndexError(f"{name} must have one entry per pair: shape {tuple(idx.shape)} for {P} pairs")
-    if P and (int(idx.min()) < 0 or int(idx.max()) >= Q):
-        raise IndexError(f"{name} must lie in [0, {Q}): got {int(idx.min())} .. {int(idx.max())}")
-    return PairIndex(idx.astype(np.int32), Q)
-
-
-def pair_pool_indexed(mol_out, pro_out, msp, psp, pro_of_pair=None, return_argmax=False):
-    """``[max, mean]`` of ``mol[seg_i] @ pro[seg_q].T`` with ``q = pro_of_pair[i]`` -> ``[P, 2]``: ``pair_pool`` against proteins that are
-    held once (``psp.B`` segments) instead of once per pair.  The max column — and with ``return_argmax`` the ``[P, 2]`` int32 rows of
-    the maximum in ``mol_out`` / ``pro_out`` (-1 for an empty pair) — is bit for bit that of ``pair_pool`` on replicated residue rows.
-    ``pro_of_pair``: see ``pair_index`` (``None`` = identity).  Inference only: there is no backward (training is ``ops.pair_pool``)."""
-    P, Q = msp.B, psp.B
-    index = pair_index(pro_of_pair, P, Q)
-    if torch.is_grad_enabled() and (mol_out.requires_grad or pro_out.requires_grad):
-        raise GlamHipError("pair_pool_indexed is inference only (no backward): call it under torch.no_grad(); the training route is "
-                           "ops.pair_pool on one protein graph per pair")
-    require_device(mol_out, pro_out)
-    mol, pro = f32c(mol_out, "mol_out"), f32c(pro_out, "pro_out")
-    if mol.size(1) != pro.size(1) or mol.size(0) != msp.N or pro.size(0) != psp.N:
-        raise GlamHipError("pair_pool_indexed: the two batches disagree (width / node count)")
-    D = mol.size(1)
-    out = torch.empty(P, 2, dtype=torch.float32, device=mol.device)
-    arg = torch.empty(P, 2, dtype=torch.int32, device=mol.device) if return_argmax else None
-    lib = _lib.api()
-    ws = torch.empty(max(lib.glam_pair_pool_workspace_bytes(P, D), 16), dtype=torch.uint8, device=mol.device)
-    lib.glam_pair_pool_indexed_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(index.on(mol.device)), P, Q, D, ptr(out), ptr(arg),
-                                   ptr(ws), ws.numel(), stream())
-    return (out, arg) if return_argmax else out
-
-
-# --------------------------------------------------------------------------------------
-# panel screening: every ligand against every selected protein, protein-stationary (csrc/pairpanel.hip, glam_pair_pool_panel_fwd)
-# --------------------------------------------------------------------------------------
-PANEL_CHUNK = 64      # residue rows per chunk (one per lane of the wave that holds them) = kPanelChunk of csrc/pairpanel.hip
-
-
-class PanelPlan:
-    """The work of one panel call over a validated selection: ``sel`` int32 ``[Qs]`` (every entry in ``[0, Q)``) and ``work`` int32
-    ``[4 * total_chunks + Qs + 1]`` — per chunk of 64 residue rows, in selection order, ``(j, first row of the chunk in the encoding,
-    rows in the chunk, index of its partials in the workspace)``, then ``chunk_ptr[Qs + 1]``, the offsets of the selections' chunk
-    runs (``chunks`` / ``chunk_ptr`` are views of it).  Host numpy; ``on(device)`` -> ``(sel, work)`` on the device, made once per
-    device (one copy out of pinned memory, only enqueued) and shared by every launch that reads them."""
-
-    def __init__(self, sel, sizes):
-        self.sel, self.Qs, self.Q = sel, int(sel.shape[0]), int(sizes.shape[0])
-        first = np.zeros(self.Q + 1, dtype=np.int64)
-        np.cumsum(sizes, out=first[1:])
-        if int(first[-1]) >= 2 ** 31 - 1:
-            raise IndexError("panel_plan: the proteins hold 2^31 residue rows or more")
-        self.N = int(first[-1])
-        n_chunks = (sizes[sel] + PANEL_CHUNK - 1) // PANEL_CHUNK                     # per selection
-        chunk_ptr = np.zeros(self.Qs + 1, dtype=np.int64)
-        np.cumsum(n_chunks, out=chunk_ptr[1:])
-        self.total_chunks = T = int(chunk_ptr[-1])
-        if T >= 2 ** 31 - 1:
-            raise IndexError("panel_plan: the selection has 2^31 chunks or more")
-        j = np.repeat(np.arange(self.Qs, dtype=np.int64), n_chunks)
-        c = np.arange(T, dtype=np.int64) - chunk_ptr[j]                              # chunk inside its protein
-        table = np.empty((T, 4), dtype=np.int32)
-        table[:, 0] = j
-        table[:, 1] = first[sel[j]] + PANEL_CHUNK * c
-        table[:, 2] = np.minimum(sizes[sel[j]] - PANEL_CHUNK * c, PANEL_CHUNK)
-        table[:, 3] = np.arange(T)
-        self.work = np.concatenate([table.reshape(-1), chunk_ptr.astype(np.int32)])
-        self.chunks, self.chunk_ptr = self.work[:4 * T].reshape(T, 4), self.work[4 * T:]
-        self._dev = {}
-
-    def on(self, device):
-        device = torch.device(device)
-        t = self._dev.get(device)
-        if t is None:
-            both = _stage_int32(np.concatenate([self.sel, self.work]), device, "the panel's selection and work table")      # (one copy)
-            t = self._dev[device] = (both[:self.Qs], both[self.Qs:])
-        return t
-
-
-def panel_plan(sizes_host, proteins=None):
-    """``PanelPlan`` of the selection ``proteins`` over ``Q = len(sizes_host)`` proteins of ``sizes_host[q]`` residue rows — host only
-    (numpy), before anything is launched (the kernel trusts the table; the policy of ``pair_index``).  ``proteins``: ``None`` = all
-    ``Q`` in order, or a host sequence / numpy array / CPU tensor of integers in ``[0, Q)``, in any order, duplicates allowed;
-    ``IndexError`` for a wrong dtype or an entry outside ``[0, Q)``; a device tensor is refused (validating it would be a hidden
-    read-back)."""
-    if torch.is_tensor(sizes_host):
-        if sizes_host.device.type != "cpu":
-            raise GlamHipError("panel_plan: the proteins' sizes live on a device: the plan is built on the host — pass their host copy")
-        sizes_host = sizes_host.detach().numpy()
-    sizes = np.asarray(sizes_host)
-    if sizes.size == 0:
-        sizes = np.zeros(0, dtype=np.int64)
-    if sizes.dtype.kind not in "iu" or sizes.ndim != 1 or (sizes.size and int(sizes.min()) < 0):
-        raise IndexError("panel_plan: the proteins' sizes must be a vector of non-negative integers")
-    sizes = sizes.astype(np.int64)
-    Q = int(sizes.shape[0])
-    if proteins is None:
-        return PanelPlan(np.arange(Q, dtype=np.int32), sizes)
-    if torch.is_tensor(proteins):
-        if proteins.device.type != "cpu":
-            raise GlamHipError("proteins lives on a device: it is validated on the host before the launch, which would be a hidden "
-                               "read-back — pass the host sequence / numpy array / CPU tensor it was made from")
-        proteins = proteins.detach().numpy()
-    sel = np.asarray(proteins)
-    if sel.size == 0:
-        sel = np.zeros(0, dtype=np.int64)
-    if sel.dtype.kind not in "iu":
-        raise IndexError(f"proteins must hold integers, got {sel.dtype}")
-    if sel.ndim != 1:
-        raise IndexError(f"proteins must be a vector of protein numbers: shape {tuple(sel.shape)}")
-    if sel.size and (int(sel.min()) < 0 or int(sel.max()) >= Q):
-        raise IndexError(f"proteins must lie in [0, {Q}): got {int(sel.min())} .. {int(sel.max())}")
-    return PanelPlan(sel.astype(np.int32), sizes)
-
-
-def pair_pool_panel(mol_out, pro_out, msp, psp, plan, molsum=None, prosum=None, return_argmax=False, slab=0):
-    """``[max, mean]`` of ``mol[seg_l] @ pro[seg_q].T`` for EVERY ligand ``l`` and every selected protein ``q = plan.sel[j]`` ->
-    ``[L, Qs, 2]``: the panel of ``Qs`` calls of ``pair_pool_indexed`` with ``pro_of_pair = [sel[j]] * L`` from one protein-stationary
-    launch (+ a finish launch).  The max column — and with ``return_argmax`` the ``[L, Qs, 2]`` int32 rows of the maximum in ``mol_out``
-    / ``pro_out`` (-1 for an empty ligand or protein) — is bit for bit that of those calls; the mean is ``<molsum[l], prosum[q]> /
-    (n_l n_q)`` and within the fp64-twin bound.  ``plan``: ``panel_plan`` over the sizes of ``psp``'s segments.  ``molsum`` ``[L, D]``
-    / ``prosum`` ``[Q, D]``: the segments' column sums (``segment_pool(x, sp, "sum")``), computed here when missing — a caller that
-    keeps the proteins keeps ``prosum`` too.  ``slab``: ligands per wave, 0 = the library chooses.  Widths 1..128.  Inference only:
-    there is no backward (training is ``ops.pair_pool`` / ``ops.pair_pool_shared``)."""
-    if not isinstance(plan, PanelPlan):
-        raise GlamHipError("pair_pool_panel: plan must come from ops.panel_plan (the kernel trusts its table)")
-    L, Q, Qs = msp.B, psp.B, plan.Qs
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (mol_out, pro_out, molsum, prosum)):
-        raise GlamHipError("pair_pool_panel is inference only (no backward): call it under torch.no_grad(); the training routes are "
-                           "ops.pair_pool on one protein graph per pair and ops.pair_pool_shared on proteins held once")
-    if plan.Q != Q or plan.N != psp.N:
-        raise GlamHipError(f"pair_pool_panel: the plan was made for {plan.Q} proteins of {plan.N} residue rows, the encoding holds {Q} of {psp.N}")
-    require_device(mol_out, pro_out)
-    if (mol_out.dim() != 2 or pro_out.dim() != 2 or mol_out.size(1) != pro_out.size(1) or mol_out.size(0) != msp.N
-            or pro_out.size(0) != psp.N):
-        raise GlamHipError(f"pair_pool_panel: the two sides disagree (width / node count): mol {tuple(mol_out.shape)} for {msp.N} rows, "
-                           f"pro {tuple(pro_out.shape)} for {psp.N} rows")
-    D = mol_out.size(1)
-    for name, t, rows in (("molsum", molsum, L), ("prosum", prosum, Q)):
-        if t is not None and (t.dim() != 2 or tuple(t.shape) != (rows, D) or t.device != mol_out.device):
-            raise GlamHipError(f"pair_pool_panel: {name} must be the [{rows}, {D}] column sums on {mol_out.device}, got {tuple(t.shape)} on {t.device}")
-    if int(slab) < 0:
-        raise GlamHipError(f"pair_pool_panel: slab must be 0 (choose) or the ligands per wave, got {slab}")
-    lib = _lib.api()
-    if _lib.load().glam_pair_pool_panel_supported(D) != 0:          # (a status: the raw binding hands it back)
-        raise GlamHipError(f"pair_pool_panel: width {D} is outside the kernel table (1..128)")
-    mol, pro = f32c(mol_out, "mol_out"), f32c(pro_out, "pro_out")
-    dev = mol.device
-    out = torch.empty(L, Qs, 2, dtype=torch.float32, device=dev)
-    arg = torch.empty(L, Qs, 2, dtype=torch.int32, device=dev) if return_argmax else None
-    if L == 0 or Qs == 0:
-        return (out, arg) if return_argmax else out
-    if msp.N == 0 or psp.N == 0:          # no row on one side: every pair is empty (and the empty matrix has no address to pass)
-        out.zero_()
-        if return_argmax:
-            arg.fill_(-1)
-        return (out, arg) if return_argmax else out
-    molsum =f32c(molsum, "molsum") if molsum is not None else segment_pool(mol, msp, "sum")
-    prosum = f32c(prosum, "prosum") if prosum is not None else segment_pool(pro, psp, "sum")
-    sel, work = plan.on(dev)
-    ws = torch.empty(max(lib.glam_pair_pool_panel_workspace_bytes(plan.total_chunks, L), 16), dtype=torch.uint8, device=dev)
-    lib.glam_pair_pool_panel_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(work), plan.total_chunks, ptr(sel), Qs, L, Q, D,
-                                 ptr(molsum), ptr(prosum), int(slab), ptr(out), ptr(arg), ptr(ws), ws.numel(), stream())
-    return (out, arg) if return_argmax else out
-
-
-# --------------------------------------------------------------------------------------
-# training against proteins held once: the indexed fusion with a backward (csrc/pairshared.hip)
-# --------------------------------------------------------------------------------------
-class _PairPoolShared(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mol, pro, msp, psp, index, with_identity=False):
-        mol_in, pro_in = mol, pro
-        mol, pro = f32c(mol, "mol_out"), f32c(pro, "pro_out")
-        P, Q, D, dev = msp.B, psp.B, mol.size(1), mol.device
-        pidx = index.on(dev)
-        order, qptr = index.by_protein().on(dev)
-        out = torch.empty(P, 2, dtype=torch.float32, device=dev)
-        arg = torch.empty(P, 2, dtype=torch.int32, device=dev)
-        sums = torch.empty(P, 2, D, dtype=torch.float32, device=dev)
-        lib = _lib.api()
-        ws = torch.empty(max(lib.glam_pair_pool_workspace_bytes(P, D), 16), dtype=torch.uint8, device=dev)
-        lib.glam_pair_pool_shared_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(pidx), P, Q, D, ptr(out), ptr(arg), ptr(sums),
-                                      ptr(ws), ws.numel(), stream())
-        ctx.save_for_backward(mol, pro, arg, sums, pidx, order, qptr)
-        ctx.sps = (msp, psp)
-        ctx.aliased = bool(with_identity)
-        if ctx.aliased:      # (as _PairPool: what the caller does with the two matrices next sends its gradient HERE)
-            ctx.set_materialize_grads(False)
-            return out, mol_in.view_as(mol_in), pro_in.view_as(pro_in)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_out, d_ma=None, d_pa=None):
-        mol, pro, arg, sums, pidx, order, qptr = ctx.saved_tensors
-        msp, psp = ctx.sps
-        if d_out is None:
-            return d_ma, d_pa, None, None, None, None
-        d_out = f32c(d_out, "d_out")
-        d_ma = None if d_ma is None else f32c(d_ma, "d_mol (next use)")
-        d_pa = None if d_pa is None else f32c(d_pa, "d_pro (next use)")
-        if msp.B == 0:       # no pair: the entry point writes nothing
-            d_mol = torch.zeros_like(mol) if d_ma is None else d_ma
-            d_pro = torch.zeros_like(pro) if d_pa is None else d_pa
-            return d_mol, d_pro, None, None, None, None
-        d_mol, d_pro = torch.empty_like(mol), torch.empty_like(pro)
-        _lib.api().glam_pair_pool_shared_bwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(pidx), ptr(order), ptr(qptr), ptr(arg),
-                                             ptr(sums), ptr(d_out), msp.B, psp.B, mol.size(1), ptr(d_ma), ptr(d_pa), ptr(d_mol),
-                                             ptr(d_pro), stream())
-        return d_mol, d_pro, None, None, None, None
-
-
-def pair_pool_shared(mol_out, pro_out, msp, psp, pro_of_pair=None, with_identity=False):
-    """``pair_pool_indexed`` WITH a backward: ``[max, mean]`` of ``mol[seg_i] @ pro[seg_q].T`` with ``q = pro_of_pair[i]`` -> ``[P, 2]``
-    against proteins held once (``psp.B`` segments), for training.  The forward is bit for bit ``pair_pool_indexed``; the gradient of a
-    protein's residue rows is the sum over every pair that points at it, taken in batch order without atomics (two runs are
-    bit-equal); a protein no pair references gets zeros.  ``pro_of_pair``: see ``pair_index`` (``None`` = identity; every ligand against
-    the one protein when ``psp.B == 1``).  ``with_identity``:
-    as ``pair_pool`` — ``(out, mol_out, pro_out)`` with the two matrices handed back through the node where its backward launch can
-    add their later gradients itself (``glam_pair_pool_add_supported``), the plain triple otherwise."""
-    P, Q = msp.B, psp.B
-    index = pair_index(pro_of_pair, P, Q, default="single" if Q == 1 and P != 1 else "identity")
-    require_device(mol_out, pro_out)
-    if (mol_out.dim() != 2 or pro_out.dim() != 2 or mol_out.size(1) != pro_out.size(1) or mol_out.size(0) != msp.N
-            or pro_out.size(0) != psp.N):
-        raise GlamHipError("pair_pool_shared: the two batches disagree (width / node count)")
-    if with_identity:
-        D = mol_out.size(1)
-        if (torch.is_grad_enabled() and mol_out.requires_grad and pro_out.requires_grad and mol_out.dtype == torch.float32
-                and pro_out.dtype == torch.float32 and _lib.api().glam_pair_pool_add_supported(D) == 1):
-            return _PairPoolShared.apply(mol_out, pro_out, msp, psp, index, True)
-        return _PairPoolShared.apply(mol_out, pro_out, msp, psp, index), mol_out, pro_out
-    return _PairPoolShared.apply(mol_out, pro_out, msp, psp, index)
-
-
-class _PairRows(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, flat, index):
-        pidx = index.on(flat.device)
-        order, qptr = index.by_protein().on(flat.device)
-        ctx.save_for_backward(order, qptr)
-        ctx.dims = (index.P, index.Q, tuple(flat.shape[1:]))
-        return flat.index_select(0, pidx)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_rows):
-        order, qptr = ctx.saved_tensors
-        P, Q, tail = ctx.dims
-        d_rows = f32c(d_rows, "d_rows")
-        W = int(np.prod(tail, dtype=np.int64))
-        if P == 0 or W == 0:
-            return torch.zeros((Q,) + tail, dtype=torch.float32, device=d_rows.device), None
-        d_flat = torch.empty((Q,) + tail, dtype=torch.float32, device=d_rows.device)
-        _lib.api().glam_pair_rows_bwd(ptr(d_rows), ptr(order), ptr(qptr), P, Q, W, ptr(d_flat), stream())
-        return d_flat, None
-
-
-def pair_rows(flat, index):
-    """``flat[index]`` -> ``[P, ...]``: the rows of a matrix that holds every protein once, one per pair (``index``: a ``PairIndex`` or
-    what ``pair_index`` accepts, over ``flat.size(0)`` rows).  Its backward sums the pairs' rows per protein in batch order
-    (``glam_pair_rows_bwd``): ``index_select``'s own backward is an atomic ``index_add``, whose bits change from run to run."""
-    if not isinstance(index, PairIndex):
-        index = pair_index(index, len(index), flat.size(0))
-    elif index.Q != flat.size(0):
-        raise IndexError(f"pair_rows: the index was validated over {index.Q} rows, the matrix has {flat.size(0)}")
-    require_device(flat)
-    if flat.dtype != torch.float32:
-        raise GlamHipError(f"pair_rows: expected float32, got {flat.dtype}")
-    return _PairRows.apply(flat, index)
-
-
-# --------------------------------------------------------------------------------------
-# drug x drug: the fusion with BOTH sides held once and both indexed (csrc/pairgather.hip, glam_pair_pool_gather_fwd)
-# --------------------------------------------------------------------------------------
-def pair_pool_gather(x1, x2, sp1, sp2, idx1=None, idx2=None, return_argmax=False):
-    """``[max, mean]`` of ``x1[seg_a] @ x2[seg_b].T`` with ``a = idx1[i]``, ``b = idx2[i]`` -> ``[P, 2]``: ``pair_pool`` on two sets of
-    small segments that are each held once (``sp1.B`` / ``sp2.B`` of them) — one wave per pair, one launch.  The max column — and with
-    ``return_argmax`` the ``[P, 2]`` int32 rows of the maximum in ``x1`` / ``x2`` (-1 for an empty pair) — is bit for bit that of
-    ``pair_pool`` on physically gathered rows; the mean is the same bits on every run and within the fp64-twin bound.
-    ``idx1`` / ``idx2``: see ``pair_index``; ``None`` = identity on that side (needs ``sp.B == P``); ``P`` is the length of whichever is
-    given.  Widths 1..128.  Inference only: there is no backward (training is ``ops.pair_pool`` on one graph per pair and side)."""
-    Q1, Q2 = sp1.B, sp2.B
-    given = idx1 if idx1 is not None else idx2
-    P = Q1 if given is None else given.P if isinstance(given, PairIndex) else len(given)
-    i1 = None if idx1 is None and Q1 == P else pair_index(idx1, P, Q1, name="idx1", over="segments of x1")
-    i2 = None if idx2 is None and Q2 == P else pair_index(idx2, P, Q2, name="idx2", over="segments of x2")
-    if torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
-        raise GlamHipError("pair_pool_gather is inference only (no backward): call it under torch.no_grad(); the training route is "
-                           "ops.pair_pool on one graph per pair and side")
-    require_device(x1, x2)
-    if x1.dim() != 2 or x2.dim() != 2 or x1.size(1) != x2.size(1) or x1.size(0) != sp1.N or x2.size(0) != sp2.N:
-        raise GlamHipError(f"pair_pool_gather: the two sides disagree (width / node count): x1 {tuple(x1.shape)} for {sp1.N} rows, "
-                           f"x2 {tuple(x2.shape)} for {sp2.N} rows")
-    x1, x2 = f32c(x1, "x1"), f32c(x2, "x2")
-    D = x1.size(1)
-    lib = _lib.api()
-    if lib.glam_pair_pool_gather_load_bytes(ptr(x1), ptr(x2), D) == 0:
-        raise GlamHipError(f"pair_pool_gather: width {D} is outside the kernel table (1..128)")
-    out = torch.empty(P, 2, dtype=torch.float32, device=x1.device)
-    arg = torch.empty(P, 2, dtype=torch.int32, device=x1.device) if return_argmax else None
-    lib.glam_pair_pool_gather_fwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if i1 is None else i1.on(x1.device)),
-                                  ptr(None if i2 is None else i2.on(x1.device)), P, Q1, Q2, D, ptr(out), ptr(arg), stream())
-    return (out, arg) if return_argmax else out
-
-
-# --------------------------------------------------------------------------------------
-# training on drugs held once: the gathered fusion with a backward (csrc/pairgather.hip train_fwd, csrc/pairgather_bwd.hip)
-# --------------------------------------------------------------------------------------
-class _PairPoolGatherShared(torch.autograd.Function):
-    """``i1`` / ``i2``: the validated ``PairIndex`` of each side (an identity side too: its by-drug lists are read by the backward);
-    ``null1`` / ``null2``: hand the kernels a NULL index on that side (identity)."""
-
-    @staticmethod
-    def forward(ctx, x1, x2, sp1, sp2, i1, i2, null1, null2, with_identity=False):
-        x1_in, x2_in = x1, x2
-        x1, x2 = f32c(x1, "x1"), f32c(x2, "x2")
-        P, Q1, Q2, D, dev = i1.P, sp1.B, sp2.B, x1.size(1), x1.device
-        d1, d2 = i1.on(dev), i2.on(dev)
-        order1, lptr1 = i1.by_protein().on(dev)
-        order2, lptr2 = i2.by_protein().on(dev)
-        out = torch.empty(P, 2, dtype=torch.float32, device=dev)
-        arg = torch.empty(P, 2, dtype=torch.int32, device=dev)
-        sums = torch.empty(P, 2, D, dtype=torch.float32, device=dev)
-        ctx.rows = x1.size(0) > 0 and x2.size(0) > 0
-        if ctx.rows:
-            _lib.api().glam_pair_pool_gather_train_fwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if null1 else d1),
-                                                       ptr(None if null2 else d2), P, Q1, Q2, D, ptr(out), ptr(arg), ptr(sums), stream())
-        else:                # no row on one side: every pair is empty (and the empty matrix has no address to pass)
-            out.zero_()
-            arg.fill_(-1)
-        ctx.save_for_backward(x1, x2, arg, sums, d1, d2, order1, lptr1, order2, lptr2)
-        ctx.sps, ctx.null, ctx.P = (sp1, sp2), (bool(null1), bool(null2)), P
-        ctx.aliased = bool(with_identity)
-        if ctx.aliased:      # (as _PairPool: what the caller does with the two matrices next sends its gradient HERE)
-            ctx.set_materialize_grads(False)
-            return out, x1_in.view_as(x1_in), x2_in.view_as(x2_in)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, d_out, d_a1=None, d_a2=None):
-        x1, x2, arg, sums, d1, d2, order1, lptr1, order2, lptr2 = ctx.saved_tensors
-        sp1, sp2 = ctx.sps
-        none = (None,) * 7
-        if d_out is None:
-            return (d_a1, d_a2) + none
-        d_out = f32c(d_out, "d_out")
-        d_a1 = None if d_a1 is None else f32c(d_a1, "d_x1 (next use)")
-        d_a2 = None if d_a2 is None else f32c(d_a2, "d_x2 (next use)")
-        if ctx.P == 0 or not ctx.rows:       # no pair, or only empty ones: the entry point writes nothing
-            return (torch.zeros_like(x1) if d_a1 is None else d_a1, torch.zeros_like(x2) if d_a2 is None else d_a2) + none
-        d_x1, d_x2 = torch.empty_like(x1), torch.empty_like(x2)
-        _lib.api().glam_pair_pool_gather_bwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if ctx.null[0] else d1),
-                                             ptr(None if ctx.null[1] else d2), ptr(order1), ptr(lptr1), ptr(order2), ptr(lptr2), ptr(arg),
-                                             ptr(sums), ptr(d_out), ctx.P, sp1.B, sp2.B, x1.size(1), ptr(d_a1), ptr(d_a2), ptr(d_x1),
-                                             ptr(d_x2), stream())
-        return (d_x1, d_x2) + none
-
-
-def pair_pool_gather_shared(x1, x2, sp1, sp2, idx1=None, idx2=None, with_identity=False):
-    """``pair_pool_gather`` WITH a backward: ``[max, mean]`` of ``x1[seg_a] @ x2[seg_b].T`` with ``a = idx1[i]``, ``b = idx2[i]`` ->
-    ``[P, 2]`` on two sets of small segments that are each held once, for training.  The forward is bit for bit ``pair_pool_gather``; the
-    gradient of a segment's rows — on EITHER side — is the sum over every pair that points at it, taken in batch order without atomics
-    (two runs are bit-equal, one launch for both sides); a segment no pair references gets zeros.  ``idx1`` / ``idx2``: as
-    ``pair_pool_gather`` (``pair_index``; ``None`` = identity on that side, needs ``sp.B == P``); keep ONE ``PairIndex`` per side across
-    the steps that use it — its device copies are made on the first, eager, visit and a hipGraph capture needs them to exist.  Widths
-    1..128.  ``with_identity``: as ``pair_pool`` — ``(out, x1, x2)`` with the two matrices handed back through the node (both require
-    grad, fp32): its backward launch then adds their later gradients itself; the plain triple otherwise."""
-    Q1, Q2 = sp1.B, sp2.B
-    given = idx1 if idx1 is not None else idx2
-    P = Q1 if given is None else given.P if isinstance(given, PairIndex) else len(given)
-    i1 = pair_index(idx1, P, Q1, name="idx1", over="segments of x1")
-    i2 = pair_index(idx2, P, Q2, name="idx2", over="segments of x2")
-    require_device(x1, x2)
-    if x1.dim() != 2 or x2.dim() != 2 or x1.size(1) != x2.size(1) or x1.size(0) != sp1.N or x2.size(0) != sp2.N:
-        raise GlamHipError(f"pair_pool_gather_shared: the two sides disagree (width / node count): x1 {tuple(x1.shape)} for {sp1.N} rows, "
-                           f"x2 {tuple(x2.shape)} for {sp2.N} rows")
-    D = x1.size(1)
-    if not 1 <= D <= 128:
-        raise GlamHipError(f"pair_pool_gather_shared: width {D} is outside the kernel table (1..128)")
-    args = (x1, x2, sp1, sp2, i1, i2, idx1 is None, idx2 is None)
-    if with_identity:
-        # (the add runs inside the backward launch for every width of the table: 1 <= D <= 128, checked above)
-        if (torch.is_grad_enabled() and x1.requires_grad and x2.requires_grad and x1.dtype == torch.float32 and x2.dtype == torch.float32):
-            return _PairPoolGatherShared.apply(*args, True)
-        return _PairPoolGatherShared.apply(*args), x1, x2
-    return _PairPoolGatherShared.apply(*args)

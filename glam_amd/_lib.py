@@ -74,6 +74,10 @@ SIGNATURES = {
     "glam_pair_pool_panel_workspace_bytes": (_sz, [_i64, _i64]),
     "glam_pair_pool_panel_supported": (_i32, [_i32]),
     "glam_pair_pool_panel_fwd": (_i32, [_vp] * 5 + [_i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "glam_hits_supported": (_i32, [_i32]),
+    "glam_hits_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "glam_hits_reset": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "glam_hits_merge": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "glam_gru_tail_rng_fwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "glam_gru_tail_rng_bwd": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _f32, _f32, _f32, _f32] + [_vp] * 6),
     "glam_bias_res_act_rng_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),

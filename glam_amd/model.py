@@ -12,7 +12,7 @@ import weakref
 
 import torch
 
-from . import graphs, ops
+from . import graphs, hits, ops
 from ._lib import GlamHipError
 
 from .layer import _None  # noqa: F401
@@ -394,6 +394,31 @@ class ArchitectureDTI(torch.nn.Module):
                                                                  + [f[:, j].contiguous() for f in fusion]))) for j in range(Qs)]
                 out = torch.stack(cols, 1)
         return (out, contacts) if return_argmax else out
+
+    def screen_top(self, batches, enc, proteins=None, k=100, task=0, largest=True):
+        """The best ``k`` ligands per selected protein of a whole library -> ``hits.HitList`` with one query per entry of the selection
+        (duplicates allowed, as in ``ops.panel_plan``).  ``batches``: an iterable of ``data_mol`` or ``(data_mol, ids)``; every item goes
+        through ``screen_panel(data_mol, enc, proteins)`` — all of its guards and refusals apply, with its own messages — and column
+        ``task`` of its output is merged into the lists by stride (``HitList.update``: two launches, no copy).  ``ids``: the ligands' ids,
+        host integers or an int32 device tensor; without them a ligand's id is its position in the stream.  Ids are not deduplicated.
+        Memory is ``Qs x k`` however long the stream: no score tensor outlives its batch, and the loop adds no read-back to those of
+        ``screen_panel`` (one per encoding).  ``k`` in 1..1024; ``largest``: whether a larger score is better."""
+        k = hits.check_k(k, "screen_top")
+        out_dim = self.lin_out1.linear.out_features
+        if isinstance(task, bool) or not isinstance(task, int) or not 0 <= task < out_dim:
+            raise GlamHipError(f"screen_top: task = {task!r} is not one of the model's {out_dim} task column(s)")
+        top = None
+        for item in batches:
+            data_mol, ids = item if isinstance(item, tuple) else (item, None)
+            out = self.screen_panel(data_mol, enc, proteins)
+            if top is None:
+                top = hits.HitList(out.size(1), k, out.device, largest)
+            top.update(out, ids, task)
+        if top is None:          # an empty stream: empty lists, after the checks a first batch would have met
+            self._screen_guard("screen_panel")
+            _check_encoding(self, "screen_panel", enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
+            top = hits.HitList(ops.panel_plan([0] * enc.num_graphs, proteins).Qs, k, enc.flat.device, largest)     # (host only: no read-back)
+        return top
 
     # ---- training on shared proteins: the protein tower runs once per DISTINCT protein of the step ----------------------------
     def _shared_index(self, pro_of_pair, P, Q, device):

@@ -665,6 +665,28 @@ int glam_pair_pool_panel_fwd(const float* mol, const float* pro, const int32_t* 
                              const float* prosum, int slab, float* out, int32_t* argmax, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* Screening hit lists: the best K candidates per query column, kept on the device while batches of scores stream past
+ * (csrc/hits.hip).  State, owned by the caller: top_score f32[Qs,K] and top_id int32[Qs,K] — every list sorted best first, empty
+ * slots (id -1, score NaN) at its end — and seen int64[1] in device memory, the number of candidates offered so far.
+ * glam_hits_reset empties the lists and zeroes *seen.  glam_hits_merge offers candidate l = 0..L-1 with the score
+ * score[l * ld_row + j * ld_col] (strides in elements, >= 0: one task column of an [L,Qs,out_dim] tensor is read in place) to list j,
+ * j = 0..Qs-1, under the id ids[l] (int32[L], every id in [0, 2^31 - 1]; not deduplicated), or *seen + l when ids is NULL (the caller
+ * keeps that below 2^31), and then adds L to *seen.  The lists are EXACT under one total order: better score first (larger if largest
+ * != 0, smaller if not; -0.0 and +0.0 are equal), equal scores by ascending id, NaN scores after every number (among themselves by
+ * ascending id), empty slots last; the stored scores are the candidates' original bits.  The same `largest` on every call of a list.
+ * Two launches on `stream`, one after the other (grid Qs x slabs: a block filters its slab of one column against the list's K-th
+ * entry and sorts the survivors in LDS; then one block per column merges the partial lists into the list), no atomics, no read-back,
+ * capturable; the result does not depend on `slabs` (0 = choose; clamped to what the workspace holds) or on the order blocks run in.
+ * Workspace: glam_hits_workspace_bytes(L, Qs, K), 8-byte aligned (0 for a non-positive argument).  K in 1..1024, else
+ * GLAM_E_UNSUPPORTED — checked before the pointers are looked at; glam_hits_supported(K) is that check alone and returns a STATUS.
+ * L == 0 or Qs == 0: GLAM_OK, nothing launched, nothing dereferenced.  L >= 2^31, a negative size or stride, a null or misaligned
+ * pointer (4 bytes; seen and the workspace 8), a short workspace: GLAM_E_INVALID. */
+int glam_hits_supported(int K);
+size_t glam_hits_workspace_bytes(int64_t L, int64_t Qs, int K);
+int glam_hits_reset(float* top_score, int32_t* top_id, int64_t* seen, int64_t Qs, int K, void* stream);
+int glam_hits_merge(const float* score, int64_t ld_row, int64_t ld_col, const int32_t* ids, int64_t L, int64_t Qs, int K, int largest,
+                    int slabs, float* top_score, int32_t* top_id, int64_t* seen, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Training-mode block tails of the reference's DEFAULT configuration (src_1gp/model.py:30-31, run.py:35-37: RReLU activations,
  * Dropout(0.2) in front of every conv) — the same launches as glam_gru_tail_* / glam_bias_res_act_* with two additions:
  *   act = 4: torch.nn.RReLU in training mode, out = y > 0 ? y : a * y with a ~ U(rr_lower, rr_upper) per element;

@@ -1202,6 +1202,14 @@ def dot_and_global_pool2_gather(x1, x2, sp1, sp2, idx1=None, idx2=None, return_a
     return ops.pair_pool_gather(x1, x2, sp1, sp2, idx1, idx2, return_argmax)
 
 
+def dot_and_global_pool2_grid(x1, x2, sp1, sp2, plan, rows=None, sum1=None, sum2=None, return_argmax=False):
+    """``dot_and_global_pool2_gather`` for the WHOLE TABLE: every first-side segment ``rows[i]`` of ``sp1`` against every second-side
+    segment ``plan.sel[j]`` of ``sp2`` -> ``[R, Cs, 2]`` from one second-side-stationary launch with packed chunks (``ops.pair_pool_grid``;
+    ``ops.grid_plan`` for the plan; ``sum1`` / ``sum2``: the column sums of the encoded drugs, kept with them) — the fusion of
+    ``ArchitectureDDI.score_matrix``.  Inference only; the rows flow as they are."""
+    return ops.pair_pool_grid(x1, x2, sp1, sp2, plan, rows, sum1, sum2, return_argmax)
+
+
 def dot_and_global_pool2_gather_shared(x1, x2, sp1, sp2, idx1=None, idx2=None, with_identity=False):
     """``dot_and_global_pool2_gather`` for TRAINING: the same forward with a backward (``ops.pair_pool_gather_shared``) — a drug's rows,
     on either side, collect the gradients of every pair that points at it.  ``with_identity`` as in ``dot_and_global_pool2``."""

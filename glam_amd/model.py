@@ -19,7 +19,7 @@ from .layer import _None  # noqa: F401
 from .layer import GlobalPool5, GlobalLAPool, Set2Set  # noqa: F401  (resolved from config strings)
 from .layer import LinearBlock, MessageBlock, dot_and_global_pool2, first_node_spec, flat_then_head, following_dropout, prestage_pass
 from .layer import _BatchNorm, _LayerNorm, _PairNorm, dot_and_global_pool2_gather, dot_and_global_pool2_indexed, dot_and_global_pool2_shared
-from .layer import dot_and_global_pool2_gather_shared, dot_and_global_pool2_panel
+from .layer import dot_and_global_pool2_gather_shared, dot_and_global_pool2_grid, dot_and_global_pool2_panel
 
 
 def model_args(args):
@@ -202,6 +202,12 @@ def _check_encoding(model, what, enc, cls, stamp, rows, w):
         raise GlamHipError(f"{what}: the encoding is stale — {w['written']} was written since {w['encode']}(): encode again")
 
 
+def _head_is_per_row(model):
+    """Both norms of the head (``lin_out0`` / ``lin_out1``) are per row in ``eval()``: a pair row's result does not depend on the rows it
+    is batched with, so the head may run over the rows of several columns at once (``screen_panel``, ``score_matrix``)."""
+    return type(model.lin_out0.norm) in _PER_ROW_NORMS and type(model.lin_out1.norm) in _PER_ROW_NORMS
+
+
 def _shared_index(model, given, P, Q, device, **words):
     """``ops.pair_index`` of ``given``; the default of ``None`` is kept per (P, Q, device): the index a later capture of the same step
     meets already has its device copies.  ``words``: ``pair_index``'s own (``default``, ``name``, ``over``)."""
@@ -361,7 +367,7 @@ class ArchitectureDTI(torch.nn.Module):
         """Whether the head may run once over the ``L * Qs`` rows of a panel: both of its norms are per row in ``eval()`` (``_None``,
         ``_BatchNorm`` on running statistics).  The batch-less ``_LayerNorm`` / ``_PairNorm`` / ``_GraphSizeNorm`` take statistics (or the
         row count) over the whole matrix they are given, so they must see one protein column ``[L, .]`` at a time, as in ``screen``."""
-        return type(self.lin_out0.norm) in _PER_ROW_NORMS and type(self.lin_out1.norm) in _PER_ROW_NORMS
+        return _head_is_per_row(self)
 
     def screen_panel(self, data_mol, enc, proteins=None, return_argmax=False):
         """``[L, Qs, out_dim]``: column ``j`` is ``screen(data_mol, enc, pro_of_pair=[proteins[j]] * L)`` — every ligand of ``data_mol``
@@ -461,12 +467,41 @@ class DrugEncoding:
     """What ``ArchitectureDDI.encode_drugs`` keeps of ``Q`` molecule graphs for ``score_pairs``: ``rows1[s]`` / ``rows2[s]`` the rows of
     tower 1 / tower 2 after message step ``s`` (contiguous, as the fusion reads them), ``sp`` their one ``SegmentPtr``, ``flat1`` /
     ``flat2`` = ``molK_flat(molK_readout(.))`` ``[Q, hid]``, ``num_graphs`` = Q, and the stamp of the tower parameters it was computed
-    from (``model`` is a weak reference)."""
+    from (``model`` is a weak reference).
+
+    What the first ``score_matrix`` call on it adds (``grid()``; ``encode_drugs`` and ``score_pairs`` never touch these): ``sizes_host``, the
+    drugs' row counts on the host — ONE read-back of ``sp.ptr`` per encoding; ``sum1[s]`` / ``sum2[s]`` ``[Q, hid]``, the column sums of
+    ``rows1[s]`` / ``rows2[s]`` per drug (the two halves of the mean column: one segment-sum launch per step and tower); ``plans``, a small
+    cache of ``ops.GridPlan`` keyed by the column selection."""
+
+    _MAX_PLANS = 16
 
     def __init__(self, model, rows1, rows2, sp, flat1, flat2, stamp):
         self.model, self.rows1, self.rows2, self.sp = weakref.ref(model), rows1, rows2, sp
         self.flat1, self.flat2, self.stamp = flat1, flat2, stamp
         self.num_graphs = sp.B
+        self.sizes_host, self.sum1, self.sum2, self.plans = None, None, None, {}
+
+    def grid(self, cols=None):
+        """``ops.GridPlan`` of the column selection ``cols`` (``ops.grid_plan``: ``None`` = every drug in order) — from the cache when this
+        selection was planned before — after filling ``sizes_host`` (the one read-back) and ``sum1`` / ``sum2`` if this is the encoding's
+        first matrix call.  The selection is validated on the host before anything is launched or read back."""
+        # (validated on the host first — the sizes play no part in that — and before the read-back below)
+        sel = None if cols is None else ops.grid_plan([0] * self.num_graphs, cols).sel
+        key = None if sel is None else tuple(sel.tolist())
+        plan = self.plans.get(key)
+        if plan is None:
+            if self.sizes_host is None:
+                ptr = self.sp.ptr.cpu().numpy().astype("int64")
+                self.sizes_host = ptr[1:] - ptr[:-1]
+            plan = ops.grid_plan(self.sizes_host, sel)
+            while len(self.plans) >= self._MAX_PLANS:
+                self.plans.pop(next(iter(self.plans)))
+            self.plans[key] = plan
+        if self.sum1 is None:
+            self.sum1 = [ops.segment_pool(r, self.sp, "sum") for r in self.rows1]
+            self.sum2 = [ops.segment_pool(r, self.sp, "sum") for r in self.rows2]
+        return plan
 
 
 class ArchitectureDDI(torch.nn.Module):
@@ -570,6 +605,77 @@ class ArchitectureDDI(torch.nn.Module):
         o2 = enc.flat2.index_select(0, i2.on(dev))
         with ops.weight_scope():
             out = self.lin_out1(self.lin_out0(ops.cat_cols([o1, o2] + fusion)))
+        return (out, contacts) if return_argmax else out
+
+    # ---- the whole table: every selected drug (tower 1) against every selected drug (tower 2) ---------------------------------
+    # The head's hidden matrix is [pairs, e_dim]: at 2 000 x 2 000 drugs and e_dim = 1 024 it would be 16 GB in one piece.  The head
+    # therefore runs over blocks of consecutive row drugs whose hidden matrix stays under this cap — a design choice (room for the
+    # block's input, hidden and output beside a resident encoding on any device this runs on), NOT a measurement.
+    _MATRIX_BLOCK_BYTES = 512 << 20
+
+    def _matrix_head_in_one_pass(self):
+        """Whether the head may run over rows of SEVERAL column drugs at once: both of its norms are per row in ``eval()`` (the condition of
+        ``ArchitectureDTI._panel_head_in_one_pass``).  A batch-less ``_LayerNorm`` / ``_PairNorm`` / ``_GraphSizeNorm`` must see one column
+        ``[R, .]`` at a time: that is the ``[P, .]`` matrix of ``score_pairs(enc, rows, [cols[j]] * R)``."""
+        return _head_is_per_row(self)
+
+    def _matrix_block_rows(self, block_pairs, R, Cs):
+        """Row drugs per head block: at most ``block_pairs`` pair rows, or with 0 the largest whole number whose hidden matrix
+        ``rows * Cs * e_dim * 4`` bytes stays within ``_MATRIX_BLOCK_BYTES``; at least one row drug."""
+        if isinstance(block_pairs, bool) or not isinstance(block_pairs, int) or block_pairs < 0:
+            raise GlamHipError(f"score_matrix: block_pairs = {block_pairs!r} must be 0 (choose) or the pair rows per head block")
+        if block_pairs == 0:
+            block_pairs = self._MATRIX_BLOCK_BYTES // (4 * self.lin_out0.linear.out_features)
+        return max(1, min(R, block_pairs // max(Cs, 1)))
+
+    def score_matrix(self, enc, rows=None, cols=None, return_argmax=False, block_pairs=0):
+        """``[R, Cs, out_dim]``: entry ``[i, j]`` is ``score_pairs(enc, [rows[i]], [cols[j]])`` — tower 1 for the row drug, tower 2 for the
+        column drug, so the matrix is not symmetric — from one second-side-stationary fusion per step over the whole table
+        (``ops.pair_pool_grid`` on ``enc.rows1[step]`` / ``enc.rows2[step]``: several small drugs share the lanes of a wave) instead of
+        ``R * Cs`` listed pairs.  Every step's fusion max and the contacts equal those of ``score_pairs`` bit for bit; the output sits
+        within the fp32 parity bound of ``model(B1, B2)`` on the expanded batches.  ``rows`` / ``cols``: host integers in ``[0, Q)``, any
+        order, duplicates allowed (``ops.pair_index`` / ``ops.grid_plan``); ``None`` = all ``Q`` in order.  With per-row head norms
+        (``_None``, ``_BatchNorm``) the head runs over blocks of consecutive row drugs of at most ``block_pairs`` pair rows each (0 = as
+        many row drugs as keep the block's hidden matrix within 512 MiB; at least one): the ``[R * Cs, e_dim]`` matrix is never built in
+        one piece.  With a batch-less norm in the head it runs once per column on ``[R, .]`` — what ``score_pairs(enc, rows, [cols[j]] *
+        R)`` computes.  ``return_argmax``: also the per-step ``[R, Cs, 2]`` int32 contacts (row of ``enc.rows1[s]``, row of
+        ``enc.rows2[s]``).  The first call on an encoding reads the drugs' sizes back once and sums their rows per step and tower
+        (``DrugEncoding.grid``); after it, a call on the same encoding and column selection does no host synchronisation of its own."""
+        self._pairs_guard("score_matrix")
+        _check_encoding(self, "score_matrix", enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
+        Q = enc.num_graphs
+        R = ops.pair_count(rows, None, Q)
+        index = None if rows is None else ops.pair_index(rows, R, Q, name="rows", over="drugs")     # host-side, before the first launch
+        sel = None if cols is None else ops.grid_plan([0] * Q, cols).sel                            # (and before the read-back)
+        Cs = Q if sel is None else int(sel.shape[0])
+        per_block = self._matrix_block_rows(block_pairs, R, Cs)
+        plan = enc.grid(sel)
+        fusion, contacts = [], []
+        for s in range(self.message_steps):
+            f = dot_and_global_pool2_grid(enc.rows1[s], enc.rows2[s], enc.sp, enc.sp, plan, index, enc.sum1[s], enc.sum2[s], return_argmax)
+            if return_argmax:
+                f, a = f
+                contacts.append(a)
+            fusion.append(f)
+        dev = enc.flat1.device
+        o1 = enc.flat1 if index is None else enc.flat1.index_select(0, index.on(dev))              # [R, hid]
+        o2 = enc.flat2.index_select(0, plan.on(dev)[0])                                            # [Cs, hid]
+        out_dim = self.lin_out1.linear.out_features
+        with ops.weight_scope():
+            if R == 0 or Cs == 0:
+                out = o1.new_zeros(R, Cs, out_dim)
+            elif self._matrix_head_in_one_pass():
+                # row-major pair rows: row (i - i0) * Cs + j of a block = cat[flat1[rows[i]], flat2[cols[j]], fusion_0[i, j], ...]
+                out = o1.new_empty(R, Cs, out_dim)
+                for i0 in range(0, R, per_block):
+                    i1 = min(R, i0 + per_block)
+                    block = ops.cat_cols([o1[i0:i1].repeat_interleave(Cs, 0), o2.repeat(i1 - i0, 1)]
+                                         + [f[i0:i1].reshape((i1 - i0) * Cs, 2) for f in fusion])
+                    out[i0:i1] = self.lin_out1(self.lin_out0(block)).view(i1 - i0, Cs, out_dim)
+            else:
+                per_col = [self.lin_out1(self.lin_out0(ops.cat_cols([o1, o2[j:j + 1].expand(R, -1).contiguous()]
+                                                                    + [f[:, j].contiguous() for f in fusion]))) for j in range(Cs)]
+                out = torch.stack(per_col, 1)
         return (out, contacts) if return_argmax else out
 
     # ---- training on shared drugs: each tower runs once per DISTINCT drug of its side of the step ----------------------------

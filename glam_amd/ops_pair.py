@@ -509,6 +509,132 @@ def pair_pool_gather(x1, x2, sp1, sp2, idx1=None, idx2=None, return_argmax=False
 
 
 # --------------------------------------------------------------------------------------
+# drug x drug, the whole table: every selected first-side segment against every selected second-side one, second-side-stationary with
+# several small segments packed into the 64 lanes of a wave (csrc/pairgrid.hip, glam_pair_pool_grid_fwd)
+# --------------------------------------------------------------------------------------
+GRID_CHUNK = 64       # second-side rows per chunk (one per lane of the wave that holds them) = kGridChunk of csrc/pairgrid.hip
+
+
+class GridPlan(_Staged):
+    """The work of one grid call over a validated column selection: ``sel`` int32 ``[Cs]`` (every entry in ``[0, Q)``) and ``work`` int32
+    ``[256 * total_chunks + Cs + 1]``.  The selection is laid out in selection order, greedily: consecutive whole segments share a chunk
+    while their rows fit in its 64 lanes; a segment of more than 64 rows closes the running chunk and takes ``ceil(n / 64)`` slices of
+    its own (its last slice is not shared); an empty segment takes no lane.  ``work`` holds, per chunk and lane, four int32 —
+    ``(row of x2 the lane holds, b: that row inside its segment, n2: rows of that segment, partial: where the lane's best goes)`` with
+    ``partial = part_ptr[j] + slice`` for a lane of selection ``j`` and ``-1`` for an idle lane (which holds the row of lane 0 and
+    ``b = n2 = 0``); the lanes of one partial are contiguous — then ``part_ptr[Cs + 1]``, the offsets of the selections' partials (one
+    per whole segment, ``ceil(n / 64)`` for a sliced one, none for an empty one; ``n_partials`` in all).  ``lanes`` ``[total_chunks, 64,
+    4]`` / ``part_ptr`` are views of ``work``; ``fill`` is the mean share of a chunk's lanes that hold a row.  A duplicate of the
+    selection gets lanes and partials of its own.  Host numpy; ``on(device)`` -> ``(sel, work)`` on the device, made once per device
+    (one copy out of pinned memory, only enqueued) and shared by every launch that reads them."""
+
+    def __init__(self, sel, sizes):
+        self.sel, self.Cs, self.Q = sel, int(sel.shape[0]), int(sizes.shape[0])
+        first = np.zeros(self.Q + 1, dtype=np.int64)
+        np.cumsum(sizes, out=first[1:])
+        if int(first[-1]) >= 2 ** 31 - 1:
+            raise IndexError("grid_plan: the segments hold 2^31 rows or more")
+        self.N = int(first[-1])
+        n = sizes[sel]                                                               # rows per selection
+        part_ptr = np.zeros(self.Cs + 1, dtype=np.int64)
+        np.cumsum((n + GRID_CHUNK - 1) // GRID_CHUNK, out=part_ptr[1:])
+        if int(part_ptr[-1]) >= 2 ** 31 - 1 or int(n.sum()) >= 2 ** 31 - 1:
+            raise IndexError("grid_plan: the selection has 2^31 rows or partials or more")
+        self.n_partials = int(part_ptr[-1])
+        # the greedy walk: chunk and first lane of every selection (one pass over the selection; the rows are filled in below, at once)
+        chunk, lane0 = np.zeros(self.Cs, dtype=np.int64), np.zeros(self.Cs, dtype=np.int64)
+        c = used = 0                                                                 # the running chunk and its lanes in use
+        for j, nj in enumerate(n.tolist()):
+            if nj == 0:
+                continue
+            if used and (nj > GRID_CHUNK or used + nj > GRID_CHUNK):                 # does not fit behind (or never shares): close it
+                c, used = c + 1, 0
+            chunk[j], lane0[j] = c, used
+            if nj >= GRID_CHUNK:
+                c, used = c + (nj + GRID_CHUNK - 1) // GRID_CHUNK, 0                 # whole slices: nothing shares the last one
+            else:
+                used += nj
+        self.total_chunks = T = c + (1 if used else 0)
+        if T * GRID_CHUNK * 4 >= 2 ** 31 - 1:
+            raise IndexError("grid_plan: the selection's table has 2^31 entries or more")
+        j = np.repeat(np.arange(self.Cs, dtype=np.int64), n)
+        k = np.arange(j.shape[0], dtype=np.int64) - (np.cumsum(n) - n)[j]            # row inside its segment
+        table = np.zeros((T * GRID_CHUNK, 4), dtype=np.int32)
+        table[:, 3] = -1
+        at = chunk[j] * GRID_CHUNK + lane0[j] + k                                    # (a sliced segment starts at lane 0 and runs on)
+        table[at, 0], table[at, 1], table[at, 2] = first[sel[j]] + k, k, n[j]
+        table[at, 3] = part_ptr[j] + k // GRID_CHUNK
+        table = table.reshape(T, GRID_CHUNK, 4)
+        idle = table[:, :, 3] < 0
+        table[:, :, 0] = np.where(idle, table[:, :1, 0], table[:, :, 0])             # an idle lane reads the row of lane 0
+        self.fill = float(j.shape[0]) / (T * GRID_CHUNK) if T else 0.0
+        self.work = np.concatenate([table.reshape(-1), part_ptr.astype(np.int32)])
+        self.lanes, self.part_ptr = self.work[:4 * GRID_CHUNK * T].reshape(T, GRID_CHUNK, 4), self.work[4 * GRID_CHUNK * T:]
+        _Staged.__init__(self, "the grid's selection and lane table", self.sel, self.work)
+
+
+def grid_plan(sizes_host, cols=None):
+    """``GridPlan`` of the column selection ``cols`` over ``Q = len(sizes_host)`` segments of ``sizes_host[q]`` rows — host only (numpy),
+    before anything is launched (the kernel trusts the table; the policy of ``panel_plan``).  ``cols``: ``None`` = all ``Q`` in order,
+    or a host sequence / numpy array / CPU tensor of integers in ``[0, Q)``, in any order, duplicates allowed; ``IndexError`` for a
+    wrong dtype or an entry outside ``[0, Q)``; a device tensor is refused (validating it would be a hidden read-back)."""
+    sizes = host_ints(sizes_host, "sizes", None, wrong="grid_plan: the segments' sizes must be a vector of non-negative integers",
+                      on_device="grid_plan: the segments' sizes live on a device: the plan is built on the host — pass their host copy")
+    sizes = sizes.astype(np.int64)
+    Q = int(sizes.shape[0])
+    if cols is None:
+        return GridPlan(np.arange(Q, dtype=np.int32), sizes)
+    return GridPlan(host_ints(cols, "cols", "be a vector of segment numbers", below=Q).astype(np.int32), sizes)
+
+
+def pair_pool_grid(x1, x2, sp1, sp2, plan, rows=None, sum1=None, sum2=None, return_argmax=False, slab=0):
+    """``[max, mean]`` of ``x1[seg_a] @ x2[seg_q].T`` for EVERY selected first-side segment ``a = rows[i]`` and every selected second-side
+    segment ``q = plan.sel[j]`` -> ``[R, Cs, 2]``: the table of ``R * Cs`` pairs of ``pair_pool_gather`` from one second-side-stationary
+    launch (+ a finish launch) in which several small segments share the 64 lanes of a wave.  The max column — and with
+    ``return_argmax`` the ``[R, Cs, 2]`` int32 rows of the maximum in ``x1`` / ``x2`` (-1 for an empty segment on either side) — is bit
+    for bit that of ``pair_pool_gather`` on those pairs; the mean is ``<sum1[a], sum2[q]> / (n_a n_q)``, within the fp64-twin bound
+    (and, for ``rows=None``, the bits of ``pair_pool_panel``).  ``plan``: ``grid_plan`` over the sizes of ``sp2``'s segments.  ``rows``:
+    host integers in ``[0, sp1.B)``, any order, duplicates allowed (``pair_index``); ``None`` = all of ``sp1.B`` in order.  ``sum1``
+    ``[Q1, D]`` / ``sum2`` ``[Q2, D]``: the segments' column sums (``segment_pool(x, sp, "sum")``), computed here when missing — a
+    caller that keeps the segments keeps their sums too.  ``slab``: first-side segments per wave, 0 = the library chooses.  Widths
+    1..128.  Inference only: there is no backward (training is ``ops.pair_pool`` / ``ops.pair_pool_gather_shared``)."""
+    if not isinstance(plan, GridPlan):
+        raise GlamHipError("pair_pool_grid: plan must come from ops.grid_plan (the kernel trusts its table)")
+    Q1, Q2, Cs = sp1.B, sp2.B, plan.Cs
+    R = pair_count(rows, None, Q1)
+    index = None if rows is None else pair_index(rows, R, Q1, name="rows", over="drugs")        # host-side, before the first launch
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x1, x2, sum1, sum2)):
+        raise GlamHipError("pair_pool_grid is inference only (no backward): call it under torch.no_grad(); the training routes are "
+                           "ops.pair_pool on one graph per pair and side and ops.pair_pool_gather_shared on segments held once")
+    if plan.Q != Q2 or plan.N != sp2.N:
+        raise GlamHipError(f"pair_pool_grid: the plan was made for {plan.Q} segments of {plan.N} rows, the second side holds {Q2} of {sp2.N}")
+    x1, x2 = _operands("pair_pool_grid", x1, x2, sp1, sp2, "x1", "x2")
+    D, dev = x1.size(1), x1.device
+    for name, t, n in (("sum1", sum1, Q1), ("sum2", sum2, Q2)):
+        if t is not None and (t.dim() != 2 or tuple(t.shape) != (n, D) or t.device != dev):
+            raise GlamHipError(f"pair_pool_grid: {name} must be the [{n}, {D}] column sums on {dev}, got {tuple(t.shape)} on {t.device}")
+    if int(slab) < 0:
+        raise GlamHipError(f"pair_pool_grid: slab must be 0 (choose) or the first-side segments per wave, got {slab}")
+    lib = _lib.api()
+    if _lib.load().glam_pair_pool_grid_supported(D) != 0:           # (a status: the raw binding hands it back)
+        raise GlamHipError(f"pair_pool_grid: width {D} is outside the kernel table (1..128)")
+    out, arg, _, _ = _outputs((R, Cs), dev, arg=return_argmax)
+    if R and Cs and (sp1.N == 0 or sp2.N == 0):          # no row on one side: every pair is empty (and the empty matrix has no address to pass)
+        out.zero_()
+        if return_argmax:
+            arg.fill_(-1)
+    elif R and Cs:
+        sum1 = f32c(sum1, "sum1") if sum1 is not None else segment_pool(x1, sp1, "sum")
+        sum2 = f32c(sum2, "sum2") if sum2 is not None else segment_pool(x2, sp2, "sum")
+        sel, work = plan.on(dev)
+        ws = torch.empty(max(lib.glam_pair_pool_grid_workspace_bytes(plan.n_partials, R), 16), dtype=torch.uint8, device=dev)
+        lib.glam_pair_pool_grid_fwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if index is None else index.on(dev)), R,
+                                    ptr(sel), Cs, ptr(work), plan.total_chunks, plan.n_partials, Q1, Q2, D, ptr(sum1), ptr(sum2),
+                                    int(slab), ptr(out), ptr(arg), ptr(ws), ws.numel(), stream())
+    return (out, arg) if return_argmax else out
+
+
+# --------------------------------------------------------------------------------------
 # training on drugs held once: the gathered fusion with a backward (csrc/pairgather.hip train_fwd, csrc/pairgather_bwd.hip)
 # --------------------------------------------------------------------------------------
 class _PairPoolGatherShared(torch.autograd.Function):

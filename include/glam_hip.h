@@ -665,6 +665,28 @@ int glam_pair_pool_panel_fwd(const float* mol, const float* pro, const int32_t* 
                              const float* prosum, int slab, float* out, int32_t* argmax, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* Grid fusion (inference): EVERY selected first-side segment rows[i], i = 0..R-1 (int32[R], entries in [0, Q1), any order, duplicates
+ * allowed; NULL = the identity over Q1, needs R == Q1), of x1 (ptr1 int32[Q1+1]) against every selected second-side segment cols[j],
+ * j = 0..Cs-1 (int32[Cs], entries in [0, Q2), any order, duplicates allowed), of x2 (ptr2 int32[Q2+1]); each segment held once on its side:
+ * out f32[R,Cs,2] = [max, mean]; argmax int32[R,Cs,2] (row of x1, row of x2; may be NULL); an empty segment on either side gives 0, 0 and
+ * -1, -1.  The max and argmax are bit for bit those of glam_pair_pool_gather_fwd on the pairs (rows[i], cols[j]); the mean is
+ * <sum1[rows[i]], sum2[cols[j]]> / (n1 * n2), one ascending fmaf chain over the D columns (sum1 f32[Q1,D], sum2 f32[Q2,D]: the column sums
+ * of the segments, computed by the caller) — the chain of glam_pair_pool_panel_fwd.  Second-side-stationary grid with PACKED chunks
+ * (csrc/pairgrid.hip): one wave per (chunk of up to 64 second-side rows — the rows of several small segments side by side —, slab of
+ * first-side segments) + a finish launch.  work int32[256 * total_chunks + Cs + 1], built and checked by the caller and trusted here: per
+ * chunk and lane (row of x2 the lane holds, that row inside its segment, rows of that segment, index of the partial the lane's best goes
+ * to; -1 = an idle lane, which holds the row of lane 0), lanes of one partial contiguous; then part_ptr[Cs+1], the offsets of the
+ * selections' partials, n_partials in all.  slab: first-side segments per wave, 0 = choose (the panel's rule, untuned: about 4 096 waves
+ * where the problem has them, never fewer than 4 segments per wave).  Workspace: glam_pair_pool_grid_workspace_bytes(n_partials, R).
+ * D in 1..128, else GLAM_E_UNSUPPORTED; glam_pair_pool_grid_supported(D) is that check alone and returns a STATUS: GLAM_OK when the width
+ * has a kernel, GLAM_E_UNSUPPORTED otherwise.  R == 0 or Cs == 0: GLAM_OK, nothing launched, no pointer looked at.  Forward only. */
+size_t glam_pair_pool_grid_workspace_bytes(int64_t n_partials, int64_t R);
+int glam_pair_pool_grid_supported(int D);
+int glam_pair_pool_grid_fwd(const float* x1, const float* x2, const int32_t* ptr1, const int32_t* ptr2, const int32_t* rows, int64_t R,
+                            const int32_t* cols, int64_t Cs, const int32_t* work, int64_t total_chunks, int64_t n_partials, int64_t Q1,
+                            int64_t Q2, int D, const float* sum1, const float* sum2, int slab, float* out, int32_t* argmax,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* Screening hit lists: the best K candidates per query column, kept on the device while batches of scores stream past
  * (csrc/hits.hip).  State, owned by the caller: top_score f32[Qs,K] and top_id int32[Qs,K] — every list sorted best first, empty
  * slots (id -1, score NaN) at its end — and seen int64[1] in device memory, the number of candidates offered so far.

@@ -208,6 +208,65 @@ def _head_is_per_row(model):
     return type(model.lin_out0.norm) in _PER_ROW_NORMS and type(model.lin_out1.norm) in _PER_ROW_NORMS
 
 
+def _check_head(what, head):
+    """The ``head=`` keyword of the table calls: ``"rows"`` (the listed head over pair rows) or ``"factored"`` (``ops.pair_head``)."""
+    if head not in ("rows", "factored"):
+        raise GlamHipError(f"{what}: head = {head!r} is not \"rows\" (the listed head over the table's pair rows) or \"factored\" "
+                           "(ops.pair_head: no [pairs, e_dim] hidden matrix)")
+    return head == "factored"
+
+
+def _factored_head(model, what, block_pairs=0):
+    """``(act, slope)`` of ``ops.pair_head`` for ``model``'s head (``lin_out0`` / ``lin_out1``), or the refusal of ``head="factored"`` —
+    on the host, before the first launch.  The factored head is ``lin_out1.linear(act(lin_out0.linear(.)))``: both norm slots ``_None``,
+    both dropout slots idle (``_None``, or a ``Dropout`` in ``eval()``), ``end_act`` elementwise and deterministic, at most 8 task columns,
+    and no head blocks (there is no hidden matrix to keep in pieces)."""
+    from torch.nn import Dropout, LeakyReLU, ReLU, RReLU
+    for name in ("lin_out0", "lin_out1"):
+        block = getattr(model, name)
+        if type(block.norm) is not _None:
+            raise GlamHipError(f"{what}: head=\"factored\" has no norm in the head, {name}'s norm is {type(block.norm).__name__} — its "
+                               "input does not separate into a row part and a column part: use head=\"rows\"")
+        d = block.dropout
+        if not (type(d) is _None or (type(d) is Dropout and (not d.training or d.p == 0))):
+            raise GlamHipError(f"{what}: head=\"factored\" needs {name}'s dropout slot idle (_None, or a Dropout in eval()), got "
+                               f"{type(d).__name__}: use head=\"rows\"")
+    a = model.lin_out0.act
+    if type(a) is _None:
+        act = "none", 0.0
+    elif type(a) is ReLU:
+        act = "relu", 0.0
+    elif type(a) is LeakyReLU:
+        act = "leaky", float(a.negative_slope)
+    elif type(a) is RReLU and not a.training:
+        act = "leaky", (float(a.lower) + float(a.upper)) / 2          # eval: the fixed mean slope, as in LinearBlock.forward
+    else:
+        raise GlamHipError(f"{what}: head=\"factored\" applies end_act inside its kernel and knows _None, ReLU, LeakyReLU and RReLU (eval), "
+                           f"not {type(a).__name__}: use head=\"rows\"")
+    if type(model.lin_out1.act) is not _None:
+        raise GlamHipError(f"{what}: head=\"factored\" ends in lin_out1's linear layer, which here is followed by "
+                           f"{type(model.lin_out1.act).__name__}: use head=\"rows\"")
+    out_dim = model.lin_out1.linear.out_features
+    if out_dim > ops.HEAD_MAX_OUT:
+        raise GlamHipError(f"{what}: head=\"factored\" keeps out_dim accumulators per pair in registers, at most {ops.HEAD_MAX_OUT}; "
+                           f"this model has out_dim = {out_dim}: use head=\"rows\"")
+    if 2 * model.message_steps > ops.HEAD_MAX_F:
+        raise GlamHipError(f"{what}: head=\"factored\" keeps the 2 * message_steps fusion columns of a pair in registers, at most "
+                           f"{ops.HEAD_MAX_F}; this model has {2 * model.message_steps}: use head=\"rows\"")
+    if isinstance(block_pairs, bool) or block_pairs != 0:
+        raise GlamHipError(f"{what}: block_pairs = {block_pairs!r} cuts the hidden matrix of head=\"rows\" into blocks; head=\"factored\" has "
+                           "no hidden matrix and no blocks: leave block_pairs at 0")
+    return act
+
+
+def _table_head_factored(model, act, flat_a, flat_b, fusion, R, Cs):
+    """``ops.pair_head`` over the table: the two flat matrices as they are, ``f`` = the steps' ``[R, Cs, 2]`` fusions side by side."""
+    f = None
+    if fusion:
+        f = ops.cat_cols([t.reshape(R * Cs, 2) for t in fusion]).view(R, Cs, 2 * len(fusion))
+    return ops.pair_head(flat_a, flat_b, f, model.lin_out0.linear, model.lin_out1.linear, act[0], act[1])
+
+
 def _shared_index(model, given, P, Q, device, **words):
     """``ops.pair_index`` of ``given``; the default of ``None`` is kept per (P, Q, device): the index a later capture of the same step
     meets already has its device copies.  ``words``: ``pair_index``'s own (``default``, ``name``, ``over``)."""
@@ -369,7 +428,7 @@ class ArchitectureDTI(torch.nn.Module):
         row count) over the whole matrix they are given, so they must see one protein column ``[L, .]`` at a time, as in ``screen``."""
         return _head_is_per_row(self)
 
-    def screen_panel(self, data_mol, enc, proteins=None, return_argmax=False):
+    def screen_panel(self, data_mol, enc, proteins=None, return_argmax=False, head="rows"):
         """``[L, Qs, out_dim]``: column ``j`` is ``screen(data_mol, enc, pro_of_pair=[proteins[j]] * L)`` — every ligand of ``data_mol``
         against every protein of the selection — from ONE pass of the ligand tower and one protein-stationary fusion per step
         (``ops.pair_pool_panel`` on ``enc.rows[step]``).  Every step's fusion max and the contacts equal those of the ``screen`` calls
@@ -377,9 +436,14 @@ class ArchitectureDTI(torch.nn.Module):
         ``proteins``: host integers in ``[0, Q)``, any order, duplicates allowed (``ops.panel_plan``); ``None`` = all ``Q`` in order.
         ``return_argmax``: also the per-step ``[L, Qs, 2]`` int32 contacts (row of ``data_mol.x``, row of the encoded proteins).
         The first call on an encoding reads the proteins' sizes back once and sums their rows per step (``ProteinEncoding.panel``);
-        after it, a call on the same encoding and selection does no host synchronisation of its own."""
+        after it, a call on the same encoding and selection does no host synchronisation of its own.
+        ``head``: ``"rows"`` is the listed head over the ``L * Qs`` pair rows; ``"factored"`` sends it through ``ops.pair_head`` (no pair
+        rows, no ``[L * Qs, e_dim]`` hidden matrix; within the same parity bound, not the bits of ``"rows"``) and is refused — before the
+        first launch, with the reason — for a norm in the head, an ``end_act`` other than ``_None`` / ``ReLU`` / ``LeakyReLU`` / ``RReLU``
+        and ``out_dim > 8``."""
         self._screen_guard("screen_panel")
         _check_encoding(self, "screen_panel", enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
+        act = _factored_head(self, "screen_panel") if _check_head("screen_panel", head) else None
         plan = enc.panel(proteins)                                 # host-side checks, before the first launch
         m = _Tower(self, "mol", data_mol)
         msp = ops.segment_ptr(data_mol.batch, m.n)
@@ -391,6 +455,8 @@ class ArchitectureDTI(torch.nn.Module):
             outp = enc.flat.index_select(0, plan.on(enc.flat.device)[0].long())                   # [Qs, hid]
             if L == 0 or Qs == 0:
                 out = outm.new_zeros(L, Qs, self.lin_out1.linear.out_features)
+            elif act:
+                out = _table_head_factored(self, act, outm, outp, fusion, L, Qs)
             elif self._panel_head_in_one_pass():
                 # ligand-major rows: row l * Qs + j = cat[outm[l], flat[sel[j]], fusion_0[l, j], ...]
                 rows = ops.cat_cols([outm.repeat_interleave(Qs, 0), outp.repeat(L, 1)] + [f.reshape(L * Qs, 2) for f in fusion])
@@ -401,14 +467,14 @@ class ArchitectureDTI(torch.nn.Module):
                 out = torch.stack(cols, 1)
         return (out, contacts) if return_argmax else out
 
-    def screen_top(self, batches, enc, proteins=None, k=100, task=0, largest=True):
+    def screen_top(self, batches, enc, proteins=None, k=100, task=0, largest=True, head="rows"):
         """The best ``k`` ligands per selected protein of a whole library -> ``hits.HitList`` with one query per entry of the selection
         (duplicates allowed, as in ``ops.panel_plan``).  ``batches``: an iterable of ``data_mol`` or ``(data_mol, ids)``; every item goes
         through ``screen_panel(data_mol, enc, proteins)`` — all of its guards and refusals apply, with its own messages — and column
         ``task`` of its output is merged into the lists by stride (``HitList.update``: two launches, no copy).  ``ids``: the ligands' ids,
         host integers or an int32 device tensor; without them a ligand's id is its position in the stream.  Ids are not deduplicated.
         Memory is ``Qs x k`` however long the stream: no score tensor outlives its batch, and the loop adds no read-back to those of
-        ``screen_panel`` (one per encoding).  ``k`` in 1..1024; ``largest``: whether a larger score is better."""
+        ``screen_panel`` (one per encoding).  ``k`` in 1..1024; ``largest``: whether a larger score is better.  ``head``: ``screen_panel``'s."""
         k = hits.check_k(k, "screen_top")
         out_dim = self.lin_out1.linear.out_features
         if isinstance(task, bool) or not isinstance(task, int) or not 0 <= task < out_dim:
@@ -416,13 +482,15 @@ class ArchitectureDTI(torch.nn.Module):
         top = None
         for item in batches:
             data_mol, ids = item if isinstance(item, tuple) else (item, None)
-            out = self.screen_panel(data_mol, enc, proteins)
+            out = self.screen_panel(data_mol, enc, proteins, head=head)
             if top is None:
                 top = hits.HitList(out.size(1), k, out.device, largest)
             top.update(out, ids, task)
         if top is None:          # an empty stream: empty lists, after the checks a first batch would have met
             self._screen_guard("screen_panel")
             _check_encoding(self, "screen_panel", enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
+            if _check_head("screen_panel", head):
+                _factored_head(self, "screen_panel")
             top = hits.HitList(ops.panel_plan([0] * enc.num_graphs, proteins).Qs, k, enc.flat.device, largest)     # (host only: no read-back)
         return top
 
@@ -628,7 +696,7 @@ class ArchitectureDDI(torch.nn.Module):
             block_pairs = self._MATRIX_BLOCK_BYTES // (4 * self.lin_out0.linear.out_features)
         return max(1, min(R, block_pairs // max(Cs, 1)))
 
-    def score_matrix(self, enc, rows=None, cols=None, return_argmax=False, block_pairs=0):
+    def score_matrix(self, enc, rows=None, cols=None, return_argmax=False, block_pairs=0, head="rows"):
         """``[R, Cs, out_dim]``: entry ``[i, j]`` is ``score_pairs(enc, [rows[i]], [cols[j]])`` — tower 1 for the row drug, tower 2 for the
         column drug, so the matrix is not symmetric — from one second-side-stationary fusion per step over the whole table
         (``ops.pair_pool_grid`` on ``enc.rows1[step]`` / ``enc.rows2[step]``: several small drugs share the lanes of a wave) instead of
@@ -640,15 +708,21 @@ class ArchitectureDDI(torch.nn.Module):
         one piece.  With a batch-less norm in the head it runs once per column on ``[R, .]`` — what ``score_pairs(enc, rows, [cols[j]] *
         R)`` computes.  ``return_argmax``: also the per-step ``[R, Cs, 2]`` int32 contacts (row of ``enc.rows1[s]``, row of
         ``enc.rows2[s]``).  The first call on an encoding reads the drugs' sizes back once and sums their rows per step and tower
-        (``DrugEncoding.grid``); after it, a call on the same encoding and column selection does no host synchronisation of its own."""
+        (``DrugEncoding.grid``); after it, a call on the same encoding and column selection does no host synchronisation of its own.
+        ``head``: ``"rows"`` is the head described above; ``"factored"`` sends it through ``ops.pair_head`` — the first linear layer as a row
+        part + a column part + the fusion columns' part, so neither the pair rows nor the hidden matrix exist and an entry's bits do not
+        depend on the selection around it; within the same parity bound, not the bits of ``"rows"``.  It is refused — before the first
+        launch, with the reason — for a norm in the head, an ``end_act`` other than ``_None`` / ``ReLU`` / ``LeakyReLU`` / ``RReLU``,
+        ``out_dim > 8`` and ``block_pairs != 0`` (it has no blocks)."""
         self._pairs_guard("score_matrix")
         _check_encoding(self, "score_matrix", enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
+        act = _factored_head(self, "score_matrix", block_pairs) if _check_head("score_matrix", head) else None
         Q = enc.num_graphs
         R = ops.pair_count(rows, None, Q)
         index = None if rows is None else ops.pair_index(rows, R, Q, name="rows", over="drugs")     # host-side, before the first launch
         sel = None if cols is None else ops.grid_plan([0] * Q, cols).sel                            # (and before the read-back)
         Cs = Q if sel is None else int(sel.shape[0])
-        per_block = self._matrix_block_rows(block_pairs, R, Cs)
+        per_block = None if act else self._matrix_block_rows(block_pairs, R, Cs)
         plan = enc.grid(sel)
         fusion, contacts = [], []
         for s in range(self.message_steps):
@@ -664,6 +738,8 @@ class ArchitectureDDI(torch.nn.Module):
         with ops.weight_scope():
             if R == 0 or Cs == 0:
                 out = o1.new_zeros(R, Cs, out_dim)
+            elif act:
+                out = _table_head_factored(self, act, o1, o2, fusion, R, Cs)
             elif self._matrix_head_in_one_pass():
                 # row-major pair rows: row (i - i0) * Cs + j of a block = cat[flat1[rows[i]], flat2[cols[j]], fusion_0[i, j], ...]
                 out = o1.new_empty(R, Cs, out_dim)
@@ -677,6 +753,42 @@ class ArchitectureDDI(torch.nn.Module):
                                                                     + [f[:, j].contiguous() for f in fusion]))) for j in range(Cs)]
                 out = torch.stack(per_col, 1)
         return (out, contacts) if return_argmax else out
+
+    # ---- partner lists: the best row drugs per column drug, without the table -------------------------------------------------
+    # Pair rows per block of row drugs when the caller leaves the choice (block_rows = 0): 2^22 — a design choice (a block's scores and
+    # fusion columns stay in the tens of MiB whatever the library's size, and a block is still thousands of waves), NOT a measurement.
+    _TOP_BLOCK_PAIRS = 1 << 22
+
+    def matrix_top(self, enc, rows=None, cols=None, k=100, task=0, largest=True, block_rows=0, head="factored"):
+        """The best ``k`` row drugs (tower 1) for every selected column drug (tower 2) -> ``hits.HitList`` with one query per entry of
+        ``cols`` (duplicates allowed) — without the ``[R, Cs]`` table ever existing.  ``rows`` is walked in blocks of ``block_rows`` row drugs
+        (0 = as many as keep a block within ``2^22`` pair rows, at least one); every block goes through ``score_matrix(enc, block, cols,
+        head=head)`` — all of its guards and refusals apply, with its own messages — and column ``task`` of its output is merged into the
+        lists (``HitList.update``: two launches, no copy) under the ids of the block's drugs, so a drug that ``rows`` names twice can hold two
+        slots.  With ``head="factored"`` an entry's bits do not depend on the block it is scored in: the lists are those of the whole
+        table.  Memory is ``Cs x k`` plus one block however long ``rows`` is.  ``k`` in 1..1024; ``largest``: whether a larger score is
+        better.  An empty ``rows`` gives empty lists, after the checks a first block would have met."""
+        k = hits.check_k(k, "matrix_top")
+        out_dim = self.lin_out1.linear.out_features
+        if isinstance(task, bool) or not isinstance(task, int) or not 0 <= task < out_dim:
+            raise GlamHipError(f"matrix_top: task = {task!r} is not one of the model's {out_dim} task column(s)")
+        if isinstance(block_rows, bool) or not isinstance(block_rows, int) or block_rows < 0:
+            raise GlamHipError(f"matrix_top: block_rows = {block_rows!r} must be 0 (choose) or the row drugs per block")
+        self._pairs_guard("score_matrix")
+        _check_encoding(self, "score_matrix", enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
+        if _check_head("score_matrix", head):
+            _factored_head(self, "score_matrix")
+        Q = enc.num_graphs
+        R = ops.pair_count(rows, None, Q)
+        ids = ops.pair_index(rows, R, Q, name="rows", over="drugs").host                            # host-side, before the first launch
+        sel = None if cols is None else ops.grid_plan([0] * Q, cols).sel
+        Cs = Q if sel is None else int(sel.shape[0])
+        per_block = block_rows or max(1, min(R, self._TOP_BLOCK_PAIRS // max(Cs, 1)))
+        top = hits.HitList(Cs, k, enc.flat1.device, largest)
+        for i0 in range(0, R, per_block):
+            block = ids[i0:i0 + per_block]
+            top.update(self.score_matrix(enc, block, sel, head=head), block, task)
+        return top
 
     # ---- training on shared drugs: each tower runs once per DISTINCT drug of its side of the step ----------------------------
     def _shared_index(self, given, P, Q, device, name):

@@ -696,3 +696,82 @@ def pair_pool_gather_shared(x1, x2, sp1, sp2, idx1=None, idx2=None, with_identit
     i2 = pair_index(idx2, P, sp2.B, name="idx2", over="segments of x2")
     # (no add_width: glam_pair_pool_gather_bwd adds inside its launch for every width of its table)
     return _apply_aliasing(_PairPoolGatherShared, (x1, x2, sp1, sp2, i1, i2, idx1 is None, idx2 is None), x1, x2, with_identity)
+
+
+# --------------------------------------------------------------------------------------
+# the head over a table: both linear layers without the [pairs, e_dim] hidden matrix (csrc/pairhead.hip, glam_pair_head_fwd)
+# --------------------------------------------------------------------------------------
+_HEAD_ACTS = {"none": 0, "relu": 1, "leaky": 2}
+HEAD_MAX_OUT, HEAD_MAX_F = 8, 16          # = kHeadMaxOut / kHeadMaxF of csrc/pairhead.hip
+
+
+def _weight_bias(lin, name):
+    """``(weight, bias)`` of ``lin`` — a ``torch.nn.Linear`` or the pair of tensors itself."""
+    if isinstance(lin, torch.nn.Linear):
+        return lin.weight, lin.bias
+    if isinstance(lin, (tuple, list)) and len(lin) == 2 and all(torch.is_tensor(t) for t in lin):
+        return lin[0], lin[1]
+    raise GlamHipError(f"pair_head: {name} must be a torch.nn.Linear with a bias or its (weight, bias) tensors, got {type(lin).__name__}")
+
+
+def _rows_view(t, name):
+    """A 2-D fp32 matrix whose rows are contiguous, as it is (a ``[n, C]`` view of padded rows keeps its leading dimension), else its
+    contiguous copy."""
+    if t.dtype != torch.float32:
+        raise GlamHipError(f"{name}: expected float32, got {t.dtype}")
+    return t if t.stride(1) == 1 and t.stride(0) >= t.size(1) else t.contiguous()
+
+
+def pair_head(flat_a, flat_b, f, lin0, lin1, act="none", slope=0.0):
+    """``lin1(act(lin0(cat[flat_a[i], flat_b[j], f[i, j]])))`` for EVERY ``i`` and ``j`` -> ``[R, Cs, out_dim]``: the two linear layers of a pair
+    model's head over a table, without the ``[R * Cs, 2 hid + F]`` input rows and the ``[R * Cs, e_dim]`` hidden matrix — the first layer
+    separates into ``A[i] + B[j] + Wf f[i, j]`` and only the ``F`` fusion columns are per pair (two launches: ``k_pair_head_side``,
+    ``k_pair_head``).  ``flat_a`` ``[R, hid]`` / ``flat_b`` ``[Cs, hid]``: as they are, views of padded rows included; ``f`` ``[R, Cs, F]`` or
+    ``None`` for ``F = 0``; ``lin0`` / ``lin1``: the two ``torch.nn.Linear`` (``2 hid + F -> e_dim -> out_dim``) or their ``(weight, bias)``;
+    ``act``: ``"none"``, ``"relu"`` or ``"leaky"`` with ``slope`` (an ``RReLU`` in ``eval()`` is a leaky of its mean slope).  An entry is
+    one fixed chain of its own ``(flat_a[i], flat_b[j], f[i, j])``: the same bits whatever the rest of the table is.  ``out_dim`` in 1..8,
+    ``F`` in 0..16, ``R * Cs < 2^31 - 1``.  Inference only: there is no backward (a head that trains is the listed one: ``head="rows"`` of
+    the table calls, ``model(...)`` / ``forward_shared`` for training)."""
+    w0, b0 = _weight_bias(lin0, "lin0")
+    w1, b1 = _weight_bias(lin1, "lin1")
+    if b0 is None or b1 is None:
+        raise GlamHipError("pair_head: both linear layers must have a bias")
+    given = (flat_a, flat_b, f, w0, b0, w1, b1)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in given):
+        raise GlamHipError("pair_head is inference only (no backward): call it under torch.no_grad(); the head that trains is the listed "
+                           "one — head=\"rows\" of score_matrix / screen_panel, and model(...) / forward_shared for the training calls")
+    require_device(*given)
+    if act not in _HEAD_ACTS:
+        raise GlamHipError(f"pair_head: act = {act!r} is not one of 'none', 'relu', 'leaky'")
+    if flat_a.dim() != 2 or flat_b.dim() != 2 or flat_a.size(1) != flat_b.size(1) or flat_a.size(1) < 1:
+        raise GlamHipError(f"pair_head: the two sides disagree (width): flat_a {tuple(flat_a.shape)}, flat_b {tuple(flat_b.shape)}")
+    R, Cs, hid = flat_a.size(0), flat_b.size(0), flat_a.size(1)
+    if f is not None and (f.dim() != 3 or tuple(f.shape[:2]) != (R, Cs)):
+        raise GlamHipError(f"pair_head: f must be [{R}, {Cs}, F] (or None for F = 0), got {tuple(f.shape)}")
+    F = 0 if f is None else f.size(2)
+    if w0.dim() != 2 or w0.size(1) != 2 * hid + F or tuple(b0.shape) != (w0.size(0),) or w0.size(0) < 1:
+        raise GlamHipError(f"pair_head: lin0 must map 2 * {hid} + {F} = {2 * hid + F} columns and carry one bias per output, got weight "
+                           f"{tuple(w0.shape)}, bias {tuple(b0.shape)}")
+    e_dim = w0.size(0)
+    if w1.dim() != 2 or w1.size(1) != e_dim or tuple(b1.shape) != (w1.size(0),):
+        raise GlamHipError(f"pair_head: lin1 must map the {e_dim} outputs of lin0 and carry one bias per output, got weight "
+                           f"{tuple(w1.shape)}, bias {tuple(b1.shape)}")
+    out_dim = w1.size(0)
+    if not 1 <= out_dim <= HEAD_MAX_OUT:
+        raise GlamHipError(f"pair_head: out_dim = {out_dim} is outside 1..{HEAD_MAX_OUT} (head=\"rows\" takes any)")
+    if F > HEAD_MAX_F:
+        raise GlamHipError(f"pair_head: F = {F} fusion columns are outside 0..{HEAD_MAX_F} (head=\"rows\" takes any)")
+    if R * Cs >= 2 ** 31 - 1:
+        raise GlamHipError(f"pair_head: a table of {R} x {Cs} pairs holds 2^31 - 1 entries or more: score it in blocks of rows")
+    a, b = _rows_view(flat_a, "flat_a"), _rows_view(flat_b, "flat_b")
+    w0 = _rows_view(w0, "lin0.weight")
+    w1, b0, b1 = f32c(w1, "lin1.weight"), f32c(b0, "lin0.bias"), f32c(b1, "lin1.bias")
+    f = None if F == 0 else f32c(f, "f")
+    dev = flat_a.device
+    out = torch.empty(R, Cs, out_dim, dtype=torch.float32, device=dev)
+    if R and Cs:
+        lib = _lib.api()
+        ws = torch.empty(max(lib.glam_pair_head_workspace_bytes(R, Cs, e_dim), 16), dtype=torch.uint8, device=dev)
+        lib.glam_pair_head_fwd(ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(f), R, Cs, hid, F, ptr(w0), w0.stride(0), ptr(b0), e_dim, ptr(w1),
+                               ptr(b1), out_dim, _HEAD_ACTS[act], float(slope), ptr(ws), ws.numel(), ptr(out), stream())
+    return out

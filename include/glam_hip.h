@@ -687,6 +687,24 @@ int glam_pair_pool_grid_fwd(const float* x1, const float* x2, const int32_t* ptr
                             int64_t Q2, int D, const float* sum1, const float* sum2, int slab, float* out, int32_t* argmax,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* Factored pair head (inference): the two linear layers of the pair models' head over a TABLE of R x Cs pairs, for a head without norms
+ * and with an elementwise activation (csrc/pairhead.hip):
+ *   out[i,j,o] = b1[o] + sum_e w1[o,e] * act(A[i,e] + B[j,e] + sum_k W0[e, 2 hid + k] * f[i,j,k])
+ *   A[i,e] = b0[e] + sum_c W0[e,c] * flat_a[i,c],   B[j,e] = sum_c W0[e, hid + c] * flat_b[j,c]
+ * which is lin1(act(lin0(cat[flat_a[i], flat_b[j], f[i,j]]))) without the [R*Cs, 2 hid + F] input rows and the [R*Cs, e_dim] hidden matrix.
+ * flat_a f32[R,hid] (leading dimension lda >= hid), flat_b f32[Cs,hid] (ldb); f f32[R,Cs,F] contiguous (NULL with F == 0); W0
+ * f32[e_dim, 2 hid + F] (leading dimension ldw), read in place; b0 f32[e_dim]; w1 f32[out_dim,e_dim] contiguous; b1 f32[out_dim]; out
+ * f32[R,Cs,out_dim].  act: 0 none, 1 relu, 2 leaky (h > 0 ? h : slope * h).  Two launches on `stream`: k_pair_head_side (A and B, both from
+ * the one launch, into the workspace) and k_pair_head.  Every A / B element is one ascending fmaf chain from its bias, every out element
+ * one ascending chain over e from b1[o]: an entry depends on its own (flat_a[i], flat_b[j], f[i,j]) alone — the same bits whatever R, Cs
+ * and the rest of the table are.  Workspace: glam_pair_head_workspace_bytes(R, Cs, e_dim) = (R + Cs) * e_dim floats, 4-byte aligned.
+ * 1 <= out_dim <= 8, 0 <= F <= 16, e_dim >= 1, hid >= 1, R * Cs < 2^31 - 1, else GLAM_E_INVALID — as a null or misaligned pointer or a short
+ * workspace; every check comes before any device work.  R == 0 or Cs == 0: GLAM_OK, nothing launched, no pointer looked at.  Forward only. */
+size_t glam_pair_head_workspace_bytes(int64_t R, int64_t Cs, int e_dim);
+int glam_pair_head_fwd(const float* flat_a, int64_t lda, const float* flat_b, int64_t ldb, const float* f, int64_t R, int64_t Cs, int hid,
+                       int F, const float* W0, int64_t ldw, const float* b0, int e_dim, const float* w1, const float* b1, int out_dim,
+                       int act, float slope, void* workspace, size_t workspace_bytes, float* out, void* stream);
+
 /* Screening hit lists: the best K candidates per query column, kept on the device while batches of scores stream past
  * (csrc/hits.hip).  State, owned by the caller: top_score f32[Qs,K] and top_id int32[Qs,K] — every list sorted best first, empty
  * slots (id -1, score NaN) at its end — and seen int64[1] in device memory, the number of candidates offered so far.

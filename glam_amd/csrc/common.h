@@ -109,6 +109,17 @@ __device__ __forceinline__ float4 ld4nt(const float* p) {
 __device__ __forceinline__ void st4g(float* p, float4 v) { *(glam_gv4*)(p) = (glam_v4f){v.x, v.y, v.z, v.w}; }
 __device__ __forceinline__ void st1g(float* p, float v) { *(glam_gf1*)(p) = v; }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+// Wave-uniform reads of data the launch does not write (the constant address space: the scalar unit fetches a value once per wave and a
+// multiply-add takes it as its scalar operand) ...
+typedef __attribute__((address_space(4))) const float glam_cf1;
+typedef __attribute__((address_space(4))) const glam_v4f glam_cv4;
+// ... through p, which every lane of the wave holds alike, said so to the compiler (its loads then go to the scalar unit whatever the
+// analysis finds)
+__device__ __forceinline__ const float* uniform_ptr(const float* p) {
+    const uintptr_t v = (uintptr_t)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (const float*)(((uintptr_t)hi << 32) | lo);
+}
 // base + 32-bit BYTE offset: lets the compiler use the scalar-base + 32-bit-VGPR-offset addressing mode instead of
 // 64-bit pointer arithmetic on the vector ALU (the hosts check that every tensor stays below 4 GiB)
 __device__ __forceinline__ float4 ld4o(const float* base, unsigned byte_off) {

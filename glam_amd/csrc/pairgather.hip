@@ -29,16 +29,6 @@ namespace glam {
 constexpr int kGatherPairs = kBlock / 64;      // pairs (waves) per block
 constexpr int kGatherMaxD = 128;
 
-typedef __attribute__((address_space(4))) const float glam_cf1;          // wave-uniform reads of data no launch of this file writes
-typedef __attribute__((address_space(4))) const glam_v4f glam_cv4;
-
-// p, which every lane of the wave holds alike, said so to the compiler (its loads then go to the scalar unit whatever the analysis finds)
-__device__ __forceinline__ const float* gather_uniform(const float* p) {
-    const uintptr_t v = (uintptr_t)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (const float*)(((uintptr_t)hi << 32) | lo);
-}
-
 __device__ __forceinline__ bool gather_better(float v, int ix, float best, int bidx) { return v > best || (v == best && ix < bidx); }
 
 // column c of the sums of rows [m0, m0 + n1) of x1 and [p0, p0 + n2) of x2, rows in ascending order.  Both segments go eight rows a
@@ -120,7 +110,7 @@ __global__ void __launch_bounds__(kBlock) k_pair_gather(const float* __restrict_
         }
         for (int r1 = 0; r1 < n1; r1 += 2) {
             const bool two = r1 + 1 < n1;                  // (an odd last row is scored twice and counted once)
-            const float* q0 = gather_uniform(x1 + (size_t)(m0 + r1) * D);
+            const float* q0 = uniform_ptr(x1 + (size_t)(m0 + r1) * D);
             const float* q1 = q0 + (two ? D : 0);
             float d0 = 0.f, d1 = 0.f;
             if constexpr (kVec) {

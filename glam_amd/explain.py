@@ -5,6 +5,10 @@ nothing).  The functions here compute them from the INPUTS of a conv / readout w
 (``csrc/attn_export.hip``): per-edge, per-head attention of a message step, per-atom "attention sent", and the readout's per-node
 weights.  ``explain(model, batch)`` runs one eager eval forward of an ``Architecture``, captures those inputs with forward
 pre-hooks and returns everything ``visualize_gp.py`` paints from.  No autograd, no CPU path: CPU tensors raise ``GlamHipError``.
+
+The two-tower models have ``explain_pair``: the scoring call (``screen`` / ``score_pairs``) plus, per message step, the maps of its
+fusion — per atom the best partner row and the mean over the partner's rows, and the same per residue / per atom of the other drug
+(``ops.pair_map``, ``csrc/pairmap.hip``: one launch for both sides, the score matrix never stored).
 """
 from __future__ import annotations
 
@@ -253,8 +257,8 @@ def explain(model, batch):
     The model must be in eval mode: training-mode RReLU and Dropout would make the explanation random."""
     from .model import Architecture
     if not isinstance(model, Architecture):
-        raise GlamHipError(f"explain: expected an Architecture, got {type(model).__name__} (for the two-tower models use conv_attention / "
-                           "readout_attention on their blocks)")
+        raise GlamHipError(f"explain: expected an Architecture, got {type(model).__name__} (the two-tower models have explain_pair: the "
+                           "per-atom and per-residue maps of their fusion; conv_attention / readout_attention work on their blocks)")
     if model.training:
         raise GlamHipError("explain: the model is in training mode (RReLU slopes and Dropout masks are random there): call model.eval() first")
     require_device(batch.x, batch.edge_index, batch.edge_attr, batch.batch)
@@ -288,3 +292,96 @@ def explain(model, batch):
     ro = model.mol_readout
     w = readout_attention(ro, hidden, node_batch, num_graphs) if isinstance(ro, (layer.GlobalLAPool, layer.GlobalAttention, layer.Set2Set)) else None
     return Explanation(out=out, hidden=hidden, edge_index=edge_index, edge_attention=alphas, atom_sent=sents, readout_attention=w, ptr=sp.ptr)
+
+
+# --------------------------------------------------------------------------------------
+# the pair models: what the fusion pools from
+# --------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class PairExplanation:
+    """What ``explain_pair`` returns.  ``out[P, out_dim]`` the prediction, bit for bit ``screen`` / ``score_pairs``; ``fusion[P, 2 *
+    message_steps]`` the ``[max, mean]`` columns the head saw, step by step; ``contacts``: per step the ``[P, 2]`` int32 rows of the maximum
+    (``return_argmax`` of those calls); ``maps``: per step an ``ops.PairMap`` — side 1 the ligand's atoms (DTI) / the first drug's (DDI),
+    side 2 the residues / the second drug's atoms, ragged and pair-major; ``ptr1`` / ``ptr2`` int32 ``[P + 1]``: the rows of pair ``i`` in
+    the side's vectors."""
+    out: torch.Tensor
+    fusion: torch.Tensor
+    contacts: List[torch.Tensor]
+    maps: list
+    ptr1: torch.Tensor
+    ptr2: torch.Tensor
+
+    CONTENTS = ("max", "mean")
+
+    def per_pair(self, t, side):
+        """``t``, whose first dimension runs over the rows of ``side`` (1 or 2), split into a list of ``P`` tensors."""
+        if side not in (1, 2):
+            raise ValueError(f"per_pair: side must be 1 or 2, got {side!r}")
+        bounds = (self.ptr1 if side == 1 else self.ptr2).to(dtype=torch.int64)
+        sizes = (bounds[1:] - bounds[:-1]).tolist()
+        if t.size(0) != sum(sizes):
+            raise ValueError(f"per_pair: the first dimension ({t.size(0)}) is not the row count of side {side} ({sum(sizes)})")
+        return list(t.split(sizes))
+
+    def weights(self, side, content="max", step=-1):
+        """The per-row ``[R]`` vector a painter would use for ``side`` (1 or 2): ``'max'`` = the row's best score against the partner,
+        ``'mean'`` its mean score, of message step ``step`` (the last by default)."""
+        if side not in (1, 2):
+            raise ValueError(f"weights: side must be 1 or 2, got {side!r}")
+        if content not in self.CONTENTS:
+            raise ValueError(f"Unknown content to visualize: {content!r} (one of {self.CONTENTS})")
+        if not self.maps:
+            raise ValueError("weights: the model has no message step, so no fusion and no map")
+        return getattr(self.maps[step], f"{content}{side}")
+
+
+def explain_pair(model, *args, **kwargs):
+    """Why a pair scored as it did: the scoring call of a two-tower model plus one ``ops.pair_map`` launch per message step ->
+    ``PairExplanation``.  ``eval()`` mode under ``torch.no_grad()``; every refusal of ``screen`` / ``score_pairs`` applies.
+
+    ``ArchitectureDTI``: ``explain_pair(model, data_mol, enc, pro_of_pair=None)`` — ``screen`` on a ``ProteinEncoding`` — or
+    ``explain_pair(model, data_mol, data_pro)`` with one protein graph per ligand (encoded here, then the same path).
+    ``ArchitectureDDI``: ``explain_pair(model, enc, first, second)`` — ``score_pairs`` on a ``DrugEncoding``."""
+    from .model import ArchitectureDDI, ArchitectureDTI
+    if isinstance(model, ArchitectureDTI):
+        return _explain_dti(model, *args, **kwargs)
+    if isinstance(model, ArchitectureDDI):
+        return _explain_ddi(model, *args, **kwargs)
+    raise GlamHipError(f"explain_pair: expected an ArchitectureDTI or ArchitectureDDI, got {type(model).__name__} (explain() takes an Architecture)")
+
+
+def _pair_explanation(out, fusion, contacts, maps, plan):
+    _, ptr1, ptr2 = plan.on(out.device)
+    fusion = torch.cat(fusion, dim=1) if fusion else out.new_zeros(plan.P, 0)
+    return PairExplanation(out=out, fusion=fusion, contacts=contacts, maps=maps, ptr1=ptr1, ptr2=ptr2)
+
+
+def _explain_dti(model, data_mol, enc, pro_of_pair=None):
+    from .model import ProteinEncoding, _host_sizes
+    model._screen_guard("explain_pair")          # (before the batch form's encode_proteins, which would name itself in the refusal)
+    if not isinstance(enc, ProteinEncoding):
+        if not all(hasattr(enc, k) for k in ("x", "edge_index", "edge_attr", "batch")):
+            raise GlamHipError("explain_pair: for an ArchitectureDTI the call is explain_pair(model, data_mol, enc, pro_of_pair=None) on a "
+                               "ProteinEncoding (model.encode_proteins) or explain_pair(model, data_mol, data_pro) on a batch of one protein "
+                               f"graph per ligand, got {type(enc).__name__}")
+        enc = model.encode_proteins(enc)                # one protein graph per ligand: encoded once, then the identity index
+        if pro_of_pair is None:
+            pro_of_pair = range(enc.num_graphs)
+    out, contacts, fusion, rows, msp, index = model._screen("explain_pair", data_mol, enc, pro_of_pair, True)
+    bounds = msp.ptr.cpu().numpy().astype("int64")      # (the ligands' sizes: one read-back, after the pass is enqueued)
+    plan = ops.map_plan(bounds[1:] - bounds[:-1], _host_sizes(enc), None, index)
+    maps = [layer.dot_and_global_pool2_map(x, r, msp, enc.sp, plan) for x, r in zip(rows, enc.rows)]
+    return _pair_explanation(out, fusion, contacts, maps, plan)
+
+
+def _explain_ddi(model, enc, first=None, second=None):
+    from .model import DrugEncoding, _host_sizes
+    model._pairs_guard("explain_pair")
+    if not isinstance(enc, DrugEncoding) or first is None or second is None:
+        raise GlamHipError("explain_pair: for an ArchitectureDDI the call is explain_pair(model, enc, first, second) on a DrugEncoding; two "
+                           "collated batches are not taken — enc = model.encode_drugs(batch) first, then the pairs as two index vectors")
+    out, contacts, fusion, i1, i2 = model._score_pairs("explain_pair", enc, first, second, True)
+    sizes = _host_sizes(enc)
+    plan = ops.map_plan(sizes, sizes, i1, i2)
+    maps = [layer.dot_and_global_pool2_map(r1, r2, enc.sp, enc.sp, plan) for r1, r2 in zip(enc.rows1, enc.rows2)]
+    return _pair_explanation(out, fusion, contacts, maps, plan)

@@ -1210,6 +1210,13 @@ def dot_and_global_pool2_grid(x1, x2, sp1, sp2, plan, rows=None, sum1=None, sum2
     return ops.pair_pool_grid(x1, x2, sp1, sp2, plan, rows, sum1, sum2, return_argmax)
 
 
+def dot_and_global_pool2_map(x1, x2, sp1, sp2, plan):
+    """What ``dot_and_global_pool2`` pools FROM, per row: for every pair of ``plan`` (``ops.map_plan`` over the segments of ``sp1`` /
+    ``sp2``) the best partner row and the mean over the partner's rows, for the rows of both sides (``ops.pair_map`` -> ``ops.PairMap``) —
+    the maps of ``explain.explain_pair``.  Inference only; the rows flow as they are."""
+    return ops.pair_map(x1, x2, sp1, sp2, plan)
+
+
 def dot_and_global_pool2_gather_shared(x1, x2, sp1, sp2, idx1=None, idx2=None, with_identity=False):
     """``dot_and_global_pool2_gather`` for TRAINING: the same forward with a backward (``ops.pair_pool_gather_shared``) — a drug's rows,
     on either side, collect the gradients of every pair that points at it.  ``with_identity`` as in ``dot_and_global_pool2``."""

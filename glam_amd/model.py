@@ -279,6 +279,14 @@ def _shared_index(model, given, P, Q, device, **words):
     return cache[key]
 
 
+def _host_sizes(enc):
+    """``enc.sizes_host``: the row counts of an encoding's segments on the host — ONE read-back of ``sp.ptr`` per encoding, on first use."""
+    if enc.sizes_host is None:
+        ptr = enc.sp.ptr.cpu().numpy().astype("int64")
+        enc.sizes_host = ptr[1:] - ptr[:-1]
+    return enc.sizes_host
+
+
 class ProteinEncoding:
     """What ``ArchitectureDTI.encode_proteins`` keeps of ``Q`` protein graphs for ``screen``: ``rows[s]`` the residue rows after
     message step ``s`` (contiguous, as the fusion reads them), ``sp`` their ``SegmentPtr``, ``flat`` = ``pro_flat(pro_readout(.))``
@@ -304,10 +312,7 @@ class ProteinEncoding:
         key = None if sel is None else tuple(sel.tolist())
         plan = self.plans.get(key)
         if plan is None:
-            if self.sizes_host is None:
-                ptr = self.sp.ptr.cpu().numpy().astype("int64")
-                self.sizes_host = ptr[1:] - ptr[:-1]
-            plan = ops.panel_plan(self.sizes_host, sel)
+            plan = ops.panel_plan(_host_sizes(self), sel)
             while len(self.plans) >= self._MAX_PLANS:
                 self.plans.pop(next(iter(self.plans)))
             self.plans[key] = plan
@@ -395,18 +400,30 @@ class ArchitectureDTI(torch.nn.Module):
         encoded residue rows of that step through the pair -> protein index (``ops.pair_pool_indexed``), ``enc.flat`` is gathered by it.
         ``pro_of_pair``: host integers, one per ligand (``ops.pair_index``); ``None`` when ``enc`` holds one protein.
         ``return_argmax``: also the per-step ``[P, 2]`` int32 contacts (row of ``data_mol.x``, row of the encoded proteins)."""
-        self._screen_guard("screen")
-        _check_encoding(self, "screen", enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
+        out, contacts = self._screen("screen", data_mol, enc, pro_of_pair, return_argmax)[:2]
+        return (out, contacts) if return_argmax else out
+
+    def _screen(self, what, data_mol, enc, pro_of_pair, return_argmax):
+        """``screen`` under the name ``what`` -> ``(out, contacts, fusion, rows, msp, index)``: also the steps' ``[P, 2]`` fusions, the
+        ligand rows every step's fusion read (a step writes new rows: the earlier ones stay), the ligands' ``SegmentPtr`` and the
+        validated index (``explain.explain_pair``)."""
+        self._screen_guard(what)
+        _check_encoding(self, what, enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
         m = _Tower(self, "mol", data_mol)
         msp = ops.segment_ptr(data_mol.batch, m.n)
         index = ops.pair_index(pro_of_pair, msp.B, enc.num_graphs, default="single")       # host-side, before the first launch
+        rows = []
+
+        def fuse(x, i):
+            rows.append(x)
+            return dot_and_global_pool2_indexed(x, enc.rows[i], data_mol.batch, enc.sp, index, return_argmax)
+
         with ops.weight_scope():
-            fusion, contacts = self._ligand_walk(m, return_argmax, lambda x, i: dot_and_global_pool2_indexed(
-                x, enc.rows[i], data_mol.batch, enc.sp, index, return_argmax))
+            fusion, contacts = self._ligand_walk(m, return_argmax, fuse)
             outm = m.flat_out()
             outp = enc.flat.index_select(0, index.on(enc.flat.device))
             out = self.lin_out1(self.lin_out0(ops.cat_cols([outm, outp] + fusion)))
-        return (out, contacts) if return_argmax else out
+        return out, contacts, fusion, rows, msp, index
 
     def _ligand_walk(self, m, return_argmax, fuse):
         """The ligand tower ``m`` against an encoding: ``fuse(rows, step)`` after every step -> the steps' fusions and contacts."""
@@ -559,10 +576,7 @@ class DrugEncoding:
         key = None if sel is None else tuple(sel.tolist())
         plan = self.plans.get(key)
         if plan is None:
-            if self.sizes_host is None:
-                ptr = self.sp.ptr.cpu().numpy().astype("int64")
-                self.sizes_host = ptr[1:] - ptr[:-1]
-            plan = ops.grid_plan(self.sizes_host, sel)
+            plan = ops.grid_plan(_host_sizes(self), sel)
             while len(self.plans) >= self._MAX_PLANS:
                 self.plans.pop(next(iter(self.plans)))
             self.plans[key] = plan
@@ -655,8 +669,14 @@ class ArchitectureDDI(torch.nn.Module):
         pairs of THIS call, as ``model(B1, B2)`` does over its batch: the equality holds per call, for the P pairs of that call (with
         ``end_norm="_LayerNorm"`` a chunk scored alone differs from the same pairs scored inside a longer call).
         ``return_argmax``: also the per-step ``[P, 2]`` int32 contacts (row of ``enc.rows1[s]``, row of ``enc.rows2[s]``)."""
-        self._pairs_guard("score_pairs")
-        _check_encoding(self, "score_pairs", enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
+        out, contacts, _, _, _ = self._score_pairs("score_pairs", enc, first, second, return_argmax)
+        return (out, contacts) if return_argmax else out
+
+    def _score_pairs(self, what, enc, first, second, return_argmax):
+        """``score_pairs`` under the name ``what`` -> ``(out, contacts, fusion, i1, i2)``: the steps' ``[P, 2]`` fusions and the two validated
+        indices kept (``explain.explain_pair``)."""
+        self._pairs_guard(what)
+        _check_encoding(self, what, enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
         Q = enc.num_graphs
         P = ops.pair_count(first)
         i1 = ops.pair_index(first, P, Q, name="first", over="drugs")               # host-side, before the first launch
@@ -673,7 +693,7 @@ class ArchitectureDDI(torch.nn.Module):
         o2 = enc.flat2.index_select(0, i2.on(dev))
         with ops.weight_scope():
             out = self.lin_out1(self.lin_out0(ops.cat_cols([o1, o2] + fusion)))
-        return (out, contacts) if return_argmax else out
+        return out, contacts, fusion, i1, i2
 
     # ---- the whole table: every selected drug (tower 1) against every selected drug (tower 2) ---------------------------------
     # The head's hidden matrix is [pairs, e_dim]: at 2 000 x 2 000 drugs and e_dim = 1 024 it would be 16 GB in one piece.  The head

@@ -8,6 +8,8 @@ writes, ``pair_count`` is "P of whichever index is given", and a Function that h
 ``_alias_bwd`` under a wrapper that ends in ``_apply_aliasing``."""
 from __future__ import annotations
 
+import dataclasses
+
 import numpy as np
 import torch
 
@@ -696,6 +698,121 @@ def pair_pool_gather_shared(x1, x2, sp1, sp2, idx1=None, idx2=None, with_identit
     i2 = pair_index(idx2, P, sp2.B, name="idx2", over="segments of x2")
     # (no add_width: glam_pair_pool_gather_bwd adds inside its launch for every width of its table)
     return _apply_aliasing(_PairPoolGatherShared, (x1, x2, sp1, sp2, i1, i2, idx1 is None, idx2 is None), x1, x2, with_identity)
+
+
+# --------------------------------------------------------------------------------------
+# interaction maps: per-row marginals of every pair's score matrix, both sides from one launch (csrc/pairmap.hip, glam_pair_map_fwd)
+# --------------------------------------------------------------------------------------
+MAP_CHUNK = 64        # owner rows per work item (one per lane of the wave that holds them) = kMapChunk of csrc/pairmap.hip
+
+
+class MapPlan(_Staged):
+    """The work of one map call over two validated indices (``None`` = identity): pair ``i`` is segment ``a = idx1[i]`` of the first side
+    against segment ``b = idx2[i]`` of the second.  ``out_ptr1`` / ``out_ptr2`` int32 ``[P + 1]``: the offsets of the pairs' rows in the
+    ragged, pair-major outputs of side 1 / side 2 (the cumulative sizes through the indices; ``R1`` / ``R2`` rows in all).  ``work`` int32
+    ``[n_items, 4]``: per item ``(a, b, 2 * chunk + side, first output row of the chunk)`` — the owner rows ``64 * chunk .. 64 * chunk + 63``
+    of segment ``a`` (side 0) or ``b`` (side 1); every owner row of every pair is in exactly one item, a pair's items are consecutive
+    (side 0 first; ``pair_of_item`` int32 ``[n_items]`` names it, host only), and a pair whose partner segment is empty keeps its items:
+    the kernel fills their rows.  ``Q1`` / ``Q2`` / ``N1`` /
+    ``N2``: the segments and rows the sizes spoke of.  Host numpy; ``on(device)`` -> ``(work, out_ptr1, out_ptr2)`` on the device, made
+    once per device (one copy out of pinned memory, only enqueued) and shared by every launch that reads them."""
+
+    def __init__(self, sizes1, sizes2, a, b):
+        self.P, self.Q1, self.Q2 = int(a.shape[0]), int(sizes1.shape[0]), int(sizes2.shape[0])
+        self.N1, self.N2 = int(sizes1.sum()), int(sizes2.sum())
+        n = (sizes1[a], sizes2[b])                                                   # rows per pair and side
+        out_ptr = [np.zeros(self.P + 1, dtype=np.int64), np.zeros(self.P + 1, dtype=np.int64)]
+        for side in (0, 1):
+            np.cumsum(n[side], out=out_ptr[side][1:])
+        self.R1, self.R2 = int(out_ptr[0][-1]), int(out_ptr[1][-1])
+        n_chunks = [(n[side] + MAP_CHUNK - 1) // MAP_CHUNK for side in (0, 1)]       # per pair
+        self.n_items = int(n_chunks[0].sum() + n_chunks[1].sum())
+        if max(self.N1, self.N2, self.R1, self.R2, self.n_items) >= 2 ** 31 - 1:
+            raise IndexError("map_plan: the segments, the outputs or the work table hold 2^31 rows or more")
+        parts = []
+        for side in (0, 1):
+            first = np.cumsum(n_chunks[side]) - n_chunks[side]
+            i = np.repeat(np.arange(self.P, dtype=np.int64), n_chunks[side])
+            c = np.arange(i.shape[0], dtype=np.int64) - first[i]                     # chunk inside its segment
+            parts.append(np.stack([i, a[i], b[i], 2 * c + side, out_ptr[side][i] + MAP_CHUNK * c], axis=1))
+        table = np.concatenate(parts)
+        table = table[np.argsort(table[:, 0], kind="stable")]                       # pair-major: a pair's two sides run side by side
+        self.pair_of_item = table[:, 0].astype(np.int32)
+        self.work = np.ascontiguousarray(table[:, 1:], dtype=np.int32)
+        self.out_ptr1, self.out_ptr2 = out_ptr[0].astype(np.int32), out_ptr[1].astype(np.int32)
+        _Staged.__init__(self, "the map's work table and output offsets", self.work.reshape(-1),
+                         np.concatenate([self.out_ptr1, self.out_ptr2]))
+
+    def on(self, device):
+        work, out_ptr = _Staged.on(self, device)
+        return work, out_ptr[:self.P + 1], out_ptr[self.P + 1:]
+
+
+def map_plan(sizes1_host, sizes2_host, idx1=None, idx2=None):
+    """``MapPlan`` of the pairs ``(idx1[i], idx2[i])`` over ``Q1 = len(sizes1_host)`` first-side segments of ``sizes1_host[q]`` rows and
+    ``Q2 = len(sizes2_host)`` second-side ones — host only (numpy), before anything is launched (the kernel trusts the table; the policy
+    of ``pair_index`` / ``grid_plan``).  ``idx1`` / ``idx2``: see ``pair_index`` — host integers, any order, duplicates allowed; ``None`` =
+    identity on that side (needs ``Q == P``); ``P`` is the length of whichever is given.  ``IndexError`` for a wrong length or dtype or an
+    entry outside the range; a device tensor is refused (validating it would be a hidden read-back)."""
+    sizes = [host_ints(s, "sizes", None, wrong=f"map_plan: the sizes of side {k} must be a vector of non-negative integers",
+                       on_device=f"map_plan: the sizes of side {k} live on a device: the plan is built on the host — pass their host copy")
+             .astype(np.int64) for k, s in ((1, sizes1_host), (2, sizes2_host))]
+    Q1, Q2 = int(sizes[0].shape[0]), int(sizes[1].shape[0])
+    P = pair_count(idx1, idx2, Q1)
+    a = pair_index(idx1, P, Q1, name="idx1", over="segments of x1").host.astype(np.int64)
+    b = pair_index(idx2, P, Q2, name="idx2", over="segments of x2").host.astype(np.int64)
+    return MapPlan(sizes[0], sizes[1], a, b)
+
+
+@dataclasses.dataclass
+class PairMap:
+    """What ``pair_map`` returns, ragged and pair-major.  Side 1 (``[R1]``, the rows of pair ``i`` at ``out_ptr1[i] : out_ptr1[i + 1]``): per
+    row ``r1`` of the pair's first segment ``max1`` = the largest score of the row, ``arg1`` int32 = the row of ``x2`` of the first partner row
+    that attains it, ``mean1`` = the mean of the row's scores.  Side 2 (``[R2]``, ``out_ptr2``): the same per row of the second segment, ``arg2``
+    a row of ``x1``.  An empty partner: 0, -1, 0.  ``out_ptr1`` / ``out_ptr2``: int32 ``[P + 1]`` on the device."""
+    max1: torch.Tensor
+    arg1: torch.Tensor
+    mean1: torch.Tensor
+    max2: torch.Tensor
+    arg2: torch.Tensor
+    mean2: torch.Tensor
+    out_ptr1: torch.Tensor
+    out_ptr2: torch.Tensor
+
+
+def pair_map(x1, x2, sp1, sp2, plan):
+    """The two marginals of ``S = x1[seg_a] @ x2[seg_b].T`` for every pair of ``plan`` (``map_plan`` over the sizes of ``sp1``'s and
+    ``sp2``'s segments) -> ``PairMap``: per row of the first segment the best partner row and the mean over the partner's rows, per row
+    of the second the same the other way — ``S`` is never stored, both sides come from ONE launch.  A score is the fmaf chain of
+    ``pair_pool_gather``: the largest ``max1`` (or ``max2``) of a pair is bit for bit its max column, and the first row that holds it
+    with its ``arg1`` is its argmax.  Ties go to the smallest partner row.  The means are the same bits on every run and within the
+    fp64-twin bound.  Widths 1..128.  Inference only: there is no backward."""
+    if not isinstance(plan, MapPlan):
+        raise GlamHipError("pair_map: plan must come from ops.map_plan (the kernel trusts its table)")
+    if torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
+        raise GlamHipError("pair_map is inference only (no backward): call it under torch.no_grad(); the training route is "
+                           "ops.pair_pool on one graph per pair and side")
+    if (plan.Q1, plan.N1, plan.Q2, plan.N2) != (sp1.B, sp1.N, sp2.B, sp2.N):
+        raise GlamHipError(f"pair_map: the plan was made for {plan.Q1} segments of {plan.N1} rows against {plan.Q2} of {plan.N2}, the "
+                           f"operands hold {sp1.B} of {sp1.N} against {sp2.B} of {sp2.N}")
+    x1, x2 = _operands("pair_map", x1, x2, sp1, sp2, "x1", "x2")
+    D, dev = x1.size(1), x1.device
+    if not 1 <= D <= 128:
+        raise GlamHipError(f"pair_map: width {D} is outside the kernel table (1..128)")
+    work, out_ptr1, out_ptr2 = plan.on(dev)
+    # (never an empty buffer: it has no address, and a call whose owner rows all sit on ONE side still launches — for the fills)
+    bufs = [(torch.empty(max(R, 1), dtype=torch.float32, device=dev), torch.empty(max(R, 1), dtype=torch.int32, device=dev),
+             torch.empty(max(R, 1), dtype=torch.float32, device=dev)) for R in (plan.R1, plan.R2)]
+    sides = [tuple(t[:R] for t in side) for side, R in zip(bufs, (plan.R1, plan.R2))]
+    if plan.n_items and (sp1.N == 0 or sp2.N == 0):      # no row on one side: every partner is empty (and the empty matrix has no address to pass)
+        for mx, arg, mean in sides:
+            mx.zero_()
+            arg.fill_(-1)
+            mean.zero_()
+    elif plan.n_items:
+        _lib.api().glam_pair_map_fwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(work), plan.n_items, D,
+                                     *[ptr(t) for side in bufs for t in side], stream())
+    return PairMap(*sides[0], *sides[1], out_ptr1, out_ptr2)
 
 
 # --------------------------------------------------------------------------------------

@@ -687,6 +687,20 @@ int glam_pair_pool_grid_fwd(const float* x1, const float* x2, const int32_t* ptr
                             int64_t Q2, int D, const float* sum1, const float* sum2, int slab, float* out, int32_t* argmax,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* Interaction maps (inference): both marginals of the score matrix S = x1[seg a] @ x2[seg b]^T of every listed pair, S never stored
+ * (csrc/pairmap.hip).  work int32[n_items,4]: per item (a, b, 2 * chunk + side, first output row of the chunk) — a wave takes the owner
+ * rows 64 * chunk .. 64 * chunk + 63 of segment a of x1 (side 0; ptr1 int32[Q1+1]) or of segment b of x2 (side 1; ptr2 int32[Q2+1]) and
+ * streams the whole other segment past them; built and checked by the caller (every owner row of every pair in exactly one item, output
+ * rows pair-major per side), trusted here.  Per owner row, at its output row of its side's arrays: max f32 = the largest score of the
+ * row, arg int32 = the row (of the OTHER matrix) of the first partner row that attains it, mean f32 = the sum of the row's scores in
+ * ascending partner order over the partner's row count; an empty partner segment gives 0, -1, 0.  A score is the one ascending fmaf chain
+ * of glam_pair_pool_gather_fwd: the largest max of a pair's rows, on either side, is bit for bit that call's max column and the first
+ * row that holds it with its arg is that call's argmax.  ONE launch for both sides, no workspace; 16-byte loads when D % 4 == 0 and x1,
+ * x2 are 16-byte aligned, dwords otherwise.  D in 1..128, else GLAM_E_UNSUPPORTED; a null pointer with n_items > 0: GLAM_E_INVALID;
+ * n_items == 0: GLAM_OK, nothing launched, no pointer looked at.  Forward only. */
+int glam_pair_map_fwd(const float* x1, const float* x2, const int32_t* ptr1, const int32_t* ptr2, const int32_t* work, int64_t n_items,
+                      int D, float* max1, int32_t* arg1, float* mean1, float* max2, int32_t* arg2, float* mean2, void* stream);
+
 /* Factored pair head (inference): the two linear layers of the pair models' head over a TABLE of R x Cs pairs, for a head without norms
  * and with an elementwise activation (csrc/pairhead.hip):
  *   out[i,j,o] = b1[o] + sum_e w1[o,e] * act(A[i,e] + B[j,e] + sum_k W0[e, 2 hid + k] * f[i,j,k])

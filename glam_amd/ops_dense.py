@@ -401,9 +401,9 @@ class _LinearTall(torch.autograd.Function):
             ctx.set_materialize_grads(False)     # the carry of the LAST application has no gradient yet: None, not a zero fill
         N, K = x.shape
         M = w.size(0)
-        ctx.fold = bool(celu_in) and K <= 96 and M <= 288 and K + 1 <= 128 and N > 0      # every product has a CELU-aware kernel
-        if celu_in and not ctx.fold:
-            x = torch.celu(x)
+        ctx.fold = bool(celu_in)
+        if ctx.fold and not _celu_folds(N, K, M):      # (a CELU applied in here would have no backward: _linear_tall_node applies it in front)
+            raise GlamHipError("_LinearTall: celu_in outside the CELU-aware kernels' shapes")
         ctx.save_for_backward(x, w)
         if K <= 96 and M <= 320:       # 92 -> 276: k_tall_x3<3, 4, 5> (15 us at N = 20.4 k; the library 29, the fp32 LDS-image kernel 24)
             lib = _lib.api()
@@ -477,9 +477,16 @@ class _LinearTall(torch.autograd.Function):
         return dx, dwb[:, :K], dwb[:, K], None, None, None
 
 
+def _celu_folds(N, K, M):
+    """Every product of ``_LinearTall`` has a CELU-aware kernel for this shape."""
+    return K <= 96 and M <= 288 and K + 1 <= 128 and N > 0
+
+
 def _linear_tall_node(x, w, b, celu_in=False):
     """``_LinearTall`` with the gradients of (w, b) carried across the applications of a block inside a weight_scope."""
     M, K = w.shape
+    if celu_in and not _celu_folds(x.size(0), K, M):
+        x, celu_in = torch.celu(x), False      # an op of its own, so that ``celu'`` reaches the gradient of the raw input
     carry = _o._Carry(("carry-lintall", id(w), id(b)), (w, b), ((M, K), (M,)))      # [d_w (M x K) | d_b (M)]: two contiguous pieces
     if carry.tensor is None:
         return _LinearTall.apply(x, w, b, None, celu_in)
@@ -489,7 +496,8 @@ def _linear_tall_node(x, w, b, celu_in=False):
 
 
 def linear_tall_supported(K, M):
-    return K % 4 == 0 and M % 4 == 0 and M <= 320 and K + 1 <= 128
+    # (K = 64: the ones column of ``[x | 1]`` would be a column chunk of its own, which ``glam_wgrad_gemm_linear`` does not take)
+    return K % 4 == 0 and M % 4 == 0 and M <= 320 and K + 1 <= 128 and K != 64
 
 
 class _LinearNarrow(torch.autograd.Function):

@@ -115,11 +115,14 @@ typedef __attribute__((address_space(4))) const float glam_cf1;
 typedef __attribute__((address_space(4))) const glam_v4f glam_cv4;
 // ... through p, which every lane of the wave holds alike, said so to the compiler (its loads then go to the scalar unit whatever the
 // analysis finds)
-__device__ __forceinline__ const float* uniform_ptr(const float* p) {
+__device__ __forceinline__ glam_cf1* uniform_cf1(const float* p) {
     const uintptr_t v = (uintptr_t)p;
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (const float*)(((uintptr_t)hi << 32) | lo);
+    return (glam_cf1*)(((uintptr_t)hi << 32) | lo);
 }
+// The order of the pair fusions' maximum (pairpool_kernels.h, pairstream.h): the larger value, and of equal values the smaller flattened
+// index r1 * n2 + r2.  (value, index) is then a TOTAL order, so the maximum and its argmax do not depend on the order of a reduction.
+__device__ __forceinline__ bool pair_better(float v, int ix, float best, int bidx) { return v > best || (v == best && ix < bidx); }
 // base + 32-bit BYTE offset: lets the compiler use the scalar-base + 32-bit-VGPR-offset addressing mode instead of
 // 64-bit pointer arithmetic on the vector ALU (the hosts check that every tensor stays below 4 GiB)
 __device__ __forceinline__ float4 ld4o(const float* base, unsigned byte_off) {

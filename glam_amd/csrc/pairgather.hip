@@ -13,23 +13,15 @@
 //       limit — plus a write -> read ordering inside the wave to argue about; the scalar route has neither, and a drug that many
 //       pairs reference stays in the scalar cache.  Its price is that the row width must be a compile-time constant, or the loads would
 //       sit behind per-chunk guards and each would expose its latency: the kernel is instantiated per width (D = 1..128).
-// Maximum: every score is ONE fmaf chain over channels 0 .. D-1 in ascending order from 0.f — the chain of k_pair_max_partial and
-// k_pair_pool_fwd — and ties go to the smallest flattened index r1 * n2 + r2 (better() there), which makes (value, index) a total
-// order: the max column and the argmax are bit for bit those of glam_pair_pool_fwd on physically gathered rows whatever the order of
-// the reduction.  Mean: sum(S) = <sum of rows of segment 1, sum of rows of segment 2>; lane c keeps columns c and c + 64 of both sums
-// (rows added in ascending order), the products are summed by the fixed butterfly of group_sum<64>: the same bits on every run.
+// Maximum: the chain of stream_score2 (pairstream.h) and the total order of pair_better (common.h): the max column and the argmax are
+// bit for bit those of glam_pair_pool_fwd on physically gathered rows whatever the order of the reduction.
+// Mean: sum(S) = <sum of rows of segment 1, sum of rows of segment 2>; lane c keeps columns c and c + 64 of both sums (rows added in
+// ascending order), the products are summed by the fixed butterfly of group_sum<64>: the same bits on every run.
 // Training (glam_pair_pool_gather_train_fwd): the same kernel also stores those two column sums (sums[i] = [s1 | s2]) for the backward of
 // pairgather_bwd.hip — a runtime pointer, NULL in the inference call, not a second template axis.
-#include <utility>
-
-#include "common.h"
+#include "pairstream.h"
 
 namespace glam {
-
-constexpr int kGatherPairs = kBlock / 64;      // pairs (waves) per block
-constexpr int kGatherMaxD = 128;
-
-__device__ __forceinline__ bool gather_better(float v, int ix, float best, int bidx) { return v > best || (v == best && ix < bidx); }
 
 // column c of the sums of rows [m0, m0 + n1) of x1 and [p0, p0 + n2) of x2, rows in ascending order.  Both segments go eight rows a
 // round, sixteen loads in flight; a row past the end of a segment is read from the segment's last row (in bounds) and adds 0.  (On
@@ -62,9 +54,8 @@ __global__ void __launch_bounds__(kBlock) k_pair_gather(const float* __restrict_
                                                        const int* __restrict__ ptr1, const int* __restrict__ ptr2,
                                                        const int* __restrict__ idx1, const int* __restrict__ idx2, int P,
                                                        float* __restrict__ out, int* __restrict__ arg, float* __restrict__ sums) {
-    static_assert(D >= 1 && D <= kGatherMaxD && (!kVec || D % 4 == 0), "k_pair_gather: width");
     const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * kGatherPairs + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int i = blockIdx.x * kStreamWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (i >= P) return;                                   // a wave without a pair (no barrier below: the others go on)
     const int a = idx1 ? idx1[i] : i, b = idx2 ? idx2[i] : i;
     const int m0 = __builtin_amdgcn_readfirstlane(ptr1[a]), n1 = __builtin_amdgcn_readfirstlane(ptr1[a + 1]) - m0;
@@ -98,47 +89,22 @@ __global__ void __launch_bounds__(kBlock) k_pair_gather(const float* __restrict_
         const bool valid = r2 < n2;
         const float* prow = x2 + (size_t)(p0 + (valid ? r2 : 0)) * D;      // (a lane past the end reads row 0 and drops its scores)
         float pr[D];
-        if constexpr (kVec) {
-#pragma unroll
-            for (int u = 0; u < D / 4; ++u) {
-                const float4 v = ld4g(prow + 4 * u);
-                pr[4 * u] = v.x; pr[4 * u + 1] = v.y; pr[4 * u + 2] = v.z; pr[4 * u + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < D; ++c) pr[c] = ld1g(prow + c);
-        }
+        stream_owner_row<D, kVec>(prow, pr);
         for (int r1 = 0; r1 < n1; r1 += 2) {
             const bool two = r1 + 1 < n1;                  // (an odd last row is scored twice and counted once)
-            const float* q0 = uniform_ptr(x1 + (size_t)(m0 + r1) * D);
-            const float* q1 = q0 + (two ? D : 0);
-            float d0 = 0.f, d1 = 0.f;
-            if constexpr (kVec) {
-#pragma unroll
-                for (int u = 0; u < D / 4; ++u) {
-                    const glam_v4f v0 = ((glam_cv4*)q0)[u], v1 = ((glam_cv4*)q1)[u];
-                    d0 = fmaf(v0.x, pr[4 * u], d0); d0 = fmaf(v0.y, pr[4 * u + 1], d0); d0 = fmaf(v0.z, pr[4 * u + 2], d0); d0 = fmaf(v0.w, pr[4 * u + 3], d0);
-                    d1 = fmaf(v1.x, pr[4 * u], d1); d1 = fmaf(v1.y, pr[4 * u + 1], d1); d1 = fmaf(v1.z, pr[4 * u + 2], d1); d1 = fmaf(v1.w, pr[4 * u + 3], d1);
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < D; ++c) {
-                    d0 = fmaf(((glam_cf1*)q0)[c], pr[c], d0);
-                    d1 = fmaf(((glam_cf1*)q1)[c], pr[c], d1);
-                }
-            }
+            const auto [d0, d1] = stream_score2<D, kVec>(x1 + (size_t)(m0 + r1) * D, two, pr);
             // (selects, not a branch on `valid`: under a divergent branch the row loads above would stop being wave-uniform)
             const float s0 = valid ? d0 : -INFINITY, s1 = valid && two ? d1 : -INFINITY;
             const int i0 = valid ? r1 * n2 + r2 : 0x7fffffff, i1 = valid && two ? i0 + n2 : 0x7fffffff;
-            if (gather_better(s0, i0, best, bidx)) { best = s0; bidx = i0; }
-            if (gather_better(s1, i1, best, bidx)) { best = s1; bidx = i1; }
+            if (pair_better(s0, i0, best, bidx)) { best = s0; bidx = i0; }
+            if (pair_better(s1, i1, best, bidx)) { best = s1; bidx = i1; }
         }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float v = __shfl_xor(best, o, 64);
         const int ix = __shfl_xor(bidx, o, 64);
-        if (gather_better(v, ix, best, bidx)) { best = v; bidx = ix; }
+        if (pair_better(v, ix, best, bidx)) { best = v; bidx = ix; }
     }
     if (lane == 0) {
         out[2 * (size_t)i] = best;
@@ -147,19 +113,7 @@ __global__ void __launch_bounds__(kBlock) k_pair_gather(const float* __restrict_
     }
 }
 
-typedef void (*gather_kernel)(const float*, const float*, const int*, const int*, const int*, const int*, int, float*, int*, float*);
-
-// [D - 1] -> the dword instantiation of width D;  [D / 4 - 1] -> the 16-byte one
-template <int... I>
-static const gather_kernel* gather_dword_table(std::integer_sequence<int, I...>) {
-    static const gather_kernel t[] = {k_pair_gather<I + 1, false>...};
-    return t;
-}
-template <int... I>
-static const gather_kernel* gather_vec_table(std::integer_sequence<int, I...>) {
-    static const gather_kernel t[] = {k_pair_gather<4 * (I + 1), true>...};
-    return t;
-}
+struct GatherKernel { template <int D, bool kVec> static constexpr auto get() { return &k_pair_gather<D, kVec>; } };
 
 }  // namespace glam
 
@@ -167,8 +121,8 @@ using namespace glam;
 
 // bytes per load of a call with these matrices: 16 (D % 4 == 0 and both 16-byte aligned), 4 otherwise, 0: D outside the kernel table
 extern "C" size_t glam_pair_pool_gather_load_bytes(const float* x1, const float* x2, int D) {
-    if (D <= 0 || D > kGatherMaxD) return 0;
-    return (D & 3) == 0 && aligned16(x1) && aligned16(x2) ? 16 : 4;
+    if (D <= 0 || D > kStreamMaxD) return 0;
+    return stream_vec(D, x1, x2) ? 16 : 4;
 }
 
 // the two entry points: sums == NULL is the inference call (the bits of the kernel before it took the pointer), sums != NULL training
@@ -177,18 +131,16 @@ static int gather_launch(const char* who, const float* x1, const float* x2, cons
                          bool training, void* stream) {
     GLAM_REQUIRE(P >= 0 && P < INT32_MAX, "%s: P out of range", who);
     GLAM_REQUIRE(Q1 >= 0 && Q1 < INT32_MAX && Q2 >= 0 && Q2 < INT32_MAX, "%s: Q1 / Q2 out of range", who);
-    if (D <= 0 || D > kGatherMaxD) return fail(GLAM_E_UNSUPPORTED, "%s: D=%d not in 1..%d", who, D, kGatherMaxD);
+    if (D <= 0 || D > kStreamMaxD) return fail(GLAM_E_UNSUPPORTED, "%s: D=%d not in 1..%d", who, D, kStreamMaxD);
     if (P == 0) return GLAM_OK;
     GLAM_REQUIRE(Q1 > 0 && Q2 > 0, "%s: pairs but no segment on one side", who);
     GLAM_REQUIRE(idx1 || Q1 == P, "%s: idx1 = NULL pairs i with segment i of x1: needs Q1 == P", who);
     GLAM_REQUIRE(idx2 || Q2 == P, "%s: idx2 = NULL pairs i with segment i of x2: needs Q2 == P", who);
     GLAM_REQUIRE(x1 && x2 && ptr1 && ptr2 && out && (!training || (argmax && sums)), "%s: null pointer", who);
     GLAM_REQUIRE(((uintptr_t)x1 & 3u) == 0 && ((uintptr_t)x2 & 3u) == 0 && ((uintptr_t)sums & 3u) == 0, "%s: rows must be 4-byte aligned", who);
-    const gather_kernel k = glam_pair_pool_gather_load_bytes(x1, x2, D) == 16
-                                ? gather_vec_table(std::make_integer_sequence<int, kGatherMaxD / 4>())[D / 4 - 1]
-                                : gather_dword_table(std::make_integer_sequence<int, kGatherMaxD>())[D - 1];
+    const auto k = stream_kernel<GatherKernel>(D, x1, x2);
     GLAM_PROF_LABEL("k_pair_gather");
-    hipLaunchKernelGGL(k, dim3((unsigned)((P + kGatherPairs - 1) / kGatherPairs)), dim3(kBlock), 0, (hipStream_t)stream, x1, x2, ptr1,
+    hipLaunchKernelGGL(k, dim3((unsigned)((P + kStreamWaves - 1) / kStreamWaves)), dim3(kBlock), 0, (hipStream_t)stream, x1, x2, ptr1,
                        ptr2, idx1, idx2, (int)P, out, argmax, sums);
     GLAM_LAUNCH_CHECK(who);
     return GLAM_OK;

@@ -10,7 +10,7 @@
 //       consecutive whole segments share a chunk while their rows fit in the 64 lanes; a segment of more than 64 rows closes the running
 //       chunk and takes ceil(n / 64) slices of its own (its last slice is not shared); an empty segment takes no lane;
 //   the slab's first-side segments are streamed past, their rows two a round through WAVE-UNIFORM loads (the constant address space,
-//       panel_uniform's route: the scalar unit fetches a row once per wave, every multiply-add takes it as its scalar operand);
+//       the route of stream_score2, pairstream.h);
 //   the four waves of a block take four CONSECUTIVE chunks against the same slab.  The waves never meet: no LDS, no block barrier, no
 //       atomics.
 // So the segment a lane belongs to, its row inside that segment (b), the segment's size (n2) and the partial its best goes to are PER
@@ -23,42 +23,16 @@
 //   partials (one per whole segment, ceil(n / 64) for a sliced one, none for an empty one).  Lanes of one partial are contiguous.
 // Per first-side segment the lanes' best (value, flattened index r1 * n2 + b OF THE LANE'S OWN SEGMENT) is reduced WITHIN each run of
 // lanes that share a partial — six __shfl_down steps, each combining only with a partner of the same partial — and the first lane of a
-// run stores ONE 8-byte partial to the workspace [partial][R].  k_pair_grid_finish — one thread per (i, j) — combines a selection's
-// partials in ascending order and forms the mean.
-// Maximum: every score is ONE fmaf chain over channels 0 .. D-1 in ascending order from 0.f — the chain of k_pair_gather and
-// k_pair_panel — and ties go to the smallest flattened index, which makes (value, index) a total order: the max column and the argmax
-// are bit for bit those of glam_pair_pool_gather_fwd on the pair (rows[i], cols[j]) whatever the packing, the slab and the order of the
-// reduction.  Mean: <sum1[a], sum2[q]> / (n1 n2), the chain of k_pair_panel_finish.
-#include <algorithm>
-#include <utility>
-
-#include "common.h"
+// run stores ONE 8-byte partial to the workspace [partial][R].  k_pair_stream_finish (pairstream.h) — one thread per (i, j) — combines a
+// selection's partials in ascending order and forms the mean.
+// Maximum: the chain of stream_score2 and the total order of pair_better: the max column and the argmax are bit for bit those of
+// glam_pair_pool_gather_fwd on the pair (rows[i], cols[j]) whatever the packing, the slab and the order of the reduction.
+// Mean: <sum1[a], sum2[q]> / (n1 n2), the panel's.
+#include "pairstream.h"
 
 namespace glam {
 
-constexpr int kGridWaves = kBlock / 64;        // chunks (waves) per block
-constexpr int kGridChunk = 64;                 // second-side rows per chunk: one per lane
-constexpr int kGridMaxD = 128;
 constexpr int kGridLane = 4;                   // int32 per lane of the table: row, b, n2, partial
-constexpr int kGridTargetWaves = 4096;         // automatic slab: 256 CUs x 4 SIMDs x 4 waves (the panel's rule, untuned here)
-constexpr int kGridMinSlab = 4;
-
-typedef __attribute__((address_space(4))) const float grid_cf1;          // wave-uniform reads of data no launch of this file writes
-typedef __attribute__((address_space(4))) const glam_v4f grid_cv4;
-
-struct GridPartial {       // one (first-side segment, partial): 8 bytes, written by one vector store
-    float v;
-    int ix;
-};
-
-// p, which every lane of the wave holds alike, said so to the compiler (its loads then go to the scalar unit whatever the analysis finds)
-__device__ __forceinline__ const float* grid_uniform(const float* p) {
-    const uintptr_t v = (uintptr_t)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (const float*)(((uintptr_t)hi << 32) | lo);
-}
-
-__device__ __forceinline__ bool grid_better(float v, int ix, float best, int bidx) { return v > best || (v == best && ix < bidx); }
 
 // kVec: D % 4 == 0 and both matrices 16-byte aligned (16-byte loads); otherwise dword loads.  work and rows are trusted.
 // grid: ceil(total_chunks / 4) * n_slabs blocks, the chunk block fastest.
@@ -66,15 +40,13 @@ template <int D, bool kVec>
 __global__ void __launch_bounds__(kBlock) k_pair_grid(const float* __restrict__ x1, const float* __restrict__ x2,
                                                      const int* __restrict__ ptr1, const int* __restrict__ rows, int R,
                                                      const int* __restrict__ work, int total_chunks, int chunk_blocks, int slab,
-                                                     GridPartial* __restrict__ ws) {
-    static_assert(D >= 1 && D <= kGridMaxD && (!kVec || D % 4 == 0), "k_pair_grid: width");
-    static_assert(kGridChunk == 64, "k_pair_grid: one second-side row of a chunk per lane of the wave");
+                                                     PairPartial* __restrict__ ws) {
     const int lane = threadIdx.x & 63;
     const int cb = blockIdx.x % chunk_blocks, s = blockIdx.x / chunk_blocks;
-    const int w = cb * kGridWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int w = cb * kStreamWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (w >= total_chunks) return;                        // a wave without a chunk (no barrier below: the others go on)
     // ---- this lane's entry of the table: PER LANE, not per wave ----
-    const int* e = work + ((size_t)w * kGridChunk + lane) * kGridLane;
+    const int* e = work + ((size_t)w * kStreamChunk + lane) * kGridLane;
     const int row = e[0], b = e[1], n2 = e[2], pid = e[3];
     const bool valid = pid >= 0;                          // (an idle lane holds the row of lane 0 and drops its scores)
     const int before = __shfl_up(pid, 1, 64);
@@ -82,16 +54,7 @@ __global__ void __launch_bounds__(kBlock) k_pair_grid(const float* __restrict__ 
     // ---- the lane's second-side row, for the whole slab ----
     const float* prow = x2 + (size_t)row * D;
     float pr[D];
-    if constexpr (kVec) {
-#pragma unroll
-        for (int u = 0; u < D / 4; ++u) {
-            const float4 v = ld4g(prow + 4 * u);
-            pr[4 * u] = v.x; pr[4 * u + 1] = v.y; pr[4 * u + 2] = v.z; pr[4 * u + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < D; ++c) pr[c] = ld1g(prow + c);
-    }
+    stream_owner_row<D, kVec>(prow, pr);
     const int i1 = (int)min((int64_t)R, (int64_t)(s + 1) * slab);
     for (int i = s * slab; i < i1; ++i) {
         const int a = rows ? __builtin_amdgcn_readfirstlane(rows[i]) : i;
@@ -101,28 +64,12 @@ __global__ void __launch_bounds__(kBlock) k_pair_grid(const float* __restrict__ 
         // The first-side rows are read through the constant address space: NOTHING in this launch writes x1 (the launch writes ws only).
         for (int r1 = 0; r1 < n1; r1 += 2) {
             const bool two = r1 + 1 < n1;                  // (an odd last row is scored twice and counted once)
-            const float* q0 = grid_uniform(x1 + (size_t)(m0 + r1) * D);
-            const float* q1 = q0 + (two ? D : 0);
-            float d0 = 0.f, d1 = 0.f;
-            if constexpr (kVec) {
-#pragma unroll
-                for (int u = 0; u < D / 4; ++u) {
-                    const glam_v4f v0 = ((grid_cv4*)q0)[u], v1 = ((grid_cv4*)q1)[u];
-                    d0 = fmaf(v0.x, pr[4 * u], d0); d0 = fmaf(v0.y, pr[4 * u + 1], d0); d0 = fmaf(v0.z, pr[4 * u + 2], d0); d0 = fmaf(v0.w, pr[4 * u + 3], d0);
-                    d1 = fmaf(v1.x, pr[4 * u], d1); d1 = fmaf(v1.y, pr[4 * u + 1], d1); d1 = fmaf(v1.z, pr[4 * u + 2], d1); d1 = fmaf(v1.w, pr[4 * u + 3], d1);
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < D; ++c) {
-                    d0 = fmaf(((grid_cf1*)q0)[c], pr[c], d0);
-                    d1 = fmaf(((grid_cf1*)q1)[c], pr[c], d1);
-                }
-            }
+            const auto [d0, d1] = stream_score2<D, kVec>(x1 + (size_t)(m0 + r1) * D, two, pr);
             // (selects, not a branch on `valid`: under a divergent branch the row loads above would stop being wave-uniform)
             const float s0 = valid ? d0 : -INFINITY, s1 = valid && two ? d1 : -INFINITY;
             const int i0 = valid ? r1 * n2 + b : 0x7fffffff, ix1 = valid && two ? i0 + n2 : 0x7fffffff;     // the lane's OWN segment
-            if (grid_better(s0, i0, best, bidx)) { best = s0; bidx = i0; }
-            if (grid_better(s1, ix1, best, bidx)) { best = s1; bidx = ix1; }
+            if (pair_better(s0, i0, best, bidx)) { best = s0; bidx = i0; }
+            if (pair_better(s1, ix1, best, bidx)) { best = s1; bidx = ix1; }
         }
         // segmented reduction: after the step of offset o a lane holds the best of lanes [lane, lane + 2 o) of its own run (runs are
         // contiguous: a partner of the same partial means every lane in between is of it too); a run's first lane ends with the run's
@@ -131,61 +78,16 @@ __global__ void __launch_bounds__(kBlock) k_pair_grid(const float* __restrict__ 
             const float v = __shfl_down(best, o, 64);
             const int ix = __shfl_down(bidx, o, 64);
             const int other = __shfl_down(pid, o, 64);
-            // (past lane 63 there is no partner: __shfl_down hands the lane its OWN pair back, and better() of a pair over itself is false —
+            // (past lane 63 there is no partner: __shfl_down hands the lane its OWN pair back, and pair_better() of a pair over itself is false —
             //  a test of the lane number here cost two registers, and at D = 60 a wave per SIMD)
-            if (other == pid && grid_better(v, ix, best, bidx)) { best = v; bidx = ix; }
+            if (other == pid && pair_better(v, ix, best, bidx)) { best = v; bidx = ix; }
         }
         // (the address is formed from pid here: no pointer is kept per lane across the slab)
-        if (head) ws[(size_t)pid * R + i] = GridPartial{best, bidx};        // (an empty first-side segment: -inf, 0x7fffffff)
+        if (head) ws[(size_t)pid * R + i] = PairPartial{best, bidx};        // (an empty first-side segment: -inf, 0x7fffffff)
     }
 }
 
-// One thread per (i, j), i fastest (the partials of a run are read side by side).  part_ptr int32[Cs + 1]: the partials of selection j.
-__global__ void __launch_bounds__(kBlock) k_pair_grid_finish(const GridPartial* __restrict__ ws, const int* __restrict__ part_ptr,
-                                                            const int* __restrict__ rows, const int* __restrict__ cols,
-                                                            const int* __restrict__ ptr1, const int* __restrict__ ptr2,
-                                                            const float* __restrict__ sum1, const float* __restrict__ sum2, int R, int Cs,
-                                                            int D, float* __restrict__ out, int* __restrict__ arg) {
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= (int64_t)R * Cs) return;
-    const int j = (int)(t / R), i = (int)(t % R);
-    const int a = rows ? rows[i] : i, q = cols[j];
-    const int m0 = ptr1[a], n1 = ptr1[a + 1] - m0;
-    const int p0 = ptr2[q], n2 = ptr2[q + 1] - p0;
-    const size_t o = 2 * ((size_t)i * Cs + j);
-    if (n1 <= 0 || n2 <= 0) {
-        out[o] = 0.f; out[o + 1] = 0.f;
-        if (arg) { arg[o] = -1; arg[o + 1] = -1; }
-        return;
-    }
-    float best = -INFINITY;
-    int bidx = 0x7fffffff;
-    for (int c = part_ptr[j]; c < part_ptr[j + 1]; ++c) {
-        const GridPartial p = ws[(size_t)c * R + i];
-        if (grid_better(p.v, p.ix, best, bidx)) { best = p.v; bidx = p.ix; }
-    }
-    const float* u = sum1 + (size_t)a * D;
-    const float* v = sum2 + (size_t)q * D;
-    float tot = 0.f;
-    for (int c = 0; c < D; ++c) tot = fmaf(u[c], v[c], tot);
-    out[o] = best;
-    out[o + 1] = tot / ((float)n1 * (float)n2);
-    if (arg) { arg[o] = m0 + bidx / n2; arg[o + 1] = p0 + bidx % n2; }
-}
-
-typedef void (*grid_kernel)(const float*, const float*, const int*, const int*, int, const int*, int, int, int, GridPartial*);
-
-// [D - 1] -> the dword instantiation of width D;  [D / 4 - 1] -> the 16-byte one
-template <int... I>
-static const grid_kernel* grid_dword_table(std::integer_sequence<int, I...>) {
-    static const grid_kernel t[] = {k_pair_grid<I + 1, false>...};
-    return t;
-}
-template <int... I>
-static const grid_kernel* grid_vec_table(std::integer_sequence<int, I...>) {
-    static const grid_kernel t[] = {k_pair_grid<4 * (I + 1), true>...};
-    return t;
-}
+struct GridKernel { template <int D, bool kVec> static constexpr auto get() { return &k_pair_grid<D, kVec>; } };
 
 }  // namespace glam
 
@@ -193,12 +95,12 @@ using namespace glam;
 
 extern "C" size_t glam_pair_pool_grid_workspace_bytes(int64_t n_partials, int64_t R) {
     if (n_partials <= 0 || R <= 0) return 0;
-    return (size_t)n_partials * (size_t)R * sizeof(GridPartial);
+    return (size_t)n_partials * (size_t)R * sizeof(PairPartial);
 }
 
 // a STATUS, as every int of this ABI that is not listed as a value: GLAM_OK when width D has a kernel
 extern "C" int glam_pair_pool_grid_supported(int D) {
-    if (D < 1 || D > kGridMaxD) return fail(GLAM_E_UNSUPPORTED, "glam_pair_pool_grid: D=%d not in 1..%d", D, kGridMaxD);
+    if (D < 1 || D > kStreamMaxD) return fail(GLAM_E_UNSUPPORTED, "glam_pair_pool_grid: D=%d not in 1..%d", D, kStreamMaxD);
     return GLAM_OK;
 }
 
@@ -206,10 +108,9 @@ extern "C" int glam_pair_pool_grid_fwd(const float* x1, const float* x2, const i
                                        int64_t R, const int32_t* cols, int64_t Cs, const int32_t* work, int64_t total_chunks,
                                        int64_t n_partials, int64_t Q1, int64_t Q2, int D, const float* sum1, const float* sum2, int slab,
                                        float* out, int32_t* argmax, void* workspace, size_t workspace_bytes, void* stream) {
-    static_assert(sizeof(GridPartial) == 8, "GridPartial: one 8-byte store");
     GLAM_REQUIRE(R >= 0 && R < INT32_MAX && Cs >= 0 && Cs < INT32_MAX, "glam_pair_pool_grid_fwd: R / Cs out of range");
     GLAM_REQUIRE(Q1 >= 0 && Q1 < INT32_MAX && Q2 >= 0 && Q2 < INT32_MAX, "glam_pair_pool_grid_fwd: Q1 / Q2 out of range");
-    GLAM_REQUIRE(total_chunks >= 0 && total_chunks < INT32_MAX / (kGridChunk * kGridLane), "glam_pair_pool_grid_fwd: total_chunks out of range");
+    GLAM_REQUIRE(total_chunks >= 0 && total_chunks < INT32_MAX / (kStreamChunk * kGridLane), "glam_pair_pool_grid_fwd: total_chunks out of range");
     GLAM_REQUIRE(n_partials >= 0 && n_partials < INT32_MAX, "glam_pair_pool_grid_fwd: n_partials out of range");
     GLAM_REQUIRE(slab >= 0, "glam_pair_pool_grid_fwd: slab must be 0 (choose) or the first-side segments per wave");
     if (const int rc = glam_pair_pool_grid_supported(D)) return rc;
@@ -223,25 +124,20 @@ extern "C" int glam_pair_pool_grid_fwd(const float* x1, const float* x2, const i
     const size_t need = glam_pair_pool_grid_workspace_bytes(n_partials, R);
     GLAM_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && ((uintptr_t)workspace & 7u) == 0),
                  "glam_pair_pool_grid_fwd: workspace too small or misaligned (glam_pair_pool_grid_workspace_bytes)");
-    GridPartial* ws = (GridPartial*)workspace;
+    PairPartial* ws = (PairPartial*)workspace;
     GLAM_PROF_LABEL("k_pair_grid");
     if (total_chunks > 0) {
-        // automatic slab: about kGridTargetWaves waves where the problem has them, never fewer than kGridMinSlab first-side segments per
-        // wave — the panel's rule, taken over as it is: it has not been tuned for packed chunks
-        int64_t sl = slab > 0 ? slab : std::max<int64_t>(kGridMinSlab, (R * total_chunks + kGridTargetWaves - 1) / kGridTargetWaves);
-        sl = std::min<int64_t>(sl, R);
-        const int64_t n_slabs = (R + sl - 1) / sl, chunk_blocks = (total_chunks + kGridWaves - 1) / kGridWaves;
+        const int64_t sl = stream_slab(slab, R, total_chunks);      // (the panel's rule, taken over as it is: not tuned for packed chunks)
+        const int64_t n_slabs = (R + sl - 1) / sl, chunk_blocks = (total_chunks + kStreamWaves - 1) / kStreamWaves;
         GLAM_REQUIRE(chunk_blocks * n_slabs < INT32_MAX, "glam_pair_pool_grid_fwd: grid out of range");
-        const grid_kernel k = (D & 3) == 0 && aligned16(x1) && aligned16(x2)
-                                  ? grid_vec_table(std::make_integer_sequence<int, kGridMaxD / 4>())[D / 4 - 1]
-                                  : grid_dword_table(std::make_integer_sequence<int, kGridMaxD>())[D - 1];
+        const auto k = stream_kernel<GridKernel>(D, x1, x2);
         hipLaunchKernelGGL(k, dim3((unsigned)(chunk_blocks * n_slabs)), dim3(kBlock), 0, (hipStream_t)stream, x1, x2, ptr1, rows, (int)R, work,
                            (int)total_chunks, (int)chunk_blocks, (int)sl, ws);
         GLAM_LAUNCH_CHECK("glam_pair_pool_grid_fwd");
     }
     GLAM_PROF_LABEL("k_pair_grid_finish");
-    hipLaunchKernelGGL(k_pair_grid_finish, dim3((unsigned)((R * Cs + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, ws,
-                       work + (size_t)total_chunks * kGridChunk * kGridLane, rows, cols, ptr1, ptr2, sum1, sum2, (int)R, (int)Cs, D, out,
+    hipLaunchKernelGGL(k_pair_stream_finish<true>, dim3((unsigned)((R * Cs + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, ws,
+                       work + (size_t)total_chunks * kStreamChunk * kGridLane, rows, cols, ptr1, ptr2, sum1, sum2, (int)R, (int)Cs, D, out,
                        argmax);
     GLAM_LAUNCH_CHECK("glam_pair_pool_grid_fwd (finish)");
     return GLAM_OK;

@@ -38,15 +38,6 @@ constexpr int kHeadMaxOut = 8;
 constexpr int kHeadMaxF = 16;
 constexpr int kSideQuad = 4;                   // chains per thread of the side kernel
 
-typedef __attribute__((address_space(4))) const float head_cf1;          // wave-uniform reads of data this launch does not write
-
-// p, which every lane of the wave holds alike, said so to the compiler (its loads then go to the scalar unit whatever the analysis finds)
-__device__ __forceinline__ head_cf1* head_uniform(const float* p) {
-    const uintptr_t v = (uintptr_t)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (head_cf1*)(((uintptr_t)hi << 32) | lo);
-}
-
 struct HeadSide {          // one of the two products: out = x[n, K] (ldx) @ W[e_dim, K]^T (ldw, already offset by col0) (+ b0)
     const float* x;
     const float* W;
@@ -107,7 +98,7 @@ __global__ void __launch_bounds__(kBlock) k_pair_head_side(HeadSide s0, HeadSide
 // The serial loop of one wave.  kRelu: act = max-with-zero that keeps a NaN; otherwise h > 0 ? h : slope * h (slope = 1: no activation,
 // the product with 1.f is exact).
 template <int OUT, int F, bool kRelu>
-__device__ __forceinline__ void head_loop(head_cf1* const (&ur)[kHeadRows], const float* lt, int nl, head_cf1* wf, int ldw, head_cf1* w1,
+__device__ __forceinline__ void head_loop(glam_cf1* const (&ur)[kHeadRows], const float* lt, int nl, glam_cf1* wf, int ldw, glam_cf1* w1,
                                           int e_dim, float slope, const float (&fr)[kHeadRows][F > 0 ? F : 1], float (&acc)[kHeadRows][OUT]) {
     // (not unrolled: an iteration holds 4 + F + OUT scalar operands, and two iterations of the wide instantiations spill them; the lane side's
     //  value of the NEXT e is loaded one iteration ahead instead — the last iteration loads its own again)
@@ -116,7 +107,7 @@ __device__ __forceinline__ void head_loop(head_cf1* const (&ur)[kHeadRows], cons
     for (int e = 0; e < e_dim; ++e) {
         const float bt = ahead;
         ahead = ld1g(lt + (size_t)min(e + 1, e_dim - 1) * nl);
-        head_cf1* wfe = wf + (size_t)e * ldw;
+        glam_cf1* wfe = wf + (size_t)e * ldw;
         float h[kHeadRows];
 #pragma unroll
         for (int r = 0; r < kHeadRows; ++r) {
@@ -152,23 +143,23 @@ __global__ void __launch_bounds__(kBlock) k_pair_head(const float* __restrict__ 
     const int l = lc * 64 + lane;
     const bool valid = l < nl;
     const int lr = valid ? l : nl - 1;                     // (an idle lane computes the last entry again and does not store)
-    head_cf1* ur[kHeadRows];
+    glam_cf1* ur[kHeadRows];
     size_t pair[kHeadRows];
     float fr[kHeadRows][F > 0 ? F : 1];
     float acc[kHeadRows][OUT];
-    head_cf1* b1u = head_uniform(b1);
+    glam_cf1* b1u = uniform_cf1(b1);
 #pragma unroll
     for (int r = 0; r < kHeadRows; ++r) {
         const int u = min(u0 + r, nu - 1);                 // (past the end: the last one again, not stored)
-        ur[r] = head_uniform(U + (size_t)u * e_dim);
+        ur[r] = uniform_cf1(U + (size_t)u * e_dim);
         pair[r] = (size_t)u * su + (size_t)lr * sl;
 #pragma unroll
         for (int k = 0; k < F; ++k) fr[r][k] = ld1g(f + pair[r] * F + k);
 #pragma unroll
         for (int o = 0; o < OUT; ++o) acc[r][o] = b1u[o];
     }
-    if (act == 1) head_loop<OUT, F, true>(ur, Lt + lr, nl, head_uniform(Wf), ldw, head_uniform(w1), e_dim, slope, fr, acc);
-    else head_loop<OUT, F, false>(ur, Lt + lr, nl, head_uniform(Wf), ldw, head_uniform(w1), e_dim, slope, fr, acc);
+    if (act == 1) head_loop<OUT, F, true>(ur, Lt + lr, nl, uniform_cf1(Wf), ldw, uniform_cf1(w1), e_dim, slope, fr, acc);
+    else head_loop<OUT, F, false>(ur, Lt + lr, nl, uniform_cf1(Wf), ldw, uniform_cf1(w1), e_dim, slope, fr, acc);
 #pragma unroll
     for (int r = 0; r < kHeadRows; ++r) {
         if (valid && u0 + r < nu) {

@@ -10,20 +10,14 @@
 //   partner rows: the whole partner segment is streamed past the lanes in ascending row order, two rows at a time, through WAVE-UNIFORM
 //       loads (the constant address space: the scalar unit fetches a row once per wave — see pairgather.hip for why not LDS), which needs
 //       the width as a compile-time constant: the kernel is instantiated per width (D = 1..128), 16-byte and dword forms.
-// The side is a wave-uniform swap of the two base pointers, not a second kernel: s(r1, r2) is ONE fmaf chain over channels 0 .. D-1 in
-// ascending order from 0.f — the chain of k_pair_gather / k_pair_pool_fwd — and fmaf(a, b, c) = fmaf(b, a, c), so either side may own.
+// The side is a wave-uniform swap of the two base pointers, not a second kernel: s(r1, r2) is the chain of stream_score2 (pairstream.h), and
+// fmaf(a, b, c) = fmaf(b, a, c), so either side may own.
 // Maximum: a strict > in ascending stream order keeps the first row that attains it: no index compare.  max over a pair's max1 rows (or
 // max2 rows) is therefore bit for bit the max column of the fusion kernels, and the first such row with its arg1 is their argmax.
 // Mean: the lane adds every score to a running sum in stream order — a fixed order, the same bits on every run.
-#include <utility>
-
-#include "common.h"
+#include "pairstream.h"
 
 namespace glam {
-
-constexpr int kMapItems = kBlock / 64;         // work items (waves) per block
-constexpr int kMapChunk = 64;                  // owner rows per item (one per lane) = MAP_CHUNK of ops_pair.py
-constexpr int kMapMaxD = 128;
 
 // work: int32[n_items, 4] = (a, b, 2 * chunk + side, first output row of the chunk); side 0: segment a of x1 owns, 1: segment b of x2.
 // kVec: D % 4 == 0 and both matrices 16-byte aligned (16-byte loads); otherwise dword loads.  The table is trusted.
@@ -33,9 +27,8 @@ __global__ void __launch_bounds__(kBlock) k_pair_map(const float* __restrict__ x
                                                     const int* __restrict__ work, int n_items,
                                                     float* __restrict__ max1, int* __restrict__ arg1, float* __restrict__ mean1,
                                                     float* __restrict__ max2, int* __restrict__ arg2, float* __restrict__ mean2) {
-    static_assert(D >= 1 && D <= kMapMaxD && (!kVec || D % 4 == 0), "k_pair_map: width");
     const int lane = threadIdx.x & 63;
-    const int it = blockIdx.x * kMapItems + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int it = blockIdx.x * kStreamWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (it >= n_items) return;                            // a wave without an item (no barrier below: the others go on)
     const int a = __builtin_amdgcn_readfirstlane(work[4 * (size_t)it]), b = __builtin_amdgcn_readfirstlane(work[4 * (size_t)it + 1]);
     const int sc = __builtin_amdgcn_readfirstlane(work[4 * (size_t)it + 2]), o0 = __builtin_amdgcn_readfirstlane(work[4 * (size_t)it + 3]);
@@ -50,7 +43,7 @@ __global__ void __launch_bounds__(kBlock) k_pair_map(const float* __restrict__ x
     float* omax = second ? max2 : max1;
     int* oarg = second ? arg2 : arg1;
     float* omean = second ? mean2 : mean1;
-    const int c0 = (sc >> 1) * kMapChunk;                             // first owner row of the chunk, inside its segment (< on)
+    const int c0 = (sc >> 1) * kStreamChunk;                          // first owner row of the chunk, inside its segment (< on)
     const bool valid = c0 + lane < on;
     const size_t o = (size_t)o0 + lane;
     if (pn <= 0) {                                                    // empty partner: the fill
@@ -59,37 +52,12 @@ __global__ void __launch_bounds__(kBlock) k_pair_map(const float* __restrict__ x
     }
     const float* prow = xo + (size_t)(ob + c0 + (valid ? lane : 0)) * D;      // (a lane past the end reads the chunk's first row and stores nothing)
     float pr[D];
-    if constexpr (kVec) {
-#pragma unroll
-        for (int u = 0; u < D / 4; ++u) {
-            const float4 v = ld4g(prow + 4 * u);
-            pr[4 * u] = v.x; pr[4 * u + 1] = v.y; pr[4 * u + 2] = v.z; pr[4 * u + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < D; ++c) pr[c] = ld1g(prow + c);
-    }
+    stream_owner_row<D, kVec>(prow, pr);
     float best = -INFINITY, sum = 0.f;
     int brow = 0;
     for (int r = 0; r < pn; r += 2) {
         const bool two = r + 1 < pn;                       // (an odd last row is scored twice and counted once)
-        const float* q0 = uniform_ptr(xp + (size_t)(pb + r) * D);
-        const float* q1 = q0 + (two ? D : 0);
-        float d0 = 0.f, d1 = 0.f;
-        if constexpr (kVec) {
-#pragma unroll
-            for (int u = 0; u < D / 4; ++u) {
-                const glam_v4f v0 = ((glam_cv4*)q0)[u], v1 = ((glam_cv4*)q1)[u];
-                d0 = fmaf(v0.x, pr[4 * u], d0); d0 = fmaf(v0.y, pr[4 * u + 1], d0); d0 = fmaf(v0.z, pr[4 * u + 2], d0); d0 = fmaf(v0.w, pr[4 * u + 3], d0);
-                d1 = fmaf(v1.x, pr[4 * u], d1); d1 = fmaf(v1.y, pr[4 * u + 1], d1); d1 = fmaf(v1.z, pr[4 * u + 2], d1); d1 = fmaf(v1.w, pr[4 * u + 3], d1);
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < D; ++c) {
-                d0 = fmaf(((glam_cf1*)q0)[c], pr[c], d0);
-                d1 = fmaf(((glam_cf1*)q1)[c], pr[c], d1);
-            }
-        }
+        const auto [d0, d1] = stream_score2<D, kVec>(xp + (size_t)(pb + r) * D, two, pr);
         // (strict >, ascending r: a later row that only ties never takes the place of an earlier one)
         if (d0 > best) { best = d0; brow = r; }
         sum += d0;
@@ -105,19 +73,7 @@ __global__ void __launch_bounds__(kBlock) k_pair_map(const float* __restrict__ x
     }
 }
 
-typedef void (*map_kernel)(const float*, const float*, const int*, const int*, const int*, int, float*, int*, float*, float*, int*, float*);
-
-// [D - 1] -> the dword instantiation of width D;  [D / 4 - 1] -> the 16-byte one
-template <int... I>
-static const map_kernel* map_dword_table(std::integer_sequence<int, I...>) {
-    static const map_kernel t[] = {k_pair_map<I + 1, false>...};
-    return t;
-}
-template <int... I>
-static const map_kernel* map_vec_table(std::integer_sequence<int, I...>) {
-    static const map_kernel t[] = {k_pair_map<4 * (I + 1), true>...};
-    return t;
-}
+struct MapKernel { template <int D, bool kVec> static constexpr auto get() { return &k_pair_map<D, kVec>; } };
 
 }  // namespace glam
 
@@ -128,16 +84,14 @@ extern "C" int glam_pair_map_fwd(const float* x1, const float* x2, const int32_t
                                  float* mean2, void* stream) {
     const char* who = "glam_pair_map_fwd";
     GLAM_REQUIRE(n_items >= 0 && n_items < INT32_MAX,"%s: n_items out of range", who);
-    if (D <= 0 || D > kMapMaxD) return fail(GLAM_E_UNSUPPORTED, "%s: D=%d not in 1..%d", who, D, kMapMaxD);
+    if (D <= 0 || D > kStreamMaxD) return fail(GLAM_E_UNSUPPORTED, "%s: D=%d not in 1..%d", who, D, kStreamMaxD);
     if (n_items == 0) return GLAM_OK;
     GLAM_REQUIRE(x1 && x2 && ptr1 && ptr2 && work && max1 && arg1 && mean1 && max2 && arg2 && mean2, "%s: null pointer", who);
     GLAM_REQUIRE(((uintptr_t)x1 & 3u) == 0 && ((uintptr_t)x2 & 3u) == 0, "%s: rows must be 4-byte aligned", who);
-    const map_kernel k = (D & 3) == 0 && aligned16(x1) && aligned16(x2)
-                             ? map_vec_table(std::make_integer_sequence<int, kMapMaxD / 4>())[D / 4 - 1]
-                             : map_dword_table(std::make_integer_sequence<int, kMapMaxD>())[D - 1];
+    const auto k = stream_kernel<MapKernel>(D, x1, x2);
     GLAM_PROF_LABEL("k_pair_map");
-    hipLaunchKernelGGL(k, dim3((unsigned)((n_items + kMapItems - 1) / kMapItems)), dim3(kBlock), 0, (hipStream_t)stream, x1, x2, ptr1, ptr2,
-                       work, (int)n_items, max1, arg1, mean1, max2, arg2, mean2);
+    hipLaunchKernelGGL(k, dim3((unsigned)((n_items + kStreamWaves - 1) / kStreamWaves)), dim3(kBlock), 0, (hipStream_t)stream, x1, x2, ptr1,
+                       ptr2, work, (int)n_items, max1, arg1, mean1, max2, arg2, mean2);
     GLAM_LAUNCH_CHECK(who);
     return GLAM_OK;
 }

@@ -12,8 +12,6 @@ constexpr int kPairSplit = 16;    // residue chunks (blocks) per pair in the spl
 constexpr int kResChunk = 64;     // residues per chunk pass: one per lane
 constexpr int kPartStride = 68;   // floats per (pair, split) partial: val, idx, pad, pad, colsum[64]
 
-__device__ __forceinline__ bool better(float v, int ix, float best, int bidx) { return v > best || (v == best && ix < bidx); }
-
 // Split path (D % 4 == 0, D <= 64).  Block (i, s): residues s*64 + k*16*64 + lane of pair i; wave q takes the ligand rows
 // a = q (mod 4), two at a time (independent dot-product chains; each dot keeps the channel order of the scalar path, so
 // values and argmax are those of the one-block kernel).
@@ -63,8 +61,8 @@ __global__ void __launch_bounds__(kBlock) k_pair_max_partial(const float* mol, c
                 }
                 if (valid) {
                     const int i0 = (t0 + a) * np + b, i1 = (t0 + a + 4) * np + b;
-                    if (better(d0, i0, best, bidx)) { best = d0; bidx = i0; }
-                    if (two && better(d1, i1, best, bidx)) { best = d1; bidx = i1; }
+                    if (pair_better(d0, i0, best, bidx)) { best = d0; bidx = i0; }
+                    if (two && pair_better(d1, i1, best, bidx)) { best = d1; bidx = i1; }
                 }
             }
         }
@@ -73,7 +71,7 @@ __global__ void __launch_bounds__(kBlock) k_pair_max_partial(const float* mol, c
     s_idx[tid] = bidx;
     __syncthreads();
     for (int o = kBlock / 2; o > 0; o >>= 1) {
-        if (tid < o && better(s_val[tid + o], s_idx[tid + o], s_val[tid], s_idx[tid])) { s_val[tid] = s_val[tid + o]; s_idx[tid] = s_idx[tid + o]; }
+        if (tid < o && pair_better(s_val[tid + o], s_idx[tid + o], s_val[tid], s_idx[tid])) { s_val[tid] = s_val[tid + o]; s_idx[tid] = s_idx[tid + o]; }
         __syncthreads();
     }
     float* dst = part + (size_t)blockIdx.x * kPartStride;
@@ -116,7 +114,7 @@ __global__ void __launch_bounds__(64) k_pair_finish(const float* mol, const int*
         for (int s = 0; s < kPairSplit; ++s) {
             const float v = pp[s * kPartStride];
             const int ix = reinterpret_cast<const int*>(pp + s * kPartStride)[1];
-            if (better(v, ix, best, bidx)) { best = v; bidx = ix; }
+            if (pair_better(v, ix, best, bidx)) { best = v; bidx = ix; }
         }
         const bool empty = nm <= 0 || np <= 0;
         out[2 * i] = empty ? 0.f : best;

@@ -303,7 +303,7 @@ def pair_pool_indexed(mol_out, pro_out, msp, psp, pro_of_pair=None, return_argma
 # --------------------------------------------------------------------------------------
 # panel screening: every ligand against every selected protein, protein-stationary (csrc/pairpanel.hip, glam_pair_pool_panel_fwd)
 # --------------------------------------------------------------------------------------
-PANEL_CHUNK = 64      # residue rows per chunk (one per lane of the wave that holds them) = kPanelChunk of csrc/pairpanel.hip
+PANEL_CHUNK = 64      # residue rows per chunk (one per lane of the wave that holds them) = kStreamChunk of csrc/pairstream.h
 
 
 class PanelPlan(_Staged):
@@ -514,7 +514,7 @@ def pair_pool_gather(x1, x2, sp1, sp2, idx1=None, idx2=None, return_argmax=False
 # drug x drug, the whole table: every selected first-side segment against every selected second-side one, second-side-stationary with
 # several small segments packed into the 64 lanes of a wave (csrc/pairgrid.hip, glam_pair_pool_grid_fwd)
 # --------------------------------------------------------------------------------------
-GRID_CHUNK = 64       # second-side rows per chunk (one per lane of the wave that holds them) = kGridChunk of csrc/pairgrid.hip
+GRID_CHUNK = 64       # second-side rows per chunk (one per lane of the wave that holds them) = kStreamChunk of csrc/pairstream.h
 
 
 class GridPlan(_Staged):
@@ -703,7 +703,7 @@ def pair_pool_gather_shared(x1, x2, sp1, sp2, idx1=None, idx2=None, with_identit
 # --------------------------------------------------------------------------------------
 # interaction maps: per-row marginals of every pair's score matrix, both sides from one launch (csrc/pairmap.hip, glam_pair_map_fwd)
 # --------------------------------------------------------------------------------------
-MAP_CHUNK = 64        # owner rows per work item (one per lane of the wave that holds them) = kMapChunk of csrc/pairmap.hip
+MAP_CHUNK = 64        # owner rows per work item (one per lane of the wave that holds them) = kStreamChunk of csrc/pairstream.h
 
 
 class MapPlan(_Staged):

@@ -74,6 +74,7 @@ SIGNATURES = {
     "glam_pair_pool_panel_workspace_bytes": (_sz, [_i64, _i64]),
     "glam_pair_pool_panel_supported": (_i32, [_i32]),
     "glam_pair_pool_panel_fwd": (_i32, [_vp] * 5 + [_i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "glam_pair_pool_panel_bwd": (_i32, [_vp] * 11 + [_i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "glam_pair_pool_grid_workspace_bytes": (_sz, [_i64, _i64]),
     "glam_pair_pool_grid_supported": (_i32, [_i32]),
     "glam_pair_pool_grid_fwd": (_i32, [_vp] * 5 + [_i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),

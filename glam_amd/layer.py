@@ -1195,6 +1195,13 @@ def dot_and_global_pool2_shared(mol_out, pro_out, mol_batch, pro_sp, pro_of_pair
     return ops.pair_pool_shared(mol_out, pro_out, ops.segment_ptr(mol_batch), pro_sp, pro_of_pair, with_identity)
 
 
+def dot_and_global_pool2_panel_shared(mol_out, pro_out, mol_batch, pro_sp, plan, with_identity=False):
+    """``dot_and_global_pool2_panel`` for TRAINING: the same forward with a backward (``ops.pair_pool_panel_shared``) -> ``[L, Qs, 2]`` — a
+    ligand's rows collect the gradients of its ``Qs`` pairs, a protein's residue rows those of every pair of the table that names it.
+    ``with_identity`` as in ``dot_and_global_pool2``."""
+    return ops.pair_pool_panel_shared(mol_out, pro_out, ops.segment_ptr(mol_batch), pro_sp, plan, with_identity)
+
+
 def dot_and_global_pool2_gather(x1, x2, sp1, sp2, idx1=None, idx2=None, return_argmax=False):
     """``dot_and_global_pool2`` with BOTH sides held once: pair i is segment ``idx1[i]`` of ``sp1`` against segment ``idx2[i]`` of ``sp2``
     (the ``SegmentPtr``s of the encoded drugs; ``ops.pair_index`` for the indices) — the fusion of ``ArchitectureDDI.score_pairs``.

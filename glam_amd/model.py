@@ -20,6 +20,7 @@ from .layer import GlobalPool5, GlobalLAPool, Set2Set  # noqa: F401  (resolved f
 from .layer import LinearBlock, MessageBlock, dot_and_global_pool2, first_node_spec, flat_then_head, following_dropout, prestage_pass
 from .layer import _BatchNorm, _LayerNorm, _PairNorm, dot_and_global_pool2_gather, dot_and_global_pool2_indexed, dot_and_global_pool2_shared
 from .layer import dot_and_global_pool2_gather_shared, dot_and_global_pool2_grid, dot_and_global_pool2_panel
+from .layer import dot_and_global_pool2_panel_shared
 
 
 def model_args(args):
@@ -154,6 +155,8 @@ _DTI_WORDS = dict(slots=_slots("pro"), thing="protein", call="model(data_mol, da
                   train="model(data_mol, data_pro) on one protein graph per pair", eager="a library walk never repeats a batch",
                   rows="residue rows", encode="encode_proteins",
                   written="a protein-side parameter or buffer (pro_lin0 / pro_conv / pro_readout / pro_flat)")
+# (forward_panel holds BOTH sides once: every ligand stands for Qs rows of the expanded batch, every protein for L * its entries in sel)
+_DTI_PANEL_WORDS = dict(_DTI_WORDS, slots=_slots("mol", "pro"), thing="graph", call="model(M, P) on the expanded batch")
 _DDI_WORDS = dict(slots=_slots("mol1", "mol2"), thing="drug", call="model(mol1, mol2)", copy="copy of a drug", fusion="gathered",
                   train="model(mol1, mol2) on one graph per pair and side",
                   eager="its pair index is validated on the host and differs from call to call", rows="rows", encode="encode_drugs",
@@ -183,15 +186,16 @@ def _inference_guard(model, what, w):
         raise GlamHipError(f"{what} runs eagerly ({w['eager']}): not inside a hipGraph capture")
 
 
-def _shared_guard(model, w):
-    """The guard of ``forward_shared``: the norms an encoding refuses, and a ``_BatchNorm`` in their slots while training."""
+def _shared_guard(model, w, what="forward_shared"):
+    """The guard of ``forward_shared`` (and of ``forward_panel``, under its name ``what``): the norms an encoding refuses, and a
+    ``_BatchNorm`` in their slots while training."""
     thing, call = w["thing"], w["call"]
-    _tower_norms_guard(model, "forward_shared", w)
+    _tower_norms_guard(model, what, w)
     for name, _ in w["slots"] if model.training else ():
         if type(getattr(model, name).norm) is _BatchNorm:
-            raise GlamHipError(f"forward_shared: {name}'s norm _BatchNorm takes its batch statistics over the {thing} rows of the step, "
+            raise GlamHipError(f"{what}: {name}'s norm _BatchNorm takes its batch statistics over the {thing} rows of the step, "
                                f"and in {call} those weigh each {thing} by how often it is repeated — over {thing}s held once they are "
-                               f"other statistics: train with {call}, or call forward_shared in eval() (running statistics are per row)")
+                               f"other statistics: train with {call}, or call {what} in eval() (running statistics are per row)")
 
 
 def _check_encoding(model, what, enc, cls, stamp, rows, w):
@@ -546,6 +550,68 @@ class ArchitectureDTI(torch.nn.Module):
                                  lambda xm, xp: dot_and_global_pool2_shared(xm, xp, data_mol.batch, psp, index, with_identity=True))
             outm = m.flat_out()
             return self.lin_out1(self.lin_out0(ops.cat_cols([outm, ops.pair_rows(p.flat_out(), index)] + fusion)))
+
+    # ---- training on a label table: both towers run once, the fusion is the panel's ------------------------------------------
+    def _panel_plan(self, data_pro, psp, proteins):
+        """The ``ops.PanelPlan`` of ``proteins`` over the graphs of ``data_pro``, kept ON the batch object (per selection): the first
+        call reads the proteins' sizes back once, a later step — or a capture — on the same batch finds the plan and its device copies."""
+        cache = data_pro.__dict__.setdefault("_glam_panel_plans", {"sizes": None, "plans": {}})
+        sel = None if proteins is None else ops.panel_plan([0] * psp.B, proteins).sel          # (validated before the read-back)
+        key = None if sel is None else tuple(sel.tolist())
+        plan = cache["plans"].get(key)
+        if plan is None or plan.Q != psp.B or plan.N != psp.N:
+            if cache["sizes"] is None or len(cache["sizes"]) != psp.B or int(cache["sizes"].sum()) != psp.N:
+                ptr = psp.ptr.cpu().numpy().astype("int64")
+                cache["sizes"] = ptr[1:] - ptr[:-1]
+            plan = cache["plans"][key] = ops.panel_plan(cache["sizes"], sel)
+        return plan
+
+    def forward_panel(self, data_mol, data_pro, proteins=None, plan=None):
+        """``model(M, P)`` as a table -> ``[L, Qs, out_dim]``: entry ``[l, j]`` is row ``l * Qs + j`` of the expanded batch ``M`` = ligand
+        ``l`` of ``data_mol`` repeated ``Qs`` times, ``P`` = the proteins ``sel`` of ``data_pro`` tiled ``L`` times — without building
+        either: ``data_pro`` holds ``Q`` DISTINCT protein graphs, BOTH towers run once (``L`` ligand graphs, ``Q`` protein graphs), every
+        step's fusion is the protein-stationary panel with a backward (``ops.pair_pool_panel_shared``), and the head runs over the
+        ``L * Qs`` ligand-major rows ``cat[mol_flat[l], pro_flat[sel[j]], fusion...]``, both flat matrices expanded by ``ops.pair_rows``.
+        It trains: gradients to every parameter of both towers and the head; a ligand's gradients are the sums over its ``Qs`` pairs, a
+        protein's over every pair that names it, in the batch order of the expanded pair list (no atomics: two runs agree bit for bit).
+        ``proteins``: host integers in ``[0, Q)``, any order, duplicates allowed (``ops.panel_plan``); ``None`` = all ``Q`` in order.
+        ``plan``: the ``ops.PanelPlan`` of the selection over the proteins' sizes, kept by the caller across the steps that use it
+        (``proteins`` is then left ``None``); without one the proteins' sizes are read back once and the plan is kept on ``data_pro``.
+        Either way its device copies are made on the first, eager, visit, and a ``GraphedTrainStep`` capture needs them to exist.
+
+        Contract.  Output and every parameter gradient equal those of ``model(M, P)`` within the fp32 parity bound WHENEVER nothing in
+        a tower is stochastic or depends on the rest of the batch: ``eval()``, or ``train()`` with ``_None()`` / ``Dropout(0)`` and
+        non-random activations.  In ``train()`` with live Dropout / RReLU in a tower the noise is drawn ONCE per ligand and ONCE per
+        protein and shared by all their pairs; the reference draws it per copy.  That is another (equally valid) regulariser, not the
+        reference's — which is why this is a call of its own and ``model(data_mol, data_pro)`` is untouched.  Refused, before any
+        launch, on EITHER tower: ``_GraphSizeNorm``; ``_LayerNorm`` / ``_PairNorm`` in a ``*_flat`` slot; a ``_BatchNorm`` while training
+        (batch statistics weigh each graph by how often it is repeated); and a ``plan`` made for other sizes.  The head's norms are not
+        refused: the head sees exactly the expanded rows.  Always eager by itself (no graphed-call route); inside a
+        ``GraphedTrainStep`` it is captured with the step."""
+        _shared_guard(self, _DTI_PANEL_WORDS, "forward_panel")
+        m, p = _Tower(self, "mol", data_mol), _Tower(self, "pro", data_pro)
+        if plan is not None:
+            if not isinstance(plan, ops.PanelPlan):
+                raise GlamHipError("forward_panel: plan must come from ops.panel_plan (the kernel trusts its table)")
+            if proteins is not None:
+                raise GlamHipError("forward_panel: pass the selection (proteins) or the plan made from it, not both")
+            if (p.n is not None and plan.Q != p.n) or plan.N != data_pro.x.size(0):
+                raise GlamHipError(f"forward_panel: the plan was made for {plan.Q} proteins of {plan.N} residue rows, data_pro holds "
+                                   f"{p.n if p.n is not None else '?'} of {data_pro.x.size(0)}")
+        msp, psp = ops.segment_ptr(data_mol.batch, m.n), ops.segment_ptr(data_pro.batch, p.n)
+        if plan is None:
+            plan = self._panel_plan(data_pro, psp, proteins)
+        L, Qs = msp.B, plan.Qs
+        lig, col = plan.row_index(L)
+        with ops.weight_scope():
+            fusion = _fused_walk(self.message_steps, m, p, False, lambda xm, xp: dot_and_global_pool2_panel_shared(
+                xm, xp, data_mol.batch, psp, plan, with_identity=True))
+            outm, outp = m.flat_out(), p.flat_out()
+            if L == 0 or Qs == 0:
+                return outm.new_zeros(L, Qs, self.lin_out1.linear.out_features)
+            # ligand-major rows: row l * Qs + j = cat[mol_flat[l], pro_flat[sel[j]], fusion_0[l, j], ...]
+            rows = ops.cat_cols([ops.pair_rows(outm, lig), ops.pair_rows(outp, col)] + [f.reshape(L * Qs, 2) for f in fusion])
+            return self.lin_out1(self.lin_out0(rows)).view(L, Qs, -1)
 
 
 class DrugEncoding:

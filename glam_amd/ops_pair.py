@@ -336,6 +336,30 @@ class PanelPlan(_Staged):
         self.work = np.concatenate([table.reshape(-1), chunk_ptr.astype(np.int32)])
         self.chunks, self.chunk_ptr = self.work[:4 * T].reshape(T, 4), self.work[4 * T:]
         _Staged.__init__(self, "the panel's selection and work table", self.sel, self.work)
+        self._by_protein, self._row_index = None, {}
+
+    def by_protein(self):
+        """The selection grouped by protein, for the protein role of the training call (``ops.pair_pool_panel_shared``): ``order`` int32
+        ``[Qs]`` — the stable argsort of ``sel`` (the entries that name a protein keep their order) — and ``ptr`` int32 ``[Q + 1]``, the
+        offsets of the proteins' runs in it.  Built once, on the host; ``.on(device)`` -> ``(order, ptr)`` on the device, made once per
+        device.  A staged pair of its own: ``plan.on(device)`` stays ``(sel, work)``."""
+        if self._by_protein is None:
+            self._by_protein = PairsByProtein(self.sel, self.Q)
+        return self._by_protein
+
+    def row_index(self, L):
+        """The two ``PairIndex`` of the ``L * Qs`` ligand-major rows of a table over ``L`` ligands — row ``l * Qs + j`` is ligand ``l``
+        (over ``L``) and protein ``sel[j]`` (over ``Q``) — for ``ops.pair_rows``.  Kept per ``L``: a later step, or a capture, finds the
+        same objects and their device copies."""
+        L = int(L)
+        if L not in self._row_index:
+            if L * self.Qs >= 2 ** 31 - 1:
+                raise IndexError(f"panel_plan: a table of {L} x {self.Qs} pairs holds 2^31 - 1 rows or more")
+            while len(self._row_index) >= 16:
+                self._row_index.pop(next(iter(self._row_index)))
+            self._row_index[L] = (PairIndex(np.repeat(np.arange(L, dtype=np.int32), self.Qs), L),
+                                  PairIndex(np.tile(self.sel, L).astype(np.int32), self.Q))
+        return self._row_index[L]
 
 
 def panel_plan(sizes_host, proteins=None):
@@ -393,6 +417,72 @@ def pair_pool_panel(mol_out, pro_out, msp, psp, plan, molsum=None, prosum=None, 
         lib.glam_pair_pool_panel_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(work), plan.total_chunks, ptr(sel), Qs, L, Q, D,
                                      ptr(molsum), ptr(prosum), int(slab), ptr(out), ptr(arg), ptr(ws), ws.numel(), stream())
     return (out, arg) if return_argmax else out
+
+
+# --------------------------------------------------------------------------------------
+# training on a label table: the panel fusion with a backward (csrc/pairpanel.hip forward, csrc/pairpanel_bwd.hip)
+# --------------------------------------------------------------------------------------
+class _PairPoolPanelShared(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mol, pro, msp, psp, plan, with_identity=False):
+        mol_in, pro_in = mol, pro
+        mol, pro = _operands("pair_pool_panel_shared", mol, pro, msp, psp, "mol_out", "pro_out")
+        L, Q, Qs, D, dev = msp.B, psp.B, plan.Qs, mol.size(1), mol.device
+        sel, work = plan.on(dev)
+        order, qptr = plan.by_protein().on(dev)
+        out, arg, _, _ = _outputs((L, Qs), dev)
+        # (no row on one side: every pair is empty, and the empty matrix has no address to pass)
+        ctx.rows = L > 0 and Qs > 0 and msp.N > 0 and psp.N > 0
+        if ctx.rows:
+            lib = _lib.api()
+            molsum, prosum = segment_pool(mol, msp, "sum"), segment_pool(pro, psp, "sum")
+            ws = torch.empty(max(lib.glam_pair_pool_panel_workspace_bytes(plan.total_chunks, L), 16), dtype=torch.uint8, device=dev)
+            lib.glam_pair_pool_panel_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(work), plan.total_chunks, ptr(sel), Qs, L, Q, D,
+                                         ptr(molsum), ptr(prosum), 0, ptr(out), ptr(arg), ptr(ws), ws.numel(), stream())
+        else:
+            out.zero_()
+            arg.fill_(-1)
+            molsum, prosum = mol.new_zeros(L, D), pro.new_zeros(Q, D)
+        ctx.save_for_backward(mol, pro, arg, molsum, prosum, sel, order, qptr)
+        ctx.sps = (msp, psp)
+        return _alias_fwd(ctx, out, mol_in, pro_in, with_identity)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out, d_ma=None, d_pa=None):
+        mol, pro, arg, molsum, prosum, sel, order, qptr = ctx.saved_tensors
+        msp, psp = ctx.sps
+        # (an empty table, or only empty pairs: the entry point writes nothing)
+        launch, d_out, d_ma, d_pa = _alias_bwd(d_out, d_ma, d_pa, mol, pro, "mol", "pro", nothing_written=not ctx.rows)
+        if not launch:
+            return d_ma, d_pa, None, None, None, None
+        d_mol, d_pro = torch.empty_like(mol), torch.empty_like(pro)
+        _lib.api().glam_pair_pool_panel_bwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(sel), ptr(order), ptr(qptr), ptr(arg),
+                                            ptr(d_out), ptr(molsum), ptr(prosum), sel.numel(), msp.B, psp.B, mol.size(1), ptr(d_ma),
+                                            ptr(d_pa), ptr(d_mol), ptr(d_pro), stream())
+        return d_mol, d_pro, None, None, None, None
+
+
+def pair_pool_panel_shared(mol_out, pro_out, msp, psp, plan, with_identity=False):
+    """``pair_pool_panel`` WITH a backward: ``[max, mean]`` of ``mol[seg_l] @ pro[seg_q].T`` for EVERY ligand ``l`` and every selected
+    protein ``q = plan.sel[j]`` -> ``[L, Qs, 2]``, for training on a ligand x protein label table.  The forward is the launches of
+    ``pair_pool_panel`` with the argmax kept (bit for bit its output); the column sums of both sides are computed once and kept for the
+    backward, ONE launch (``glam_pair_pool_panel_bwd``): a ligand's rows collect the gradients of its ``Qs`` pairs with ``j`` ascending, a
+    protein's rows those of every pair that names it in ascending ``l * Qs + j`` — the batch order of the expanded pair list — without
+    atomics (two runs are bit-equal); duplicates in the selection add up, a protein the selection does not name gets zeros.  ``plan``:
+    ``panel_plan`` over the sizes of ``psp``'s segments — keep ONE across the steps that use it: its device copies are made on the
+    first, eager, visit and a hipGraph capture needs them to exist.  Widths 1..128.  ``with_identity``: as ``pair_pool`` — ``(out,
+    mol_out, pro_out)`` with the two matrices handed back through the node (both require grad, fp32): its backward launch then adds
+    their later gradients itself; the plain triple otherwise."""
+    if not isinstance(plan, PanelPlan):
+        raise GlamHipError("pair_pool_panel_shared: plan must come from ops.panel_plan (the kernel trusts its table)")
+    if plan.Q != psp.B or plan.N != psp.N:
+        raise GlamHipError(f"pair_pool_panel_shared: the plan was made for {plan.Q} proteins of {plan.N} residue rows, the operands hold "
+                           f"{psp.B} of {psp.N}")
+    if mol_out.dim() == 2 and not 1 <= mol_out.size(1) <= 128:
+        raise GlamHipError(f"pair_pool_panel_shared: width {mol_out.size(1)} is outside the kernel table (1..128)")
+    # (no add_width: glam_pair_pool_panel_bwd adds inside its launch for every width of its table)
+    return _apply_aliasing(_PairPoolPanelShared, (mol_out, pro_out, msp, psp, plan), mol_out, pro_out, with_identity)
 
 
 # --------------------------------------------------------------------------------------

@@ -664,6 +664,25 @@ int glam_pair_pool_panel_fwd(const float* mol, const float* pro, const int32_t* 
                              int64_t total_chunks, const int32_t* sel, int64_t Qs, int64_t L, int64_t Q, int D, const float* molsum,
                              const float* prosum, int slab, float* out, int32_t* argmax, void* workspace, size_t workspace_bytes,
                              void* stream);
+/* ... and its backward (csrc/pairpanel_bwd.hip), ONE launch: training on a ligand x protein label table.  argmax int32[L,Qs,2] and d_out
+ * f32[L,Qs,2] are those of glam_pair_pool_panel_fwd (the argmax kept: not NULL here); molsum / prosum as there.  sel_order int32[Qs]: the
+ * selection stably sorted by protein (a stable argsort of sel); sel_ptr int32[Q+1]: the offsets of the proteins' runs in it (both built
+ * and checked by the caller, trusted here, like sel).  With g = d_out, q_j = sel[j] and w[l,j] = g[l,j,1] / ((float)n_l * (float)n_{q_j}):
+ *   d_mol, every row a of every ligand l:  0, + w[l,j] * prosum[q_j] for j = 0..Qs-1 ascending, then fmaf(g[l,j,0], pro[argmax[l,j,1]], .)
+ *          for the j with argmax[l,j,0] == a in the same order, + add_mol[a] last;
+ *   d_pro, every row b of every protein q (selected or not):  0, + w[l,j] * molsum[l] for the pairs (l, j) with sel[j] == q in ascending
+ *          l * Qs + j (the batch order of the expanded pair list), then fmaf(g[l,j,0], mol[argmax[l,j,0]], .) for those of them with
+ *          argmax[l,j,1] == b in the same order, + add_pro[b] last.
+ * An empty ligand or protein (argmax -1) contributes nothing; the rows of a protein no entry of sel names get exact zeros (+ add_pro);
+ * duplicates in sel add up.  No atomics: the order of every sum depends on the table alone, two runs are bit-equal.  One block per
+ * (segment, 16 of its rows): 32 blocks a protein, 2 a ligand, each walking its segment's list (Qs pairs for a ligand, L * (entries of
+ * sel that name it) for a protein).  add_mol / add_pro (the gradients of a later use of mol / pro) may be NULL.  16-byte loads and stores
+ * when D % 4 == 0 and mol, pro, molsum, prosum, add_mol, add_pro, d_mol, d_pro are 16-byte aligned, dwords otherwise.  D in 1..128, else
+ * GLAM_E_UNSUPPORTED; L == 0 or Qs == 0: GLAM_OK, nothing launched or written. */
+int glam_pair_pool_panel_bwd(const float* mol, const float* pro, const int32_t* mol_ptr, const int32_t* pro_ptr, const int32_t* sel,
+                             const int32_t* sel_order, const int32_t* sel_ptr, const int32_t* argmax, const float* d_out,
+                             const float* molsum, const float* prosum, int64_t Qs, int64_t L, int64_t Q, int D, const float* add_mol,
+                             const float* add_pro, float* d_mol, float* d_pro, void* stream);
 
 /* Grid fusion (inference): EVERY selected first-side segment rows[i], i = 0..R-1 (int32[R], entries in [0, Q1), any order, duplicates
  * allowed; NULL = the identity over Q1, needs R == Q1), of x1 (ptr1 int32[Q1+1]) against every selected second-side segment cols[j],

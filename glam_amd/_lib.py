@@ -81,6 +81,9 @@ SIGNATURES = {
     "glam_pair_map_fwd": (_i32, [_vp] * 5 + [_i64, _i32] + [_vp] * 7),
     "glam_pair_head_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "glam_pair_head_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _f32, _vp, _sz, _vp, _vp]),
+    "glam_pair_head_classes_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "glam_pair_head_classes_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _f32,
+                                          _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "glam_hits_supported": (_i32, [_i32]),
     "glam_hits_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "glam_hits_reset": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]),

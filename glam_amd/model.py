@@ -220,21 +220,20 @@ def _check_head(what, head):
     return head == "factored"
 
 
-def _factored_head(model, what, block_pairs=0):
-    """``(act, slope)`` of ``ops.pair_head`` for ``model``'s head (``lin_out0`` / ``lin_out1``), or the refusal of ``head="factored"`` —
-    on the host, before the first launch.  The factored head is ``lin_out1.linear(act(lin_out0.linear(.)))``: both norm slots ``_None``,
-    both dropout slots idle (``_None``, or a ``Dropout`` in ``eval()``), ``end_act`` elementwise and deterministic, at most 8 task columns,
-    and no head blocks (there is no hidden matrix to keep in pieces)."""
+def _head_activation(model, what, route, instead):
+    """``(act, slope)`` of the table heads' kernels (``ops.pair_head``, ``ops.pair_head_classes``) for ``model``'s head, or the refusal in
+    the words of ``route`` — what the two routes share: both norm slots ``_None``, both dropout slots idle, ``end_act`` elementwise and
+    deterministic, ``lin_out1`` ending in its linear layer, the fusion columns within the kernels' registers."""
     from torch.nn import Dropout, LeakyReLU, ReLU, RReLU
     for name in ("lin_out0", "lin_out1"):
         block = getattr(model, name)
         if type(block.norm) is not _None:
-            raise GlamHipError(f"{what}: head=\"factored\" has no norm in the head, {name}'s norm is {type(block.norm).__name__} — its "
-                               "input does not separate into a row part and a column part: use head=\"rows\"")
+            raise GlamHipError(f"{what}: {route} has no norm in the head, {name}'s norm is {type(block.norm).__name__} — its "
+                               f"input does not separate into a row part and a column part: {instead}")
         d = block.dropout
         if not (type(d) is _None or (type(d) is Dropout and (not d.training or d.p == 0))):
-            raise GlamHipError(f"{what}: head=\"factored\" needs {name}'s dropout slot idle (_None, or a Dropout in eval()), got "
-                               f"{type(d).__name__}: use head=\"rows\"")
+            raise GlamHipError(f"{what}: {route} needs {name}'s dropout slot idle (_None, or a Dropout in eval()), got "
+                               f"{type(d).__name__}: {instead}")
     a = model.lin_out0.act
     if type(a) is _None:
         act = "none", 0.0
@@ -245,21 +244,43 @@ def _factored_head(model, what, block_pairs=0):
     elif type(a) is RReLU and not a.training:
         act = "leaky", (float(a.lower) + float(a.upper)) / 2          # eval: the fixed mean slope, as in LinearBlock.forward
     else:
-        raise GlamHipError(f"{what}: head=\"factored\" applies end_act inside its kernel and knows _None, ReLU, LeakyReLU and RReLU (eval), "
-                           f"not {type(a).__name__}: use head=\"rows\"")
+        raise GlamHipError(f"{what}: {route} applies end_act inside its kernel and knows _None, ReLU, LeakyReLU and RReLU (eval), "
+                           f"not {type(a).__name__}: {instead}")
     if type(model.lin_out1.act) is not _None:
-        raise GlamHipError(f"{what}: head=\"factored\" ends in lin_out1's linear layer, which here is followed by "
-                           f"{type(model.lin_out1.act).__name__}: use head=\"rows\"")
+        raise GlamHipError(f"{what}: {route} ends in lin_out1's linear layer, which here is followed by "
+                           f"{type(model.lin_out1.act).__name__}: {instead}")
+    if 2 * model.message_steps > ops.HEAD_MAX_F:
+        raise GlamHipError(f"{what}: {route} keeps the 2 * message_steps fusion columns of a pair in registers, at most "
+                           f"{ops.HEAD_MAX_F}; this model has {2 * model.message_steps}: {instead}")
+    return act
+
+
+def _factored_head(model, what, block_pairs=0):
+    """``(act, slope)`` of ``ops.pair_head`` for ``model``'s head (``lin_out0`` / ``lin_out1``), or the refusal of ``head="factored"`` —
+    on the host, before the first launch.  The factored head is ``lin_out1.linear(act(lin_out0.linear(.)))``: both norm slots ``_None``,
+    both dropout slots idle (``_None``, or a ``Dropout`` in ``eval()``), ``end_act`` elementwise and deterministic, at most 8 task columns,
+    and no head blocks (there is no hidden matrix to keep in pieces)."""
+    act = _head_activation(model, what, "head=\"factored\"", "use head=\"rows\"")
     out_dim = model.lin_out1.linear.out_features
     if out_dim > ops.HEAD_MAX_OUT:
         raise GlamHipError(f"{what}: head=\"factored\" keeps out_dim accumulators per pair in registers, at most {ops.HEAD_MAX_OUT}; "
                            f"this model has out_dim = {out_dim}: use head=\"rows\"")
-    if 2 * model.message_steps > ops.HEAD_MAX_F:
-        raise GlamHipError(f"{what}: head=\"factored\" keeps the 2 * message_steps fusion columns of a pair in registers, at most "
-                           f"{ops.HEAD_MAX_F}; this model has {2 * model.message_steps}: use head=\"rows\"")
     if isinstance(block_pairs, bool) or block_pairs != 0:
         raise GlamHipError(f"{what}: block_pairs = {block_pairs!r} cuts the hidden matrix of head=\"rows\" into blocks; head=\"factored\" has "
                            "no hidden matrix and no blocks: leave block_pairs at 0")
+    return act
+
+
+def _class_head(model, what):
+    """``(act, slope)`` of ``ops.pair_head_classes`` for ``model``'s head, or the refusal of the class route (``classify_matrix``,
+    ``classify_panel``, ``score="logp"`` of the top calls) — on the host, before the first launch: the checks of ``_factored_head``
+    without its limit of 8 task columns, and a head that has classes to choose between."""
+    instead = "take the logits from head=\"rows\" and torch.log_softmax / argmax"
+    act = _head_activation(model, what, "the class head", instead)
+    out_dim = model.lin_out1.linear.out_features
+    if not 2 <= out_dim <= ops.HEAD_MAX_CLASSES:
+        raise GlamHipError(f"{what}: the class head calls one of 2..{ops.HEAD_MAX_CLASSES} classes; this model has out_dim = {out_dim}"
+                           + (" (one column is a score, not a class: score=\"logit\")" if out_dim == 1 else f": {instead}"))
     return act
 
 
@@ -269,6 +290,25 @@ def _table_head_factored(model, act, flat_a, flat_b, fusion, R, Cs):
     if fusion:
         f = ops.cat_cols([t.reshape(R * Cs, 2) for t in fusion]).view(R, Cs, 2 * len(fusion))
     return ops.pair_head(flat_a, flat_b, f, model.lin_out0.linear, model.lin_out1.linear, act[0], act[1])
+
+
+def _table_head_classes(model, act, flat_a, flat_b, fusion, R, Cs, classes, logits):
+    """``ops.pair_head_classes`` over the table, on the operands of ``_table_head_factored`` -> ``ops.ClassTable``."""
+    f = None
+    if fusion and R and Cs:
+        f = ops.cat_cols([t.reshape(R * Cs, 2) for t in fusion]).view(R, Cs, 2 * len(fusion))
+    elif fusion:
+        f = flat_a.new_zeros(R, Cs, 2 * len(fusion))
+    return ops.pair_head_classes(flat_a, flat_b, f, model.lin_out0.linear, model.lin_out1.linear, act[0], act[1], classes, logits)
+
+
+def _check_score(what, score):
+    """The ``score=`` keyword of the top calls: ``"logit"`` (column ``task`` of the head's output) or ``"logp"`` (the log-softmax of class
+    ``task``, through the class head); whether it is the latter."""
+    if score not in ("logit", "logp"):
+        raise GlamHipError(f"{what}: score = {score!r} is not \"logit\" (the raw output column task) or \"logp\" (the log-softmax of class "
+                           "task over the model's classes: ops.pair_head_classes)")
+    return score == "logp"
 
 
 def _shared_index(model, given, P, Q, device, **words):
@@ -449,6 +489,15 @@ class ArchitectureDTI(torch.nn.Module):
         row count) over the whole matrix they are given, so they must see one protein column ``[L, .]`` at a time, as in ``screen``."""
         return _head_is_per_row(self)
 
+    def _panel_walk(self, m, data_mol, enc, plan, return_argmax):
+        """The walk of ``screen_panel`` (inside its weight scope): the ligand tower ``m`` step by step with the protein-stationary fusion
+        of each step -> ``(fusion, contacts, outm [L, hid], outp [Qs, hid])``."""
+        fusion, contacts = self._ligand_walk(m, return_argmax, lambda x, i: dot_and_global_pool2_panel(
+            x, enc.rows[i], data_mol.batch, enc.sp, plan, None, enc.prosum[i], return_argmax))
+        outm = m.flat_out()
+        outp = enc.flat.index_select(0, plan.on(enc.flat.device)[0].long())                   # [Qs, hid]
+        return fusion, contacts, outm, outp
+
     def screen_panel(self, data_mol, enc, proteins=None, return_argmax=False, head="rows"):
         """``[L, Qs, out_dim]``: column ``j`` is ``screen(data_mol, enc, pro_of_pair=[proteins[j]] * L)`` — every ligand of ``data_mol``
         against every protein of the selection — from ONE pass of the ligand tower and one protein-stationary fusion per step
@@ -470,10 +519,7 @@ class ArchitectureDTI(torch.nn.Module):
         msp = ops.segment_ptr(data_mol.batch, m.n)
         L, Qs = msp.B, plan.Qs
         with ops.weight_scope():
-            fusion, contacts = self._ligand_walk(m, return_argmax, lambda x, i: dot_and_global_pool2_panel(
-                x, enc.rows[i], data_mol.batch, enc.sp, plan, None, enc.prosum[i], return_argmax))
-            outm = m.flat_out()
-            outp = enc.flat.index_select(0, plan.on(enc.flat.device)[0].long())                   # [Qs, hid]
+            fusion, contacts, outm, outp = self._panel_walk(m, data_mol, enc, plan, return_argmax)
             if L == 0 or Qs == 0:
                 out = outm.new_zeros(L, Qs, self.lin_out1.linear.out_features)
             elif act:
@@ -488,30 +534,64 @@ class ArchitectureDTI(torch.nn.Module):
                 out = torch.stack(cols, 1)
         return (out, contacts) if return_argmax else out
 
-    def screen_top(self, batches, enc, proteins=None, k=100, task=0, largest=True, head="rows"):
+    def classify_panel(self, data_mol, enc, proteins=None, classes=(), return_logits=False):
+        """``screen_panel`` read as a classifier -> ``ops.ClassTable(cls, logp, sel, logits)`` over the ``[L, Qs]`` panel: per ligand and
+        protein the called class (``torch.argmax`` of the head's output), its log-softmax, and the log-softmax of the classes ``classes``
+        names (host ints in ``[0, out_dim)``, at most 8) — for the screening model ``classes=[1]`` and ``sel[..., 0].exp()`` is the
+        ligand's probability of class 1.  The walk is ``screen_panel``'s; the head is ``ops.pair_head_classes`` (one side launch, one table
+        launch): no pair rows, no hidden matrix and, unless ``return_logits`` asks for it, no ``[L, Qs, out_dim]`` table.  The logits are
+        those of ``screen_panel(head="factored")`` bit for bit where that head exists (``out_dim <= 8``).  Refused, before the first
+        launch: what ``head="factored"`` refuses in the head except its limit on ``out_dim`` (any of 2..1 024 is taken), and
+        ``out_dim = 1``."""
+        return self._classify_panel("classify_panel", data_mol, enc, proteins, classes, return_logits)
+
+    def _classify_panel(self, what, data_mol, enc, proteins, classes, return_logits):
+        self._screen_guard(what)
+        _check_encoding(self, what, enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
+        act = _class_head(self, what)
+        chosen = ops.class_selection(classes, self.lin_out1.linear.out_features, what)
+        plan = enc.panel(proteins)                                 # host-side checks, before the first launch
+        m = _Tower(self, "mol", data_mol)
+        msp = ops.segment_ptr(data_mol.batch, m.n)
+        with ops.weight_scope():
+            fusion, _, outm, outp = self._panel_walk(m, data_mol, enc, plan, False)
+            return _table_head_classes(self, act, outm, outp, fusion, msp.B, plan.Qs, chosen, return_logits)
+
+    def screen_top(self, batches, enc, proteins=None, k=100, task=0, largest=True, head="rows", score="logit"):
         """The best ``k`` ligands per selected protein of a whole library -> ``hits.HitList`` with one query per entry of the selection
         (duplicates allowed, as in ``ops.panel_plan``).  ``batches``: an iterable of ``data_mol`` or ``(data_mol, ids)``; every item goes
         through ``screen_panel(data_mol, enc, proteins)`` — all of its guards and refusals apply, with its own messages — and column
         ``task`` of its output is merged into the lists by stride (``HitList.update``: two launches, no copy).  ``ids``: the ligands' ids,
         host integers or an int32 device tensor; without them a ligand's id is its position in the stream.  Ids are not deduplicated.
         Memory is ``Qs x k`` however long the stream: no score tensor outlives its batch, and the loop adds no read-back to those of
-        ``screen_panel`` (one per encoding).  ``k`` in 1..1024; ``largest``: whether a larger score is better.  ``head``: ``screen_panel``'s."""
+        ``screen_panel`` (one per encoding).  ``k`` in 1..1024; ``largest``: whether a larger score is better.  ``head``: ``screen_panel``'s.
+        ``score``: ``"logit"`` ranks by the raw output column ``task`` (the call described above); ``"logp"`` ranks by the log-softmax of class
+        ``task`` over the model's classes — what a cross-entropy model's score is: every batch goes through the class head
+        (``classify_panel`` with ``classes=[task]``, whose guards apply under this call's name; ``head`` is not consulted) and
+        ``sel[..., 0]`` is merged in place."""
         k = hits.check_k(k, "screen_top")
+        logp = _check_score("screen_top", score)
         out_dim = self.lin_out1.linear.out_features
         if isinstance(task, bool) or not isinstance(task, int) or not 0 <= task < out_dim:
             raise GlamHipError(f"screen_top: task = {task!r} is not one of the model's {out_dim} task column(s)")
         top = None
         for item in batches:
             data_mol, ids = item if isinstance(item, tuple) else (item, None)
-            out = self.screen_panel(data_mol, enc, proteins, head=head)
+            if logp:             # sel[..., 0] = the log-softmax of class task, merged in place by stride
+                out, col = self._classify_panel("screen_top", data_mol, enc, proteins, [task], False).sel, 0
+            else:
+                out, col = self.screen_panel(data_mol, enc, proteins, head=head), task
             if top is None:
                 top = hits.HitList(out.size(1), k, out.device, largest)
-            top.update(out, ids, task)
+            top.update(out, ids, col)
         if top is None:          # an empty stream: empty lists, after the checks a first batch would have met
-            self._screen_guard("screen_panel")
-            _check_encoding(self, "screen_panel", enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
-            if _check_head("screen_panel", head):
-                _factored_head(self, "screen_panel")
+            what = "screen_top" if logp else "screen_panel"
+            self._screen_guard(what)
+            _check_encoding(self, what, enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
+            if logp:
+                _class_head(self, what)
+            elif _check_head(what, head):
+                _factored_head(self, what)
             top = hits.HitList(ops.panel_plan([0] * enc.num_graphs, proteins).Qs, k, enc.flat.device, largest)     # (host only: no read-back)
         return top
 
@@ -782,6 +862,31 @@ class ArchitectureDDI(torch.nn.Module):
             block_pairs = self._MATRIX_BLOCK_BYTES // (4 * self.lin_out0.linear.out_features)
         return max(1, min(R, block_pairs // max(Cs, 1)))
 
+    @staticmethod
+    def _matrix_selection(enc, rows, cols):
+        """``(R, Cs, index, sel)`` of a table's ``rows`` / ``cols`` — host-side, before the first launch and before the read-back."""
+        Q = enc.num_graphs
+        R = ops.pair_count(rows, None, Q)
+        index = None if rows is None else ops.pair_index(rows, R, Q, name="rows", over="drugs")
+        sel = None if cols is None else ops.grid_plan([0] * Q, cols).sel
+        return R, (Q if sel is None else int(sel.shape[0])), index, sel
+
+    def _matrix_walk(self, enc, index, sel, return_argmax):
+        """The fusion walk of ``score_matrix``: one second-side-stationary fusion per step over the whole table ->
+        ``(fusion, contacts, o1 [R, hid], o2 [Cs, hid])``."""
+        plan = enc.grid(sel)
+        fusion, contacts = [], []
+        for s in range(self.message_steps):
+            f = dot_and_global_pool2_grid(enc.rows1[s], enc.rows2[s], enc.sp, enc.sp, plan, index, enc.sum1[s], enc.sum2[s], return_argmax)
+            if return_argmax:
+                f, a = f
+                contacts.append(a)
+            fusion.append(f)
+        dev = enc.flat1.device
+        o1 = enc.flat1 if index is None else enc.flat1.index_select(0, index.on(dev))              # [R, hid]
+        o2 = enc.flat2.index_select(0, plan.on(dev)[0])                                            # [Cs, hid]
+        return fusion, contacts, o1, o2
+
     def score_matrix(self, enc, rows=None, cols=None, return_argmax=False, block_pairs=0, head="rows"):
         """``[R, Cs, out_dim]``: entry ``[i, j]`` is ``score_pairs(enc, [rows[i]], [cols[j]])`` — tower 1 for the row drug, tower 2 for the
         column drug, so the matrix is not symmetric — from one second-side-stationary fusion per step over the whole table
@@ -803,23 +908,9 @@ class ArchitectureDDI(torch.nn.Module):
         self._pairs_guard("score_matrix")
         _check_encoding(self, "score_matrix", enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
         act = _factored_head(self, "score_matrix", block_pairs) if _check_head("score_matrix", head) else None
-        Q = enc.num_graphs
-        R = ops.pair_count(rows, None, Q)
-        index = None if rows is None else ops.pair_index(rows, R, Q, name="rows", over="drugs")     # host-side, before the first launch
-        sel = None if cols is None else ops.grid_plan([0] * Q, cols).sel                            # (and before the read-back)
-        Cs = Q if sel is None else int(sel.shape[0])
+        R, Cs, index, sel = self._matrix_selection(enc, rows, cols)
         per_block = None if act else self._matrix_block_rows(block_pairs, R, Cs)
-        plan = enc.grid(sel)
-        fusion, contacts = [], []
-        for s in range(self.message_steps):
-            f = dot_and_global_pool2_grid(enc.rows1[s], enc.rows2[s], enc.sp, enc.sp, plan, index, enc.sum1[s], enc.sum2[s], return_argmax)
-            if return_argmax:
-                f, a = f
-                contacts.append(a)
-            fusion.append(f)
-        dev = enc.flat1.device
-        o1 = enc.flat1 if index is None else enc.flat1.index_select(0, index.on(dev))              # [R, hid]
-        o2 = enc.flat2.index_select(0, plan.on(dev)[0])                                            # [Cs, hid]
+        fusion, contacts, o1, o2 = self._matrix_walk(enc, index, sel, return_argmax)
         out_dim = self.lin_out1.linear.out_features
         with ops.weight_scope():
             if R == 0 or Cs == 0:
@@ -840,12 +931,33 @@ class ArchitectureDDI(torch.nn.Module):
                 out = torch.stack(per_col, 1)
         return (out, contacts) if return_argmax else out
 
+    def classify_matrix(self, enc, rows=None, cols=None, classes=(), return_logits=False):
+        """``score_matrix`` read as a classifier -> ``ops.ClassTable(cls, logp, sel, logits)`` over the ``[R, Cs]`` table: per pair of drugs
+        the called class (``torch.argmax`` of the head's output — the interaction type), its log-softmax (how sure), and the log-softmax
+        of the classes ``classes`` names (host ints in ``[0, out_dim)``, at most 8, duplicates allowed, order kept).  The fusion walk is
+        ``score_matrix``'s; the head is ``ops.pair_head_classes`` (one side launch, one table launch): no pair rows, no ``[pairs, e_dim]``
+        hidden matrix and, unless ``return_logits`` asks for it, no ``[R, Cs, out_dim]`` table — for ANY ``out_dim`` in 2..1 024.  An entry's
+        results do not depend on the selection around it; its logits are those of ``score_matrix(head="factored")`` bit for bit where
+        that head exists (``out_dim <= 8``).  Refused, before the first launch: what ``head="factored"`` refuses in the head except its
+        limit on ``out_dim``, and ``out_dim = 1``."""
+        return self._classify_matrix("classify_matrix", enc, rows, cols, classes, return_logits)
+
+    def _classify_matrix(self, what, enc, rows, cols, classes, return_logits):
+        self._pairs_guard(what)
+        _check_encoding(self, what, enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
+        act = _class_head(self, what)
+        chosen = ops.class_selection(classes, self.lin_out1.linear.out_features, what)
+        R, Cs, index, sel = self._matrix_selection(enc, rows, cols)
+        fusion, _, o1, o2 = self._matrix_walk(enc, index, sel, False)
+        with ops.weight_scope():
+            return _table_head_classes(self, act, o1, o2, fusion, R, Cs, chosen, return_logits)
+
     # ---- partner lists: the best row drugs per column drug, without the table -------------------------------------------------
     # Pair rows per block of row drugs when the caller leaves the choice (block_rows = 0): 2^22 — a design choice (a block's scores and
     # fusion columns stay in the tens of MiB whatever the library's size, and a block is still thousands of waves), NOT a measurement.
     _TOP_BLOCK_PAIRS = 1 << 22
 
-    def matrix_top(self, enc, rows=None, cols=None, k=100, task=0, largest=True, block_rows=0, head="factored"):
+    def matrix_top(self, enc, rows=None, cols=None, k=100, task=0, largest=True, block_rows=0, head="factored", score="logit"):
         """The best ``k`` row drugs (tower 1) for every selected column drug (tower 2) -> ``hits.HitList`` with one query per entry of
         ``cols`` (duplicates allowed) — without the ``[R, Cs]`` table ever existing.  ``rows`` is walked in blocks of ``block_rows`` row drugs
         (0 = as many as keep a block within ``2^22`` pair rows, at least one); every block goes through ``score_matrix(enc, block, cols,
@@ -853,17 +965,25 @@ class ArchitectureDDI(torch.nn.Module):
         lists (``HitList.update``: two launches, no copy) under the ids of the block's drugs, so a drug that ``rows`` names twice can hold two
         slots.  With ``head="factored"`` an entry's bits do not depend on the block it is scored in: the lists are those of the whole
         table.  Memory is ``Cs x k`` plus one block however long ``rows`` is.  ``k`` in 1..1024; ``largest``: whether a larger score is
-        better.  An empty ``rows`` gives empty lists, after the checks a first block would have met."""
+        better.  An empty ``rows`` gives empty lists, after the checks a first block would have met.
+        ``score``: ``"logit"`` ranks by the raw output column ``task`` (the call described above); ``"logp"`` ranks by the log-softmax of class
+        ``task`` over the model's classes — what a cross-entropy model's score is: every block goes through the class head
+        (``classify_matrix`` with ``classes=[task]``, whose guards apply under this call's name; ``head`` is not consulted) and
+        ``sel[..., 0]`` is merged in place.  Its entries do not depend on the block either."""
         k = hits.check_k(k, "matrix_top")
+        logp = _check_score("matrix_top", score)
         out_dim = self.lin_out1.linear.out_features
         if isinstance(task, bool) or not isinstance(task, int) or not 0 <= task < out_dim:
             raise GlamHipError(f"matrix_top: task = {task!r} is not one of the model's {out_dim} task column(s)")
         if isinstance(block_rows, bool) or not isinstance(block_rows, int) or block_rows < 0:
             raise GlamHipError(f"matrix_top: block_rows = {block_rows!r} must be 0 (choose) or the row drugs per block")
-        self._pairs_guard("score_matrix")
-        _check_encoding(self, "score_matrix", enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
-        if _check_head("score_matrix", head):
-            _factored_head(self, "score_matrix")
+        what = "matrix_top" if logp else "score_matrix"
+        self._pairs_guard(what)
+        _check_encoding(self, what, enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
+        if logp:
+            _class_head(self, what)
+        elif _check_head(what, head):
+            _factored_head(self, what)
         Q = enc.num_graphs
         R = ops.pair_count(rows, None, Q)
         ids = ops.pair_index(rows, R, Q, name="rows", over="drugs").host                            # host-side, before the first launch
@@ -873,7 +993,10 @@ class ArchitectureDDI(torch.nn.Module):
         top = hits.HitList(Cs, k, enc.flat1.device, largest)
         for i0 in range(0, R, per_block):
             block = ids[i0:i0 + per_block]
-            top.update(self.score_matrix(enc, block, sel, head=head), block, task)
+            if logp:             # sel[..., 0] = the log-softmax of class task, merged in place by stride
+                top.update(self._classify_matrix(what, enc, block, sel, [task], False).sel, block, 0)
+            else:
+                top.update(self.score_matrix(enc, block, sel, head=head), block, task)
         return top
 
     # ---- training on shared drugs: each tower runs once per DISTINCT drug of its side of the step ----------------------------

@@ -8,7 +8,9 @@ writes, ``pair_count`` is "P of whichever index is given", and a Function that h
 ``_alias_bwd`` under a wrapper that ends in ``_apply_aliasing``."""
 from __future__ import annotations
 
+import ctypes
 import dataclasses
+import typing
 
 import numpy as np
 import torch
@@ -912,13 +914,13 @@ _HEAD_ACTS = {"none": 0, "relu": 1, "leaky": 2}
 HEAD_MAX_OUT, HEAD_MAX_F = 8, 16          # = kHeadMaxOut / kHeadMaxF of csrc/pairhead.hip
 
 
-def _weight_bias(lin, name):
+def _weight_bias(lin, name, who="pair_head"):
     """``(weight, bias)`` of ``lin`` — a ``torch.nn.Linear`` or the pair of tensors itself."""
     if isinstance(lin, torch.nn.Linear):
         return lin.weight, lin.bias
     if isinstance(lin, (tuple, list)) and len(lin) == 2 and all(torch.is_tensor(t) for t in lin):
         return lin[0], lin[1]
-    raise GlamHipError(f"pair_head: {name} must be a torch.nn.Linear with a bias or its (weight, bias) tensors, got {type(lin).__name__}")
+    raise GlamHipError(f"{who}: {name} must be a torch.nn.Linear with a bias or its (weight, bias) tensors, got {type(lin).__name__}")
 
 
 def _rows_view(t, name):
@@ -927,6 +929,49 @@ def _rows_view(t, name):
     if t.dtype != torch.float32:
         raise GlamHipError(f"{name}: expected float32, got {t.dtype}")
     return t if t.stride(1) == 1 and t.stride(0) >= t.size(1) else t.contiguous()
+
+
+def _head_operands(who, flat_a, flat_b, f, lin0, lin1, act, out_lo, out_hi, host_checks=None):
+    """The argument checks the table heads share (``pair_head``, ``pair_head_classes``), in one order and with one wording, and the
+    operands as the entry points take them.  ``host_checks(out_dim)`` runs before anything needs a device."""
+    w0, b0 = _weight_bias(lin0, "lin0", who)
+    w1, b1 = _weight_bias(lin1, "lin1", who)
+    if b0 is None or b1 is None:
+        raise GlamHipError(f"{who}: both linear layers must have a bias")
+    if host_checks is not None and w1.dim() == 2:
+        host_checks(w1.size(0))
+    given = (flat_a, flat_b, f, w0, b0, w1, b1)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in given):
+        raise GlamHipError(f"{who} is inference only (no backward): call it under torch.no_grad(); the head that trains is the listed "
+                           "one — head=\"rows\" of score_matrix / screen_panel, and model(...) / forward_shared for the training calls")
+    require_device(*given)
+    if act not in _HEAD_ACTS:
+        raise GlamHipError(f"{who}: act = {act!r} is not one of 'none', 'relu', 'leaky'")
+    if flat_a.dim() != 2 or flat_b.dim() != 2 or flat_a.size(1) != flat_b.size(1) or flat_a.size(1) < 1:
+        raise GlamHipError(f"{who}: the two sides disagree (width): flat_a {tuple(flat_a.shape)}, flat_b {tuple(flat_b.shape)}")
+    R, Cs, hid = flat_a.size(0), flat_b.size(0), flat_a.size(1)
+    if f is not None and (f.dim() != 3 or tuple(f.shape[:2]) != (R, Cs)):
+        raise GlamHipError(f"{who}: f must be [{R}, {Cs}, F] (or None for F = 0), got {tuple(f.shape)}")
+    F = 0 if f is None else f.size(2)
+    if w0.dim() != 2 or w0.size(1) != 2 * hid + F or tuple(b0.shape) != (w0.size(0),) or w0.size(0) < 1:
+        raise GlamHipError(f"{who}: lin0 must map 2 * {hid} + {F} = {2 * hid + F} columns and carry one bias per output, got weight "
+                           f"{tuple(w0.shape)}, bias {tuple(b0.shape)}")
+    e_dim = w0.size(0)
+    if w1.dim() != 2 or w1.size(1) != e_dim or tuple(b1.shape) != (w1.size(0),):
+        raise GlamHipError(f"{who}: lin1 must map the {e_dim} outputs of lin0 and carry one bias per output, got weight "
+                           f"{tuple(w1.shape)}, bias {tuple(b1.shape)}")
+    out_dim = w1.size(0)
+    if not out_lo <= out_dim <= out_hi:
+        raise GlamHipError(f"{who}: out_dim = {out_dim} is outside {out_lo}..{out_hi} (head=\"rows\" takes any)")
+    if F > HEAD_MAX_F:
+        raise GlamHipError(f"{who}: F = {F} fusion columns are outside 0..{HEAD_MAX_F} (head=\"rows\" takes any)")
+    if R * Cs >= 2 ** 31 - 1:
+        raise GlamHipError(f"{who}: a table of {R} x {Cs} pairs holds 2^31 - 1 entries or more: score it in blocks of rows")
+    a, b = _rows_view(flat_a, "flat_a"), _rows_view(flat_b, "flat_b")
+    w0 = _rows_view(w0, "lin0.weight")
+    w1, b0, b1 = f32c(w1, "lin1.weight"), f32c(b0, "lin0.bias"), f32c(b1, "lin1.bias")
+    f = None if F == 0 else f32c(f, "f")
+    return a, b, f, w0, b0, w1, b1, R, Cs, hid, F, e_dim, out_dim
 
 
 def pair_head(flat_a, flat_b, f, lin0, lin1, act="none", slope=0.0):
@@ -939,41 +984,7 @@ def pair_head(flat_a, flat_b, f, lin0, lin1, act="none", slope=0.0):
     one fixed chain of its own ``(flat_a[i], flat_b[j], f[i, j])``: the same bits whatever the rest of the table is.  ``out_dim`` in 1..8,
     ``F`` in 0..16, ``R * Cs < 2^31 - 1``.  Inference only: there is no backward (a head that trains is the listed one: ``head="rows"`` of
     the table calls, ``model(...)`` / ``forward_shared`` for training)."""
-    w0, b0 = _weight_bias(lin0, "lin0")
-    w1, b1 = _weight_bias(lin1, "lin1")
-    if b0 is None or b1 is None:
-        raise GlamHipError("pair_head: both linear layers must have a bias")
-    given = (flat_a, flat_b, f, w0, b0, w1, b1)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in given):
-        raise GlamHipError("pair_head is inference only (no backward): call it under torch.no_grad(); the head that trains is the listed "
-                           "one — head=\"rows\" of score_matrix / screen_panel, and model(...) / forward_shared for the training calls")
-    require_device(*given)
-    if act not in _HEAD_ACTS:
-        raise GlamHipError(f"pair_head: act = {act!r} is not one of 'none', 'relu', 'leaky'")
-    if flat_a.dim() != 2 or flat_b.dim() != 2 or flat_a.size(1) != flat_b.size(1) or flat_a.size(1) < 1:
-        raise GlamHipError(f"pair_head: the two sides disagree (width): flat_a {tuple(flat_a.shape)}, flat_b {tuple(flat_b.shape)}")
-    R, Cs, hid = flat_a.size(0), flat_b.size(0), flat_a.size(1)
-    if f is not None and (f.dim() != 3 or tuple(f.shape[:2]) != (R, Cs)):
-        raise GlamHipError(f"pair_head: f must be [{R}, {Cs}, F] (or None for F = 0), got {tuple(f.shape)}")
-    F = 0 if f is None else f.size(2)
-    if w0.dim() != 2 or w0.size(1) != 2 * hid + F or tuple(b0.shape) != (w0.size(0),) or w0.size(0) < 1:
-        raise GlamHipError(f"pair_head: lin0 must map 2 * {hid} + {F} = {2 * hid + F} columns and carry one bias per output, got weight "
-                           f"{tuple(w0.shape)}, bias {tuple(b0.shape)}")
-    e_dim = w0.size(0)
-    if w1.dim() != 2 or w1.size(1) != e_dim or tuple(b1.shape) != (w1.size(0),):
-        raise GlamHipError(f"pair_head: lin1 must map the {e_dim} outputs of lin0 and carry one bias per output, got weight "
-                           f"{tuple(w1.shape)}, bias {tuple(b1.shape)}")
-    out_dim = w1.size(0)
-    if not 1 <= out_dim <= HEAD_MAX_OUT:
-        raise GlamHipError(f"pair_head: out_dim = {out_dim} is outside 1..{HEAD_MAX_OUT} (head=\"rows\" takes any)")
-    if F > HEAD_MAX_F:
-        raise GlamHipError(f"pair_head: F = {F} fusion columns are outside 0..{HEAD_MAX_F} (head=\"rows\" takes any)")
-    if R * Cs >= 2 ** 31 - 1:
-        raise GlamHipError(f"pair_head: a table of {R} x {Cs} pairs holds 2^31 - 1 entries or more: score it in blocks of rows")
-    a, b = _rows_view(flat_a, "flat_a"), _rows_view(flat_b, "flat_b")
-    w0 = _rows_view(w0, "lin0.weight")
-    w1, b0, b1 = f32c(w1, "lin1.weight"), f32c(b0, "lin0.bias"), f32c(b1, "lin1.bias")
-    f = None if F == 0 else f32c(f, "f")
+    a, b, f, w0, b0, w1, b1, R, Cs, hid, F, e_dim, out_dim = _head_operands("pair_head", flat_a, flat_b, f, lin0, lin1, act, 1, HEAD_MAX_OUT)
     dev = flat_a.device
     out = torch.empty(R, Cs, out_dim, dtype=torch.float32, device=dev)
     if R and Cs:
@@ -982,3 +993,57 @@ def pair_head(flat_a, flat_b, f, lin0, lin1, act="none", slope=0.0):
         lib.glam_pair_head_fwd(ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(f), R, Cs, hid, F, ptr(w0), w0.stride(0), ptr(b0), e_dim, ptr(w1),
                                ptr(b1), out_dim, _HEAD_ACTS[act], float(slope), ptr(ws), ws.numel(), ptr(out), stream())
     return out
+
+
+# --------------------------------------------------------------------------------------
+# the class table: called class, its log-probability and selected log-probabilities, for any out_dim (glam_pair_head_classes_fwd)
+# --------------------------------------------------------------------------------------
+HEAD_CLASS_TILE, HEAD_MAX_CLASSES, HEAD_MAX_SEL = 16, 1024, 8          # = kClassTile / kHeadMaxClasses / kMaxSel of csrc/pairhead.hip
+
+
+class ClassTable(typing.NamedTuple):
+    """``cls`` int32 ``[R, Cs]``: the called class (``torch.argmax`` of the logits); ``logp`` ``[R, Cs]``: its log-softmax; ``sel``
+    ``[R, Cs, S]``: the log-softmax of the ``S`` selected classes, in the order given; ``logits`` ``[R, Cs, out_dim]`` or ``None``."""
+    cls: torch.Tensor
+    logp: torch.Tensor
+    sel: torch.Tensor
+    logits: typing.Optional[torch.Tensor]
+
+
+def class_selection(classes, out_dim, who="pair_head_classes"):
+    """``classes`` as a list of host ints in ``[0, out_dim)``, at most ``HEAD_MAX_SEL`` of them (duplicates allowed, order kept), or the
+    refusal."""
+    sel = host_ints(classes, "classes", "be a vector of class indices", below=out_dim,
+                    on_device=f"{who}: classes lives on a device: it is a host sequence of at most {HEAD_MAX_SEL} class indices")
+    if sel.shape[0] > HEAD_MAX_SEL:
+        raise GlamHipError(f"{who}: {sel.shape[0]} selected classes, the kernel catches at most {HEAD_MAX_SEL} per call (return_logits / "
+                           "logits=True hands out all of them)")
+    return [int(c) for c in sel]
+
+
+def pair_head_classes(flat_a, flat_b, f, lin0, lin1, act="none", slope=0.0, classes=(), logits=False):
+    """The head of ``pair_head`` read as a classifier, for ANY ``out_dim`` in 2..1 024 -> ``ClassTable(cls, logp, sel, logits)``: per pair
+    the called class (``torch.argmax`` of the logits: a NaN is the largest, of equal logits the smallest index), its log-softmax, and the
+    log-softmax of the classes ``classes`` names (host ints in ``[0, out_dim)``, at most 8, duplicates allowed, order kept) — from the side
+    launch and ONE ``k_pair_head_classes``, which walks the classes in tiles of ``HEAD_CLASS_TILE`` and keeps a running maximum and sum:
+    neither the ``[R * Cs, e_dim]`` hidden matrix nor, unless ``logits=True`` asks for it, the ``[R, Cs, out_dim]`` table exists.  A logit
+    is ``pair_head``'s chain bit for bit; an entry's four results are one fixed sequence of its own ``(flat_a[i], flat_b[j], f[i, j])``.
+    ``logp`` / ``sel`` are NaN where a logit is NaN (``torch.log_softmax``).  Arguments, checks and limits otherwise as ``pair_head``
+    (``F`` in 0..16, ``R * Cs < 2^31 - 1``, inference only, empty tables without a launch)."""
+    who = "pair_head_classes"
+    chosen = []
+    a, b, f, w0, b0, w1, b1, R, Cs, hid, F, e_dim, out_dim = _head_operands(
+        who, flat_a, flat_b, f, lin0, lin1, act, 2, HEAD_MAX_CLASSES, lambda n: chosen.extend(class_selection(classes, n, who)))
+    dev = flat_a.device
+    S = len(chosen)
+    cls = torch.empty(R, Cs, dtype=torch.int32, device=dev)
+    logp = torch.empty(R, Cs, dtype=torch.float32, device=dev)
+    sel = torch.empty(R, Cs, S, dtype=torch.float32, device=dev)
+    table = torch.empty(R, Cs, out_dim, dtype=torch.float32, device=dev) if logits else None
+    if R and Cs:
+        lib = _lib.api()
+        ws = torch.empty(max(lib.glam_pair_head_classes_workspace_bytes(R, Cs, e_dim, out_dim), 16), dtype=torch.uint8, device=dev)
+        lib.glam_pair_head_classes_fwd(ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(f), R, Cs, hid, F, ptr(w0), w0.stride(0), ptr(b0), e_dim,
+                                       ptr(w1), ptr(b1), out_dim, _HEAD_ACTS[act], float(slope), (ctypes.c_int * max(S, 1))(*chosen), S,
+                                       ptr(ws), ws.numel(), ptr(cls), ptr(logp), ptr(sel) if S else None, ptr(table), stream())
+    return ClassTable(cls, logp, sel, table)

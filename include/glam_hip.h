@@ -738,6 +738,26 @@ int glam_pair_head_fwd(const float* flat_a, int64_t lda, const float* flat_b, in
                        int F, const float* W0, int64_t ldw, const float* b0, int e_dim, const float* w1, const float* b1, int out_dim,
                        int act, float slope, void* workspace, size_t workspace_bytes, float* out, void* stream);
 
+/* Class table (inference): the head above for ANY out_dim in 2..1024, ending in the called class and its log-softmax:
+ *   x[o]  = the logit of glam_pair_head_fwd, the same chain bit for bit (acc = b1[o]; acc = fmaf(w1[o,e], h_e, acc), e ascending)
+ *   cls   = argmax_o x[o]            int32[R,Cs]    (torch.argmax: a NaN is the largest, of equal values the smallest index)
+ *   logp  = x[cls] - lse             f32[R,Cs]      lse = m + log(sum_o exp(x[o] - m)), kept as a running (m, sum) over o ascending
+ *   sel   = x[classes[k]] - lse      f32[R,Cs,n_sel] (NULL with n_sel == 0);  classes: a HOST array of n_sel ints in [0, out_dim), n_sel <= 8,
+ *                                                    duplicates allowed, order kept (read by this call and passed to the kernel by value)
+ *   logits = x                       f32[R,Cs,out_dim], or NULL: not written
+ * logp / sel are NaN where a logit of the pair is NaN (torch.log_softmax).  The classes are walked in tiles of 16, each with its own pass
+ * over e: the registers do not depend on out_dim, and neither the hidden matrix nor (without logits) the [R,Cs,out_dim] table exists.
+ * Two launches on `stream`: k_pair_head_classes_side (A, B and the transposed, tile-padded lin1 weight with its bias, into the workspace)
+ * and k_pair_head_classes.  An entry depends on its own (flat_a[i], flat_b[j], f[i,j]) alone.  Workspace:
+ * glam_pair_head_classes_workspace_bytes(R, Cs, e_dim, out_dim) = ((R + Cs) * e_dim + (e_dim + 1) * ceil(out_dim / 16) * 16) floats.
+ * Other operands, limits and statuses as glam_pair_head_fwd; R * Cs * out_dim < 2^63.  Every check comes before any device work and before
+ * any device pointer is looked at.  R == 0 or Cs == 0: GLAM_OK after the limit checks, nothing launched.  Forward only. */
+size_t glam_pair_head_classes_workspace_bytes(int64_t R, int64_t Cs, int e_dim, int out_dim);
+int glam_pair_head_classes_fwd(const float* flat_a, int64_t lda, const float* flat_b, int64_t ldb, const float* f, int64_t R, int64_t Cs,
+                               int hid, int F, const float* W0, int64_t ldw, const float* b0, int e_dim, const float* w1, const float* b1,
+                               int out_dim, int act, float slope, const int* classes, int n_sel, void* workspace, size_t workspace_bytes,
+                               int* cls, float* logp, float* sel, float* logits, void* stream);
+
 /* Screening hit lists: the best K candidates per query column, kept on the device while batches of scores stream past
  * (csrc/hits.hip).  State, owned by the caller: top_score f32[Qs,K] and top_id int32[Qs,K] — every list sorted best first, empty
  * slots (id -1, score NaN) at its end — and seen int64[1] in device memory, the number of candidates offered so far.

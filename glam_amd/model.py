@@ -284,22 +284,60 @@ def _class_head(model, what):
     return act
 
 
+def _fusion_columns(fusion, R, Cs, like):
+    """The steps' ``[R, Cs, 2]`` fusions side by side -> ``[R, Cs, 2 * steps]`` (zeros for an empty table), ``None`` without steps."""
+    if not fusion:
+        return None
+    if R * Cs == 0:
+        return like.new_zeros(R, Cs, 2 * len(fusion))
+    return ops.cat_cols([t.reshape(R * Cs, 2) for t in fusion]).view(R, Cs, 2 * len(fusion))
+
+
 def _table_head_factored(model, act, flat_a, flat_b, fusion, R, Cs):
-    """``ops.pair_head`` over the table: the two flat matrices as they are, ``f`` = the steps' ``[R, Cs, 2]`` fusions side by side."""
-    f = None
-    if fusion:
-        f = ops.cat_cols([t.reshape(R * Cs, 2) for t in fusion]).view(R, Cs, 2 * len(fusion))
-    return ops.pair_head(flat_a, flat_b, f, model.lin_out0.linear, model.lin_out1.linear, act[0], act[1])
+    """``ops.pair_head`` over the table: the two flat matrices as they are, ``f`` = ``_fusion_columns``."""
+    return ops.pair_head(flat_a, flat_b, _fusion_columns(fusion, R, Cs, flat_a), model.lin_out0.linear, model.lin_out1.linear, act[0], act[1])
 
 
 def _table_head_classes(model, act, flat_a, flat_b, fusion, R, Cs, classes, logits):
     """``ops.pair_head_classes`` over the table, on the operands of ``_table_head_factored`` -> ``ops.ClassTable``."""
-    f = None
-    if fusion and R and Cs:
-        f = ops.cat_cols([t.reshape(R * Cs, 2) for t in fusion]).view(R, Cs, 2 * len(fusion))
-    elif fusion:
-        f = flat_a.new_zeros(R, Cs, 2 * len(fusion))
-    return ops.pair_head_classes(flat_a, flat_b, f, model.lin_out0.linear, model.lin_out1.linear, act[0], act[1], classes, logits)
+    return ops.pair_head_classes(flat_a, flat_b, _fusion_columns(fusion, R, Cs, flat_a), model.lin_out0.linear, model.lin_out1.linear,
+                                 act[0], act[1], classes, logits)
+
+
+def _table_rows(a_rows, b_rows, fusion):
+    """The head's input over pair rows: ``cat[a_rows, b_rows, fusion_0, ...]``, every step's fusion of those pairs as ``[pairs, 2]``."""
+    return ops.cat_cols([a_rows, b_rows] + [f.reshape(a_rows.size(0), 2) for f in fusion])
+
+
+def _table_head_rows(model, a, b, fusion, R, Cs, per_block):
+    """The listed head (``lin_out0`` / ``lin_out1``, inside the caller's weight scope) over the table of ``a`` ``[R, hid]`` against ``b``
+    ``[Cs, hid]`` -> ``[R, Cs, out_dim]``.  ``per_block`` > 0 (both head norms per row): over blocks of that many table rows, row
+    ``(i - i0) * Cs + j`` of a block = ``cat[a[i], b[j], fusion_0[i, j], ...]``; ONE block that covers the table is returned as the head
+    wrote it.  ``per_block`` = 0 (a batch-less norm must see one column ``[R, .]`` at a time): once per column.  Empty: zeros, no head."""
+    head = lambda rows: model.lin_out1(model.lin_out0(rows))       # noqa: E731
+    if R == 0 or Cs == 0:
+        return a.new_zeros(R, Cs, model.lin_out1.linear.out_features)
+    if not per_block:
+        return torch.stack([head(_table_rows(a, b[j:j + 1].expand(R, -1).contiguous(), [f[:, j].contiguous() for f in fusion]))
+                            for j in range(Cs)], 1)
+    out = None if per_block >= R else a.new_empty(R, Cs, model.lin_out1.linear.out_features)
+    for i0 in range(0, R, per_block):
+        n = min(R, i0 + per_block) - i0
+        ai, fi = (a, fusion) if n == R else (a[i0:i0 + n], [f[i0:i0 + n] for f in fusion])          # (the whole table: no views)
+        block = head(_table_rows(ai.repeat_interleave(Cs, 0), b.repeat(n, 1), fi)).view(n, Cs, -1)
+        if out is None:
+            return block
+        out[i0:i0 + n] = block
+    return out
+
+
+def _table_guard(model, what, enc, head, classes=False, block_pairs=0):
+    """What opens a table call, in this order: the inference guard, the encoding, then the head — ``classes``: the class head's checks
+    (``_class_head``), else the ``head=`` keyword and with ``"factored"`` its checks -> ``(act, slope)`` of the kernel head, or None."""
+    model._encoding_guard(what, enc)
+    if classes:
+        return _class_head(model, what)
+    return _factored_head(model, what, block_pairs) if _check_head(what, head) else None
 
 
 def _check_score(what, score):
@@ -309,6 +347,19 @@ def _check_score(what, score):
         raise GlamHipError(f"{what}: score = {score!r} is not \"logit\" (the raw output column task) or \"logp\" (the log-softmax of class "
                            "task over the model's classes: ops.pair_head_classes)")
     return score == "logp"
+
+
+def _check_task(what, task, out_dim):
+    if isinstance(task, bool) or not isinstance(task, int) or not 0 <= task < out_dim:
+        raise GlamHipError(f"{what}: task = {task!r} is not one of the model's {out_dim} task column(s)")
+
+
+def _top_scores(classify, table, what, args, task, head, logp):
+    """``(scores, column)`` of one block of a top call: ``sel[..., 0]`` of the class route under the call's name (the log-softmax of
+    class ``task``, merged in place by stride), else column ``task`` of the table call's output."""
+    if logp:
+        return classify(what, *args, [task], False).sel, 0
+    return table(*args, head=head), task
 
 
 def _shared_index(model, given, P, Q, device, **words):
@@ -326,9 +377,35 @@ def _shared_index(model, given, P, Q, device, **words):
 def _host_sizes(enc):
     """``enc.sizes_host``: the row counts of an encoding's segments on the host — ONE read-back of ``sp.ptr`` per encoding, on first use."""
     if enc.sizes_host is None:
-        ptr = enc.sp.ptr.cpu().numpy().astype("int64")
-        enc.sizes_host = ptr[1:] - ptr[:-1]
+        enc.sizes_host = _segment_sizes(enc.sp)
     return enc.sizes_host
+
+
+def _segment_sizes(sp):
+    ptr = sp.ptr.cpu().numpy().astype("int64")          # (the read-back)
+    return ptr[1:] - ptr[:-1]
+
+
+def _cached_plan(plans, make_plan, Q, selection, sizes, bound=None, stale=None):
+    """The plan (``make_plan``: ``ops.panel_plan`` / ``ops.grid_plan``) of ``selection`` over ``Q`` segments out of the dict ``plans`` —
+    keyed by the validated selection, ``None`` = all in order — or made from ``sizes()`` and kept.  The selection is validated on the
+    host first (the sizes play no part in that); ``sizes`` is called after it, only for a plan that is missing or ``stale(plan)``.
+    ``bound``: the first-inserted plan leaves when the dict holds that many; ``None`` = unbounded."""
+    sel = None if selection is None else make_plan([0] * Q, selection).sel
+    key = None if sel is None else tuple(sel.tolist())
+    plan = plans.get(key)
+    if plan is None or (stale is not None and stale(plan)):
+        plan = make_plan(sizes(), sel)
+        while bound is not None and key not in plans and len(plans) >= bound:
+            plans.pop(next(iter(plans)))
+        plans[key] = plan
+    return plan
+
+
+def _step_fusions(steps, return_argmax, fuse):
+    """``fuse(step)`` for every step, in order — the step's fusion, or ``(fusion, argmax)`` with ``return_argmax`` -> the two lists."""
+    got = [fuse(s) for s in range(steps)]
+    return ([f for f, _ in got], [a for _, a in got]) if return_argmax else (got, [])
 
 
 class ProteinEncoding:
@@ -351,15 +428,7 @@ class ProteinEncoding:
         """``ops.PanelPlan`` of the selection ``proteins`` (``ops.panel_plan``: ``None`` = every protein in order) — from the cache when this
         selection was planned before — after filling ``sizes_host`` (the one read-back) and ``prosum`` (one segment-sum launch per step) if
         this is the encoding's first panel call.  The selection is validated on the host before anything is launched or read back."""
-        # (validated on the host first — the sizes play no part in that — and before the read-back below)
-        sel = None if proteins is None else ops.panel_plan([0] * self.num_graphs, proteins).sel
-        key = None if sel is None else tuple(sel.tolist())
-        plan = self.plans.get(key)
-        if plan is None:
-            plan = ops.panel_plan(_host_sizes(self), sel)
-            while len(self.plans) >= self._MAX_PLANS:
-                self.plans.pop(next(iter(self.plans)))
-            self.plans[key] = plan
+        plan = _cached_plan(self.plans, ops.panel_plan, self.num_graphs, proteins, lambda: _host_sizes(self), self._MAX_PLANS)
         if self.prosum is None:
             self.prosum = [ops.segment_pool(r, self.sp, "sum") for r in self.rows]
         return plan
@@ -425,6 +494,11 @@ class ArchitectureDTI(torch.nn.Module):
     def _screen_guard(self, what):
         _inference_guard(self, what, _DTI_WORDS)
 
+    def _encoding_guard(self, what, enc):
+        """The guard of a call that reads ``enc``: ``_screen_guard``, then the encoding is this model's and fresh."""
+        self._screen_guard(what)
+        _check_encoding(self, what, enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
+
     def encode_proteins(self, data_pro):
         """The protein tower, once, over the ``Q`` graphs of ``data_pro`` -> ``ProteinEncoding`` for ``screen``.  ``eval()`` mode under
         ``torch.no_grad()``; valid until a protein-side parameter or buffer changes."""
@@ -451,8 +525,7 @@ class ArchitectureDTI(torch.nn.Module):
         """``screen`` under the name ``what`` -> ``(out, contacts, fusion, rows, msp, index)``: also the steps' ``[P, 2]`` fusions, the
         ligand rows every step's fusion read (a step writes new rows: the earlier ones stay), the ligands' ``SegmentPtr`` and the
         validated index (``explain.explain_pair``)."""
-        self._screen_guard(what)
-        _check_encoding(self, what, enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
+        self._encoding_guard(what, enc)
         m = _Tower(self, "mol", data_mol)
         msp = ops.segment_ptr(data_mol.batch, m.n)
         index = ops.pair_index(pro_of_pair, msp.B, enc.num_graphs, default="single")       # host-side, before the first launch
@@ -471,17 +544,13 @@ class ArchitectureDTI(torch.nn.Module):
 
     def _ligand_walk(self, m, return_argmax, fuse):
         """The ligand tower ``m`` against an encoding: ``fuse(rows, step)`` after every step -> the steps' fusions and contacts."""
-        _embed(m)
-        fusion, contacts = [], []
-        for i in range(self.message_steps):
+        def step_then_fuse(i):
             with ops.block_feeds_itself(i + 1 < self.message_steps):
                 m.step()
-            f = fuse(m.x, i)
-            if return_argmax:
-                f, a = f
-                contacts.append(a)
-            fusion.append(f)
-        return fusion, contacts
+            return fuse(m.x, i)
+
+        _embed(m)
+        return _step_fusions(self.message_steps, return_argmax, step_then_fuse)
 
     def _panel_head_in_one_pass(self):
         """Whether the head may run once over the ``L * Qs`` rows of a panel: both of its norms are per row in ``eval()`` (``_None``,
@@ -511,27 +580,17 @@ class ArchitectureDTI(torch.nn.Module):
         rows, no ``[L * Qs, e_dim]`` hidden matrix; within the same parity bound, not the bits of ``"rows"``) and is refused — before the
         first launch, with the reason — for a norm in the head, an ``end_act`` other than ``_None`` / ``ReLU`` / ``LeakyReLU`` / ``RReLU``
         and ``out_dim > 8``."""
-        self._screen_guard("screen_panel")
-        _check_encoding(self, "screen_panel", enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
-        act = _factored_head(self, "screen_panel") if _check_head("screen_panel", head) else None
+        act = _table_guard(self, "screen_panel", enc, head)
         plan = enc.panel(proteins)                                 # host-side checks, before the first launch
         m = _Tower(self, "mol", data_mol)
         msp = ops.segment_ptr(data_mol.batch, m.n)
         L, Qs = msp.B, plan.Qs
         with ops.weight_scope():
             fusion, contacts, outm, outp = self._panel_walk(m, data_mol, enc, plan, return_argmax)
-            if L == 0 or Qs == 0:
-                out = outm.new_zeros(L, Qs, self.lin_out1.linear.out_features)
-            elif act:
+            if act and L and Qs:
                 out = _table_head_factored(self, act, outm, outp, fusion, L, Qs)
-            elif self._panel_head_in_one_pass():
-                # ligand-major rows: row l * Qs + j = cat[outm[l], flat[sel[j]], fusion_0[l, j], ...]
-                rows = ops.cat_cols([outm.repeat_interleave(Qs, 0), outp.repeat(L, 1)] + [f.reshape(L * Qs, 2) for f in fusion])
-                out = self.lin_out1(self.lin_out0(rows)).view(L, Qs, -1)
-            else:
-                cols = [self.lin_out1(self.lin_out0(ops.cat_cols([outm, outp[j:j + 1].expand(L, -1).contiguous()]
-                                                                 + [f[:, j].contiguous() for f in fusion]))) for j in range(Qs)]
-                out = torch.stack(cols, 1)
+            else:          # ligand-major rows, all in one block: row l * Qs + j = cat[outm[l], flat[sel[j]], fusion_0[l, j], ...]
+                out = _table_head_rows(self, outm, outp, fusion, L, Qs, L if self._panel_head_in_one_pass() else 0)
         return (out, contacts) if return_argmax else out
 
     def classify_panel(self, data_mol, enc, proteins=None, classes=(), return_logits=False):
@@ -546,9 +605,7 @@ class ArchitectureDTI(torch.nn.Module):
         return self._classify_panel("classify_panel", data_mol, enc, proteins, classes, return_logits)
 
     def _classify_panel(self, what, data_mol, enc, proteins, classes, return_logits):
-        self._screen_guard(what)
-        _check_encoding(self, what, enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
-        act = _class_head(self, what)
+        act = _table_guard(self, what, enc, None, classes=True)
         chosen = ops.class_selection(classes, self.lin_out1.linear.out_features, what)
         plan = enc.panel(proteins)                                 # host-side checks, before the first launch
         m = _Tower(self, "mol", data_mol)
@@ -571,27 +628,16 @@ class ArchitectureDTI(torch.nn.Module):
         ``sel[..., 0]`` is merged in place."""
         k = hits.check_k(k, "screen_top")
         logp = _check_score("screen_top", score)
-        out_dim = self.lin_out1.linear.out_features
-        if isinstance(task, bool) or not isinstance(task, int) or not 0 <= task < out_dim:
-            raise GlamHipError(f"screen_top: task = {task!r} is not one of the model's {out_dim} task column(s)")
+        _check_task("screen_top", task, self.lin_out1.linear.out_features)
         top = None
         for item in batches:
             data_mol, ids = item if isinstance(item, tuple) else (item, None)
-            if logp:             # sel[..., 0] = the log-softmax of class task, merged in place by stride
-                out, col = self._classify_panel("screen_top", data_mol, enc, proteins, [task], False).sel, 0
-            else:
-                out, col = self.screen_panel(data_mol, enc, proteins, head=head), task
+            out, col = _top_scores(self._classify_panel, self.screen_panel, "screen_top", (data_mol, enc, proteins), task, head, logp)
             if top is None:
                 top = hits.HitList(out.size(1), k, out.device, largest)
             top.update(out, ids, col)
         if top is None:          # an empty stream: empty lists, after the checks a first batch would have met
-            what = "screen_top" if logp else "screen_panel"
-            self._screen_guard(what)
-            _check_encoding(self, what, enc, ProteinEncoding, self._protein_stamp(), "rows", _DTI_WORDS)
-            if logp:
-                _class_head(self, what)
-            elif _check_head(what, head):
-                _factored_head(self, what)
+            _table_guard(self, "screen_top" if logp else "screen_panel", enc, head, classes=logp)
             top = hits.HitList(ops.panel_plan([0] * enc.num_graphs, proteins).Qs, k, enc.flat.device, largest)     # (host only: no read-back)
         return top
 
@@ -636,15 +682,13 @@ class ArchitectureDTI(torch.nn.Module):
         """The ``ops.PanelPlan`` of ``proteins`` over the graphs of ``data_pro``, kept ON the batch object (per selection): the first
         call reads the proteins' sizes back once, a later step — or a capture — on the same batch finds the plan and its device copies."""
         cache = data_pro.__dict__.setdefault("_glam_panel_plans", {"sizes": None, "plans": {}})
-        sel = None if proteins is None else ops.panel_plan([0] * psp.B, proteins).sel          # (validated before the read-back)
-        key = None if sel is None else tuple(sel.tolist())
-        plan = cache["plans"].get(key)
-        if plan is None or plan.Q != psp.B or plan.N != psp.N:
+
+        def sizes():          # (kept with the plans, and read again when the batch no longer holds what they say)
             if cache["sizes"] is None or len(cache["sizes"]) != psp.B or int(cache["sizes"].sum()) != psp.N:
-                ptr = psp.ptr.cpu().numpy().astype("int64")
-                cache["sizes"] = ptr[1:] - ptr[:-1]
-            plan = cache["plans"][key] = ops.panel_plan(cache["sizes"], sel)
-        return plan
+                cache["sizes"] = _segment_sizes(psp)
+            return cache["sizes"]
+
+        return _cached_plan(cache["plans"], ops.panel_plan, psp.B, proteins, sizes, stale=lambda plan: plan.Q != psp.B or plan.N != psp.N)
 
     def forward_panel(self, data_mol, data_pro, proteins=None, plan=None):
         """``model(M, P)`` as a table -> ``[L, Qs, out_dim]``: entry ``[l, j]`` is row ``l * Qs + j`` of the expanded batch ``M`` = ligand
@@ -671,8 +715,7 @@ class ArchitectureDTI(torch.nn.Module):
         _shared_guard(self, _DTI_PANEL_WORDS, "forward_panel")
         m, p = _Tower(self, "mol", data_mol), _Tower(self, "pro", data_pro)
         if plan is not None:
-            if not isinstance(plan, ops.PanelPlan):
-                raise GlamHipError("forward_panel: plan must come from ops.panel_plan (the kernel trusts its table)")
+            ops._require_plan("forward_panel", plan, ops.PanelPlan, "panel_plan")
             if proteins is not None:
                 raise GlamHipError("forward_panel: pass the selection (proteins) or the plan made from it, not both")
             if (p.n is not None and plan.Q != p.n) or plan.N != data_pro.x.size(0):
@@ -690,8 +733,7 @@ class ArchitectureDTI(torch.nn.Module):
             if L == 0 or Qs == 0:
                 return outm.new_zeros(L, Qs, self.lin_out1.linear.out_features)
             # ligand-major rows: row l * Qs + j = cat[mol_flat[l], pro_flat[sel[j]], fusion_0[l, j], ...]
-            rows = ops.cat_cols([ops.pair_rows(outm, lig), ops.pair_rows(outp, col)] + [f.reshape(L * Qs, 2) for f in fusion])
-            return self.lin_out1(self.lin_out0(rows)).view(L, Qs, -1)
+            return self.lin_out1(self.lin_out0(_table_rows(ops.pair_rows(outm, lig), ops.pair_rows(outp, col), fusion))).view(L, Qs, -1)
 
 
 class DrugEncoding:
@@ -717,15 +759,7 @@ class DrugEncoding:
         """``ops.GridPlan`` of the column selection ``cols`` (``ops.grid_plan``: ``None`` = every drug in order) — from the cache when this
         selection was planned before — after filling ``sizes_host`` (the one read-back) and ``sum1`` / ``sum2`` if this is the encoding's
         first matrix call.  The selection is validated on the host before anything is launched or read back."""
-        # (validated on the host first — the sizes play no part in that — and before the read-back below)
-        sel = None if cols is None else ops.grid_plan([0] * self.num_graphs, cols).sel
-        key = None if sel is None else tuple(sel.tolist())
-        plan = self.plans.get(key)
-        if plan is None:
-            plan = ops.grid_plan(_host_sizes(self), sel)
-            while len(self.plans) >= self._MAX_PLANS:
-                self.plans.pop(next(iter(self.plans)))
-            self.plans[key] = plan
+        plan = _cached_plan(self.plans, ops.grid_plan, self.num_graphs, cols, lambda: _host_sizes(self), self._MAX_PLANS)
         if self.sum1 is None:
             self.sum1 = [ops.segment_pool(r, self.sp, "sum") for r in self.rows1]
             self.sum2 = [ops.segment_pool(r, self.sp, "sum") for r in self.rows2]
@@ -789,6 +823,11 @@ class ArchitectureDDI(torch.nn.Module):
     def _pairs_guard(self, what):
         _inference_guard(self, what, _DDI_WORDS)
 
+    def _encoding_guard(self, what, enc):
+        """The guard of a call that reads ``enc``: ``_pairs_guard``, then the encoding is this model's and fresh."""
+        self._pairs_guard(what)
+        _check_encoding(self, what, enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
+
     def encode_drugs(self, data):
         """Both towers, once, over the ``Q`` graphs of ``data`` -> ``DrugEncoding`` for ``score_pairs``.  ``eval()`` mode under
         ``torch.no_grad()``; valid until a parameter or buffer of either tower changes."""
@@ -821,19 +860,13 @@ class ArchitectureDDI(torch.nn.Module):
     def _score_pairs(self, what, enc, first, second, return_argmax):
         """``score_pairs`` under the name ``what`` -> ``(out, contacts, fusion, i1, i2)``: the steps' ``[P, 2]`` fusions and the two validated
         indices kept (``explain.explain_pair``)."""
-        self._pairs_guard(what)
-        _check_encoding(self, what, enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
+        self._encoding_guard(what, enc)
         Q = enc.num_graphs
         P = ops.pair_count(first)
         i1 = ops.pair_index(first, P, Q, name="first", over="drugs")               # host-side, before the first launch
         i2 = ops.pair_index(second, P, Q, name="second", over="drugs")
-        fusion, contacts = [], []
-        for s in range(self.message_steps):
-            f = dot_and_global_pool2_gather(enc.rows1[s], enc.rows2[s], enc.sp, enc.sp, i1, i2, return_argmax)
-            if return_argmax:
-                f, a = f
-                contacts.append(a)
-            fusion.append(f)
+        fusion, contacts = _step_fusions(self.message_steps, return_argmax, lambda s: dot_and_global_pool2_gather(
+            enc.rows1[s], enc.rows2[s], enc.sp, enc.sp, i1, i2, return_argmax))
         dev = enc.flat1.device
         o1 = enc.flat1.index_select(0, i1.on(dev))
         o2 = enc.flat2.index_select(0, i2.on(dev))
@@ -875,13 +908,8 @@ class ArchitectureDDI(torch.nn.Module):
         """The fusion walk of ``score_matrix``: one second-side-stationary fusion per step over the whole table ->
         ``(fusion, contacts, o1 [R, hid], o2 [Cs, hid])``."""
         plan = enc.grid(sel)
-        fusion, contacts = [], []
-        for s in range(self.message_steps):
-            f = dot_and_global_pool2_grid(enc.rows1[s], enc.rows2[s], enc.sp, enc.sp, plan, index, enc.sum1[s], enc.sum2[s], return_argmax)
-            if return_argmax:
-                f, a = f
-                contacts.append(a)
-            fusion.append(f)
+        fusion, contacts = _step_fusions(self.message_steps, return_argmax, lambda s: dot_and_global_pool2_grid(
+            enc.rows1[s], enc.rows2[s], enc.sp, enc.sp, plan, index, enc.sum1[s], enc.sum2[s], return_argmax))
         dev = enc.flat1.device
         o1 = enc.flat1 if index is None else enc.flat1.index_select(0, index.on(dev))              # [R, hid]
         o2 = enc.flat2.index_select(0, plan.on(dev)[0])                                            # [Cs, hid]
@@ -905,30 +933,15 @@ class ArchitectureDDI(torch.nn.Module):
         depend on the selection around it; within the same parity bound, not the bits of ``"rows"``.  It is refused — before the first
         launch, with the reason — for a norm in the head, an ``end_act`` other than ``_None`` / ``ReLU`` / ``LeakyReLU`` / ``RReLU``,
         ``out_dim > 8`` and ``block_pairs != 0`` (it has no blocks)."""
-        self._pairs_guard("score_matrix")
-        _check_encoding(self, "score_matrix", enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
-        act = _factored_head(self, "score_matrix", block_pairs) if _check_head("score_matrix", head) else None
+        act = _table_guard(self, "score_matrix", enc, head, block_pairs=block_pairs)
         R, Cs, index, sel = self._matrix_selection(enc, rows, cols)
         per_block = None if act else self._matrix_block_rows(block_pairs, R, Cs)
         fusion, contacts, o1, o2 = self._matrix_walk(enc, index, sel, return_argmax)
-        out_dim = self.lin_out1.linear.out_features
         with ops.weight_scope():
-            if R == 0 or Cs == 0:
-                out = o1.new_zeros(R, Cs, out_dim)
-            elif act:
+            if act and R and Cs:
                 out = _table_head_factored(self, act, o1, o2, fusion, R, Cs)
-            elif self._matrix_head_in_one_pass():
-                # row-major pair rows: row (i - i0) * Cs + j of a block = cat[flat1[rows[i]], flat2[cols[j]], fusion_0[i, j], ...]
-                out = o1.new_empty(R, Cs, out_dim)
-                for i0 in range(0, R, per_block):
-                    i1 = min(R, i0 + per_block)
-                    block = ops.cat_cols([o1[i0:i1].repeat_interleave(Cs, 0), o2.repeat(i1 - i0, 1)]
-                                         + [f[i0:i1].reshape((i1 - i0) * Cs, 2) for f in fusion])
-                    out[i0:i1] = self.lin_out1(self.lin_out0(block)).view(i1 - i0, Cs, out_dim)
-            else:
-                per_col = [self.lin_out1(self.lin_out0(ops.cat_cols([o1, o2[j:j + 1].expand(R, -1).contiguous()]
-                                                                    + [f[:, j].contiguous() for f in fusion]))) for j in range(Cs)]
-                out = torch.stack(per_col, 1)
+            else:          # row-major pair rows: row (i - i0) * Cs + j of a block = cat[flat1[rows[i]], flat2[cols[j]], fusion_0[i, j], ...]
+                out = _table_head_rows(self, o1, o2, fusion, R, Cs, per_block if self._matrix_head_in_one_pass() else 0)
         return (out, contacts) if return_argmax else out
 
     def classify_matrix(self, enc, rows=None, cols=None, classes=(), return_logits=False):
@@ -943,9 +956,7 @@ class ArchitectureDDI(torch.nn.Module):
         return self._classify_matrix("classify_matrix", enc, rows, cols, classes, return_logits)
 
     def _classify_matrix(self, what, enc, rows, cols, classes, return_logits):
-        self._pairs_guard(what)
-        _check_encoding(self, what, enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
-        act = _class_head(self, what)
+        act = _table_guard(self, what, enc, None, classes=True)
         chosen = ops.class_selection(classes, self.lin_out1.linear.out_features, what)
         R, Cs, index, sel = self._matrix_selection(enc, rows, cols)
         fusion, _, o1, o2 = self._matrix_walk(enc, index, sel, False)
@@ -972,31 +983,19 @@ class ArchitectureDDI(torch.nn.Module):
         ``sel[..., 0]`` is merged in place.  Its entries do not depend on the block either."""
         k = hits.check_k(k, "matrix_top")
         logp = _check_score("matrix_top", score)
-        out_dim = self.lin_out1.linear.out_features
-        if isinstance(task, bool) or not isinstance(task, int) or not 0 <= task < out_dim:
-            raise GlamHipError(f"matrix_top: task = {task!r} is not one of the model's {out_dim} task column(s)")
+        _check_task("matrix_top", task, self.lin_out1.linear.out_features)
         if isinstance(block_rows, bool) or not isinstance(block_rows, int) or block_rows < 0:
             raise GlamHipError(f"matrix_top: block_rows = {block_rows!r} must be 0 (choose) or the row drugs per block")
         what = "matrix_top" if logp else "score_matrix"
-        self._pairs_guard(what)
-        _check_encoding(self, what, enc, DrugEncoding, self._drug_stamp(), "rows1", _DDI_WORDS)
-        if logp:
-            _class_head(self, what)
-        elif _check_head(what, head):
-            _factored_head(self, what)
-        Q = enc.num_graphs
-        R = ops.pair_count(rows, None, Q)
-        ids = ops.pair_index(rows, R, Q, name="rows", over="drugs").host                            # host-side, before the first launch
-        sel = None if cols is None else ops.grid_plan([0] * Q, cols).sel
-        Cs = Q if sel is None else int(sel.shape[0])
+        _table_guard(self, what, enc, head, classes=logp)
+        R, Cs, index, sel = self._matrix_selection(enc, rows, cols)                              # host-side, before the first launch
+        ids = (index or ops.pair_index(None, R, R)).host                                         # (rows=None: every drug in order)
         per_block = block_rows or max(1, min(R, self._TOP_BLOCK_PAIRS // max(Cs, 1)))
         top = hits.HitList(Cs, k, enc.flat1.device, largest)
         for i0 in range(0, R, per_block):
             block = ids[i0:i0 + per_block]
-            if logp:             # sel[..., 0] = the log-softmax of class task, merged in place by stride
-                top.update(self._classify_matrix(what, enc, block, sel, [task], False).sel, block, 0)
-            else:
-                top.update(self.score_matrix(enc, block, sel, head=head), block, task)
+            out, col = _top_scores(self._classify_matrix, self.score_matrix, what, (enc, block, sel), task, head, logp)
+            top.update(out, block, col)
         return top
 
     # ---- training on shared drugs: each tower runs once per DISTINCT drug of its side of the step ----------------------------

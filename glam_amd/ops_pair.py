@@ -3,9 +3,10 @@
 Part of ``glam_amd.ops`` (every public name here is re-exported there: ``from glam_amd import ops; ops.pair_pool(...)``).
 
 The next fusion call is built from the helpers of this file, not from a copy of the call before it: ``host_ints`` validates a host
-vector of integers, ``_Staged`` keeps its per-device copies, ``_operands`` checks the two matrices, ``_outputs`` allocates what a launch
-writes, ``pair_count`` is "P of whichever index is given", and a Function that hands its inputs back is ``_alias_fwd`` /
-``_alias_bwd`` under a wrapper that ends in ``_apply_aliasing``."""
+vector of integers, ``_Staged`` keeps its per-device copies, ``_operands`` checks the two matrices, ``_outputs`` / ``_workspace`` allocate
+what a launch writes (``_all_empty``: with no row on one side), ``pair_count`` is "P of whichever index is given", the shared refusals are
+``_inference_only`` / ``_require_plan`` / ``_check_sums_slab``, a plan starts from ``_plan_sizes`` / ``_plan_selection`` / ``_first_rows``, and a
+Function that hands its inputs back is ``_alias_fwd`` / ``_alias_bwd`` under a wrapper that ends in ``_apply_aliasing``."""
 from __future__ import annotations
 
 import ctypes
@@ -95,7 +96,54 @@ def _outputs(shape, dev, arg=True, D=None, ws_bytes=None):
     return (torch.empty(*shape, 2, dtype=torch.float32, device=dev),
             torch.empty(*shape, 2, dtype=torch.int32, device=dev) if arg else None,
             None if D is None else torch.empty(*shape, 2, D, dtype=torch.float32, device=dev),
-            None if ws_bytes is None else torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev))
+            None if ws_bytes is None else _workspace(ws_bytes, dev))
+
+
+def _workspace(nbytes, dev):
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+
+
+def _all_empty(out, arg):          # no row on one side: every pair is empty (and the empty matrix has no address to pass to a launch)
+    out.zero_()
+    if arg is not None:
+        arg.fill_(-1)
+
+
+def _inference_only(who, tensors, instead):
+    """The refusal of a call without a backward when autograd would follow one of ``tensors``; ``instead``: what trains."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise GlamHipError(f"{who} is inference only (no backward): call it under torch.no_grad(); {instead}")
+
+
+def _require_plan(who, plan, cls, maker):
+    if not isinstance(plan, cls):
+        raise GlamHipError(f"{who}: plan must come from ops.{maker} (the kernel trusts its table)")
+
+
+def _check_sums_slab(who, D, dev, sums, slab, per_wave):
+    """What a caller may hand a stationary launch: ``sums`` — ``(name, tensor or None, rows)`` each, ``[rows, D]`` on ``dev`` — and a slab."""
+    for name, t, rows in sums:
+        if t is not None and (t.dim() != 2 or tuple(t.shape) != (rows, D) or t.device != dev):
+            raise GlamHipError(f"{who}: {name} must be the [{rows}, {D}] column sums on {dev}, got {tuple(t.shape)} on {t.device}")
+    if int(slab) < 0:
+        raise GlamHipError(f"{who}: slab must be 0 (choose) or the {per_wave} per wave, got {slab}")
+
+
+def _plan_sizes(who, sizes_host, nouns):
+    """The sizes a plan is built over (``nouns``: what ``who``'s messages call them) as a host int64 vector."""
+    return host_ints(sizes_host, "sizes", None, wrong=f"{who}: {nouns} must be a vector of non-negative integers",
+                     on_device=f"{who}: {nouns} live on a device: the plan is built on the host — pass their host copy").astype(np.int64)
+
+
+def _plan_selection(name, entries, selection, Q):
+    return np.arange(Q, dtype=np.int32) if selection is None else host_ints(selection, name, entries, below=Q).astype(np.int32)
+
+
+def _first_rows(sizes, too_many):          # -> (the offsets of the segments' rows, int64 [Q + 1]; N, their last: below 2^31 - 1)
+    first = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(sizes, dtype=np.int64)])
+    if int(first[-1]) >= 2 ** 31 - 1:
+        raise IndexError(too_many)
+    return first, int(first[-1])
 
 
 def _alias_fwd(ctx, out, a_in, b_in, with_identity):
@@ -290,9 +338,7 @@ def pair_pool_indexed(mol_out, pro_out, msp, psp, pro_of_pair=None, return_argma
     ``pro_of_pair``: see ``pair_index`` (``None`` = identity).  Inference only: there is no backward (training is ``ops.pair_pool``)."""
     P, Q = msp.B, psp.B
     index = pair_index(pro_of_pair, P, Q)
-    if torch.is_grad_enabled() and (mol_out.requires_grad or pro_out.requires_grad):
-        raise GlamHipError("pair_pool_indexed is inference only (no backward): call it under torch.no_grad(); the training route is "
-                           "ops.pair_pool on one protein graph per pair")
+    _inference_only("pair_pool_indexed", (mol_out, pro_out), "the training route is ops.pair_pool on one protein graph per pair")
     mol, pro = _operands("pair_pool_indexed", mol_out, pro_out, msp, psp, "mol_out", "pro_out")
     D = mol.size(1)
     lib = _lib.api()
@@ -317,11 +363,7 @@ class PanelPlan(_Staged):
 
     def __init__(self, sel, sizes):
         self.sel, self.Qs, self.Q = sel, int(sel.shape[0]), int(sizes.shape[0])
-        first = np.zeros(self.Q + 1, dtype=np.int64)
-        np.cumsum(sizes, out=first[1:])
-        if int(first[-1]) >= 2 ** 31 - 1:
-            raise IndexError("panel_plan: the proteins hold 2^31 residue rows or more")
-        self.N = int(first[-1])
+        first, self.N = _first_rows(sizes, "panel_plan: the proteins hold 2^31 residue rows or more")
         n_chunks = (sizes[sel] + PANEL_CHUNK - 1) // PANEL_CHUNK                     # per selection
         chunk_ptr = np.zeros(self.Qs + 1, dtype=np.int64)
         np.cumsum(n_chunks, out=chunk_ptr[1:])
@@ -370,13 +412,8 @@ def panel_plan(sizes_host, proteins=None):
     ``Q`` in order, or a host sequence / numpy array / CPU tensor of integers in ``[0, Q)``, in any order, duplicates allowed;
     ``IndexError`` for a wrong dtype or an entry outside ``[0, Q)``; a device tensor is refused (validating it would be a hidden
     read-back)."""
-    sizes = host_ints(sizes_host, "sizes", None, wrong="panel_plan: the proteins' sizes must be a vector of non-negative integers",
-                      on_device="panel_plan: the proteins' sizes live on a device: the plan is built on the host — pass their host copy")
-    sizes = sizes.astype(np.int64)
-    Q = int(sizes.shape[0])
-    if proteins is None:
-        return PanelPlan(np.arange(Q, dtype=np.int32), sizes)
-    return PanelPlan(host_ints(proteins, "proteins", "be a vector of protein numbers", below=Q).astype(np.int32), sizes)
+    sizes = _plan_sizes("panel_plan", sizes_host, "the proteins' sizes")
+    return PanelPlan(_plan_selection("proteins", "be a vector of protein numbers", proteins, int(sizes.shape[0])), sizes)
 
 
 def pair_pool_panel(mol_out, pro_out, msp, psp, plan, molsum=None, prosum=None, return_argmax=False, slab=0):
@@ -388,37 +425,37 @@ def pair_pool_panel(mol_out, pro_out, msp, psp, plan, molsum=None, prosum=None, 
     / ``prosum`` ``[Q, D]``: the segments' column sums (``segment_pool(x, sp, "sum")``), computed here when missing — a caller that
     keeps the proteins keeps ``prosum`` too.  ``slab``: ligands per wave, 0 = the library chooses.  Widths 1..128.  Inference only:
     there is no backward (training is ``ops.pair_pool`` / ``ops.pair_pool_shared``)."""
-    if not isinstance(plan, PanelPlan):
-        raise GlamHipError("pair_pool_panel: plan must come from ops.panel_plan (the kernel trusts its table)")
-    L, Q, Qs = msp.B, psp.B, plan.Qs
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (mol_out, pro_out, molsum, prosum)):
-        raise GlamHipError("pair_pool_panel is inference only (no backward): call it under torch.no_grad(); the training routes are "
-                           "ops.pair_pool on one protein graph per pair and ops.pair_pool_shared on proteins held once")
-    if plan.Q != Q or plan.N != psp.N:
-        raise GlamHipError(f"pair_pool_panel: the plan was made for {plan.Q} proteins of {plan.N} residue rows, the encoding holds {Q} of {psp.N}")
+    _require_plan("pair_pool_panel", plan, PanelPlan, "panel_plan")
+    _inference_only("pair_pool_panel", (mol_out, pro_out, molsum, prosum), "the training routes are ops.pair_pool on one protein graph "
+                    "per pair and ops.pair_pool_shared on proteins held once")
+    if plan.Q != psp.B or plan.N != psp.N:
+        raise GlamHipError(f"pair_pool_panel: the plan was made for {plan.Q} proteins of {plan.N} residue rows, the encoding holds {psp.B} of "
+                           f"{psp.N}")
     mol, pro = _operands("pair_pool_panel", mol_out, pro_out, msp, psp, "mol_out", "pro_out")
-    D, dev = mol.size(1), mol.device
-    for name, t, rows in (("molsum", molsum, L), ("prosum", prosum, Q)):
-        if t is not None and (t.dim() != 2 or tuple(t.shape) != (rows, D) or t.device != dev):
-            raise GlamHipError(f"pair_pool_panel: {name} must be the [{rows}, {D}] column sums on {dev}, got {tuple(t.shape)} on {t.device}")
-    if int(slab) < 0:
-        raise GlamHipError(f"pair_pool_panel: slab must be 0 (choose) or the ligands per wave, got {slab}")
-    lib = _lib.api()
+    D = mol.size(1)
+    _check_sums_slab("pair_pool_panel", D, mol.device, (("molsum", molsum, msp.B), ("prosum", prosum, psp.B)), slab, "ligands")
     if _lib.load().glam_pair_pool_panel_supported(D) != 0:          # (a status: the raw binding hands it back)
         raise GlamHipError(f"pair_pool_panel: width {D} is outside the kernel table (1..128)")
-    out, arg, _, _ = _outputs((L, Qs), dev, arg=return_argmax)
-    if L and Qs and (msp.N == 0 or psp.N == 0):          # no row on one side: every pair is empty (and the empty matrix has no address to pass)
-        out.zero_()
-        if return_argmax:
-            arg.fill_(-1)
-    elif L and Qs:
-        molsum = f32c(molsum, "molsum") if molsum is not None else segment_pool(mol, msp, "sum")
-        prosum = f32c(prosum, "prosum") if prosum is not None else segment_pool(pro, psp, "sum")
-        sel, work = plan.on(dev)
-        ws = torch.empty(max(lib.glam_pair_pool_panel_workspace_bytes(plan.total_chunks, L), 16), dtype=torch.uint8, device=dev)
-        lib.glam_pair_pool_panel_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(work), plan.total_chunks, ptr(sel), Qs, L, Q, D,
-                                     ptr(molsum), ptr(prosum), int(slab), ptr(out), ptr(arg), ptr(ws), ws.numel(), stream())
+    out, arg, _, _ = _panel_fwd(mol, pro, msp, psp, plan, molsum, prosum, slab, return_argmax)
     return (out, arg) if return_argmax else out
+
+
+def _panel_fwd(mol, pro, msp, psp, plan, molsum, prosum, slab, want_arg):
+    """The launches of a panel forward on checked operands -> ``(out, arg, molsum, prosum)``: the column sums that are not given, then
+    ``glam_pair_pool_panel_fwd``; with no row on one side the all-empty fill, and ``None`` for the sums (so too for a table of no entry)."""
+    L, Q, Qs, D, dev = msp.B, psp.B, plan.Qs, mol.size(1), mol.device
+    out, arg, _, _ = _outputs((L, Qs), dev, arg=want_arg)
+    if L == 0 or Qs == 0 or msp.N == 0 or psp.N == 0:
+        _all_empty(out, arg)
+        return out, arg, None, None
+    lib = _lib.api()
+    molsum = f32c(molsum, "molsum") if molsum is not None else segment_pool(mol, msp, "sum")
+    prosum = f32c(prosum, "prosum") if prosum is not None else segment_pool(pro, psp, "sum")
+    sel, work = plan.on(dev)
+    ws = _workspace(lib.glam_pair_pool_panel_workspace_bytes(plan.total_chunks, L), dev)
+    lib.glam_pair_pool_panel_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(work), plan.total_chunks, ptr(sel), Qs, L, Q, D,
+                                 ptr(molsum), ptr(prosum), int(slab), ptr(out), ptr(arg), ptr(ws), ws.numel(), stream())
+    return out, arg, molsum, prosum
 
 
 # --------------------------------------------------------------------------------------
@@ -429,22 +466,12 @@ class _PairPoolPanelShared(torch.autograd.Function):
     def forward(ctx, mol, pro, msp, psp, plan, with_identity=False):
         mol_in, pro_in = mol, pro
         mol, pro = _operands("pair_pool_panel_shared", mol, pro, msp, psp, "mol_out", "pro_out")
-        L, Q, Qs, D, dev = msp.B, psp.B, plan.Qs, mol.size(1), mol.device
-        sel, work = plan.on(dev)
-        order, qptr = plan.by_protein().on(dev)
-        out, arg, _, _ = _outputs((L, Qs), dev)
-        # (no row on one side: every pair is empty, and the empty matrix has no address to pass)
-        ctx.rows = L > 0 and Qs > 0 and msp.N > 0 and psp.N > 0
-        if ctx.rows:
-            lib = _lib.api()
-            molsum, prosum = segment_pool(mol, msp, "sum"), segment_pool(pro, psp, "sum")
-            ws = torch.empty(max(lib.glam_pair_pool_panel_workspace_bytes(plan.total_chunks, L), 16), dtype=torch.uint8, device=dev)
-            lib.glam_pair_pool_panel_fwd(ptr(mol), ptr(pro), ptr(msp.ptr), ptr(psp.ptr), ptr(work), plan.total_chunks, ptr(sel), Qs, L, Q, D,
-                                         ptr(molsum), ptr(prosum), 0, ptr(out), ptr(arg), ptr(ws), ws.numel(), stream())
-        else:
-            out.zero_()
-            arg.fill_(-1)
-            molsum, prosum = mol.new_zeros(L, D), pro.new_zeros(Q, D)
+        sel, _ = plan.on(mol.device)
+        order, qptr = plan.by_protein().on(mol.device)
+        out, arg, molsum, prosum = _panel_fwd(mol, pro, msp, psp, plan, None, None, 0, True)
+        ctx.rows = molsum is not None          # (else an empty table, or only empty pairs: nothing for a backward to read)
+        if not ctx.rows:
+            molsum, prosum = mol.new_zeros(msp.B, mol.size(1)), pro.new_zeros(psp.B, mol.size(1))
         ctx.save_for_backward(mol, pro, arg, molsum, prosum, sel, order, qptr)
         ctx.sps = (msp, psp)
         return _alias_fwd(ctx, out, mol_in, pro_in, with_identity)
@@ -476,8 +503,7 @@ def pair_pool_panel_shared(mol_out, pro_out, msp, psp, plan, with_identity=False
     first, eager, visit and a hipGraph capture needs them to exist.  Widths 1..128.  ``with_identity``: as ``pair_pool`` — ``(out,
     mol_out, pro_out)`` with the two matrices handed back through the node (both require grad, fp32): its backward launch then adds
     their later gradients itself; the plain triple otherwise."""
-    if not isinstance(plan, PanelPlan):
-        raise GlamHipError("pair_pool_panel_shared: plan must come from ops.panel_plan (the kernel trusts its table)")
+    _require_plan("pair_pool_panel_shared", plan, PanelPlan, "panel_plan")
     if plan.Q != psp.B or plan.N != psp.N:
         raise GlamHipError(f"pair_pool_panel_shared: the plan was made for {plan.Q} proteins of {plan.N} residue rows, the operands hold "
                            f"{psp.B} of {psp.N}")
@@ -588,9 +614,7 @@ def pair_pool_gather(x1, x2, sp1, sp2, idx1=None, idx2=None, return_argmax=False
     P = pair_count(idx1, idx2, Q1)
     i1 = None if idx1 is None and Q1 == P else pair_index(idx1, P, Q1, name="idx1", over="segments of x1")
     i2 = None if idx2 is None and Q2 == P else pair_index(idx2, P, Q2, name="idx2", over="segments of x2")
-    if torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
-        raise GlamHipError("pair_pool_gather is inference only (no backward): call it under torch.no_grad(); the training route is "
-                           "ops.pair_pool on one graph per pair and side")
+    _inference_only("pair_pool_gather", (x1, x2), "the training route is ops.pair_pool on one graph per pair and side")
     x1, x2 = _operands("pair_pool_gather", x1, x2, sp1, sp2, "x1", "x2")
     D = x1.size(1)
     lib = _lib.api()
@@ -624,11 +648,7 @@ class GridPlan(_Staged):
 
     def __init__(self, sel, sizes):
         self.sel, self.Cs, self.Q = sel, int(sel.shape[0]), int(sizes.shape[0])
-        first = np.zeros(self.Q + 1, dtype=np.int64)
-        np.cumsum(sizes, out=first[1:])
-        if int(first[-1]) >= 2 ** 31 - 1:
-            raise IndexError("grid_plan: the segments hold 2^31 rows or more")
-        self.N = int(first[-1])
+        first, self.N = _first_rows(sizes, "grid_plan: the segments hold 2^31 rows or more")
         n = sizes[sel]                                                               # rows per selection
         part_ptr = np.zeros(self.Cs + 1, dtype=np.int64)
         np.cumsum((n + GRID_CHUNK - 1) // GRID_CHUNK, out=part_ptr[1:])
@@ -672,13 +692,8 @@ def grid_plan(sizes_host, cols=None):
     before anything is launched (the kernel trusts the table; the policy of ``panel_plan``).  ``cols``: ``None`` = all ``Q`` in order,
     or a host sequence / numpy array / CPU tensor of integers in ``[0, Q)``, in any order, duplicates allowed; ``IndexError`` for a
     wrong dtype or an entry outside ``[0, Q)``; a device tensor is refused (validating it would be a hidden read-back)."""
-    sizes = host_ints(sizes_host, "sizes", None, wrong="grid_plan: the segments' sizes must be a vector of non-negative integers",
-                      on_device="grid_plan: the segments' sizes live on a device: the plan is built on the host — pass their host copy")
-    sizes = sizes.astype(np.int64)
-    Q = int(sizes.shape[0])
-    if cols is None:
-        return GridPlan(np.arange(Q, dtype=np.int32), sizes)
-    return GridPlan(host_ints(cols, "cols", "be a vector of segment numbers", below=Q).astype(np.int32), sizes)
+    sizes = _plan_sizes("grid_plan", sizes_host, "the segments' sizes")
+    return GridPlan(_plan_selection("cols", "be a vector of segment numbers", cols, int(sizes.shape[0])), sizes)
 
 
 def pair_pool_grid(x1, x2, sp1, sp2, plan, rows=None, sum1=None, sum2=None, return_argmax=False, slab=0):
@@ -692,36 +707,28 @@ def pair_pool_grid(x1, x2, sp1, sp2, plan, rows=None, sum1=None, sum2=None, retu
     ``[Q1, D]`` / ``sum2`` ``[Q2, D]``: the segments' column sums (``segment_pool(x, sp, "sum")``), computed here when missing — a
     caller that keeps the segments keeps their sums too.  ``slab``: first-side segments per wave, 0 = the library chooses.  Widths
     1..128.  Inference only: there is no backward (training is ``ops.pair_pool`` / ``ops.pair_pool_gather_shared``)."""
-    if not isinstance(plan, GridPlan):
-        raise GlamHipError("pair_pool_grid: plan must come from ops.grid_plan (the kernel trusts its table)")
+    _require_plan("pair_pool_grid", plan, GridPlan, "grid_plan")
     Q1, Q2, Cs = sp1.B, sp2.B, plan.Cs
     R = pair_count(rows, None, Q1)
     index = None if rows is None else pair_index(rows, R, Q1, name="rows", over="drugs")        # host-side, before the first launch
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x1, x2, sum1, sum2)):
-        raise GlamHipError("pair_pool_grid is inference only (no backward): call it under torch.no_grad(); the training routes are "
-                           "ops.pair_pool on one graph per pair and side and ops.pair_pool_gather_shared on segments held once")
+    _inference_only("pair_pool_grid", (x1, x2, sum1, sum2), "the training routes are ops.pair_pool on one graph per pair and side and "
+                    "ops.pair_pool_gather_shared on segments held once")
     if plan.Q != Q2 or plan.N != sp2.N:
         raise GlamHipError(f"pair_pool_grid: the plan was made for {plan.Q} segments of {plan.N} rows, the second side holds {Q2} of {sp2.N}")
     x1, x2 = _operands("pair_pool_grid", x1, x2, sp1, sp2, "x1", "x2")
     D, dev = x1.size(1), x1.device
-    for name, t, n in (("sum1", sum1, Q1), ("sum2", sum2, Q2)):
-        if t is not None and (t.dim() != 2 or tuple(t.shape) != (n, D) or t.device != dev):
-            raise GlamHipError(f"pair_pool_grid: {name} must be the [{n}, {D}] column sums on {dev}, got {tuple(t.shape)} on {t.device}")
-    if int(slab) < 0:
-        raise GlamHipError(f"pair_pool_grid: slab must be 0 (choose) or the first-side segments per wave, got {slab}")
+    _check_sums_slab("pair_pool_grid", D, dev, (("sum1", sum1, Q1), ("sum2", sum2, Q2)), slab, "first-side segments")
     lib = _lib.api()
     if _lib.load().glam_pair_pool_grid_supported(D) != 0:           # (a status: the raw binding hands it back)
         raise GlamHipError(f"pair_pool_grid: width {D} is outside the kernel table (1..128)")
     out, arg, _, _ = _outputs((R, Cs), dev, arg=return_argmax)
-    if R and Cs and (sp1.N == 0 or sp2.N == 0):          # no row on one side: every pair is empty (and the empty matrix has no address to pass)
-        out.zero_()
-        if return_argmax:
-            arg.fill_(-1)
+    if R and Cs and (sp1.N == 0 or sp2.N == 0):          # no row on one side
+        _all_empty(out, arg)
     elif R and Cs:
         sum1 = f32c(sum1, "sum1") if sum1 is not None else segment_pool(x1, sp1, "sum")
         sum2 = f32c(sum2, "sum2") if sum2 is not None else segment_pool(x2, sp2, "sum")
         sel, work = plan.on(dev)
-        ws = torch.empty(max(lib.glam_pair_pool_grid_workspace_bytes(plan.n_partials, R), 16), dtype=torch.uint8, device=dev)
+        ws = _workspace(lib.glam_pair_pool_grid_workspace_bytes(plan.n_partials, R), dev)
         lib.glam_pair_pool_grid_fwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if index is None else index.on(dev)), R,
                                     ptr(sel), Cs, ptr(work), plan.total_chunks, plan.n_partials, Q1, Q2, D, ptr(sum1), ptr(sum2),
                                     int(slab), ptr(out), ptr(arg), ptr(ws), ws.numel(), stream())
@@ -751,9 +758,8 @@ class _PairPoolGatherShared(torch.autograd.Function):
         if ctx.rows:
             _lib.api().glam_pair_pool_gather_train_fwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(None if null1 else d1),
                                                        ptr(None if null2 else d2), P, Q1, Q2, D, ptr(out), ptr(arg), ptr(sums), stream())
-        else:                # no row on one side: every pair is empty (and the empty matrix has no address to pass)
-            out.zero_()
-            arg.fill_(-1)
+        else:                # no row on one side
+            _all_empty(out, arg)
         ctx.save_for_backward(x1, x2, arg, sums, d1, d2, order1, lptr1, order2, lptr2)
         ctx.sps, ctx.null, ctx.P = (sp1, sp2), (bool(null1), bool(null2)), P
         return _alias_fwd(ctx, out, x1_in, x2_in, with_identity)
@@ -846,9 +852,7 @@ def map_plan(sizes1_host, sizes2_host, idx1=None, idx2=None):
     of ``pair_index`` / ``grid_plan``).  ``idx1`` / ``idx2``: see ``pair_index`` — host integers, any order, duplicates allowed; ``None`` =
     identity on that side (needs ``Q == P``); ``P`` is the length of whichever is given.  ``IndexError`` for a wrong length or dtype or an
     entry outside the range; a device tensor is refused (validating it would be a hidden read-back)."""
-    sizes = [host_ints(s, "sizes", None, wrong=f"map_plan: the sizes of side {k} must be a vector of non-negative integers",
-                       on_device=f"map_plan: the sizes of side {k} live on a device: the plan is built on the host — pass their host copy")
-             .astype(np.int64) for k, s in ((1, sizes1_host), (2, sizes2_host))]
+    sizes = [_plan_sizes("map_plan", s, f"the sizes of side {k}") for k, s in ((1, sizes1_host), (2, sizes2_host))]
     Q1, Q2 = int(sizes[0].shape[0]), int(sizes[1].shape[0])
     P = pair_count(idx1, idx2, Q1)
     a = pair_index(idx1, P, Q1, name="idx1", over="segments of x1").host.astype(np.int64)
@@ -879,11 +883,8 @@ def pair_map(x1, x2, sp1, sp2, plan):
     ``pair_pool_gather``: the largest ``max1`` (or ``max2``) of a pair is bit for bit its max column, and the first row that holds it
     with its ``arg1`` is its argmax.  Ties go to the smallest partner row.  The means are the same bits on every run and within the
     fp64-twin bound.  Widths 1..128.  Inference only: there is no backward."""
-    if not isinstance(plan, MapPlan):
-        raise GlamHipError("pair_map: plan must come from ops.map_plan (the kernel trusts its table)")
-    if torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
-        raise GlamHipError("pair_map is inference only (no backward): call it under torch.no_grad(); the training route is "
-                           "ops.pair_pool on one graph per pair and side")
+    _require_plan("pair_map", plan, MapPlan, "map_plan")
+    _inference_only("pair_map", (x1, x2), "the training route is ops.pair_pool on one graph per pair and side")
     if (plan.Q1, plan.N1, plan.Q2, plan.N2) != (sp1.B, sp1.N, sp2.B, sp2.N):
         raise GlamHipError(f"pair_map: the plan was made for {plan.Q1} segments of {plan.N1} rows against {plan.Q2} of {plan.N2}, the "
                            f"operands hold {sp1.B} of {sp1.N} against {sp2.B} of {sp2.N}")
@@ -896,10 +897,9 @@ def pair_map(x1, x2, sp1, sp2, plan):
     bufs = [(torch.empty(max(R, 1), dtype=torch.float32, device=dev), torch.empty(max(R, 1), dtype=torch.int32, device=dev),
              torch.empty(max(R, 1), dtype=torch.float32, device=dev)) for R in (plan.R1, plan.R2)]
     sides = [tuple(t[:R] for t in side) for side, R in zip(bufs, (plan.R1, plan.R2))]
-    if plan.n_items and (sp1.N == 0 or sp2.N == 0):      # no row on one side: every partner is empty (and the empty matrix has no address to pass)
+    if plan.n_items and (sp1.N == 0 or sp2.N == 0):      # no row on one side: every partner is empty
         for mx, arg, mean in sides:
-            mx.zero_()
-            arg.fill_(-1)
+            _all_empty(mx, arg)
             mean.zero_()
     elif plan.n_items:
         _lib.api().glam_pair_map_fwd(ptr(x1), ptr(x2), ptr(sp1.ptr), ptr(sp2.ptr), ptr(work), plan.n_items, D,
@@ -931,9 +931,10 @@ def _rows_view(t, name):
     return t if t.stride(1) == 1 and t.stride(0) >= t.size(1) else t.contiguous()
 
 
-def _head_operands(who, flat_a, flat_b, f, lin0, lin1, act, out_lo, out_hi, host_checks=None):
-    """The argument checks the table heads share (``pair_head``, ``pair_head_classes``), in one order and with one wording, and the
-    operands as the entry points take them.  ``host_checks(out_dim)`` runs before anything needs a device."""
+def _head_operands(who, flat_a, flat_b, f, lin0, lin1, act, slope, out_lo, out_hi, host_checks=None):
+    """The argument checks the table heads share (``pair_head``, ``pair_head_classes``), in one order and with one wording -> ``(lead, held,
+    R, Cs, e_dim, out_dim)``: the 18 leading arguments of both entry points and the tensors they point into (kept by the caller until
+    its launch is enqueued).  ``host_checks(out_dim)`` runs before anything needs a device."""
     w0, b0 = _weight_bias(lin0, "lin0", who)
     w1, b1 = _weight_bias(lin1, "lin1", who)
     if b0 is None or b1 is None:
@@ -941,9 +942,8 @@ def _head_operands(who, flat_a, flat_b, f, lin0, lin1, act, out_lo, out_hi, host
     if host_checks is not None and w1.dim() == 2:
         host_checks(w1.size(0))
     given = (flat_a, flat_b, f, w0, b0, w1, b1)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in given):
-        raise GlamHipError(f"{who} is inference only (no backward): call it under torch.no_grad(); the head that trains is the listed "
-                           "one — head=\"rows\" of score_matrix / screen_panel, and model(...) / forward_shared for the training calls")
+    _inference_only(who, given, "the head that trains is the listed one — head=\"rows\" of score_matrix / screen_panel, and model(...) / "
+                    "forward_shared for the training calls")
     require_device(*given)
     if act not in _HEAD_ACTS:
         raise GlamHipError(f"{who}: act = {act!r} is not one of 'none', 'relu', 'leaky'")
@@ -971,7 +971,9 @@ def _head_operands(who, flat_a, flat_b, f, lin0, lin1, act, out_lo, out_hi, host
     w0 = _rows_view(w0, "lin0.weight")
     w1, b0, b1 = f32c(w1, "lin1.weight"), f32c(b0, "lin0.bias"), f32c(b1, "lin1.bias")
     f = None if F == 0 else f32c(f, "f")
-    return a, b, f, w0, b0, w1, b1, R, Cs, hid, F, e_dim, out_dim
+    lead = (ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(f), R, Cs, hid, F, ptr(w0), w0.stride(0), ptr(b0), e_dim, ptr(w1), ptr(b1), out_dim,
+            _HEAD_ACTS[act], float(slope))
+    return lead, (a, b, f, w0, b0, w1, b1), R, Cs, e_dim, out_dim
 
 
 def pair_head(flat_a, flat_b, f, lin0, lin1, act="none", slope=0.0):
@@ -984,14 +986,12 @@ def pair_head(flat_a, flat_b, f, lin0, lin1, act="none", slope=0.0):
     one fixed chain of its own ``(flat_a[i], flat_b[j], f[i, j])``: the same bits whatever the rest of the table is.  ``out_dim`` in 1..8,
     ``F`` in 0..16, ``R * Cs < 2^31 - 1``.  Inference only: there is no backward (a head that trains is the listed one: ``head="rows"`` of
     the table calls, ``model(...)`` / ``forward_shared`` for training)."""
-    a, b, f, w0, b0, w1, b1, R, Cs, hid, F, e_dim, out_dim = _head_operands("pair_head", flat_a, flat_b, f, lin0, lin1, act, 1, HEAD_MAX_OUT)
-    dev = flat_a.device
-    out = torch.empty(R, Cs, out_dim, dtype=torch.float32, device=dev)
+    lead, _held, R, Cs, e_dim, out_dim = _head_operands("pair_head", flat_a, flat_b, f, lin0, lin1, act, slope, 1, HEAD_MAX_OUT)
+    out = torch.empty(R, Cs, out_dim, dtype=torch.float32, device=flat_a.device)
     if R and Cs:
         lib = _lib.api()
-        ws = torch.empty(max(lib.glam_pair_head_workspace_bytes(R, Cs, e_dim), 16), dtype=torch.uint8, device=dev)
-        lib.glam_pair_head_fwd(ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(f), R, Cs, hid, F, ptr(w0), w0.stride(0), ptr(b0), e_dim, ptr(w1),
-                               ptr(b1), out_dim, _HEAD_ACTS[act], float(slope), ptr(ws), ws.numel(), ptr(out), stream())
+        ws = _workspace(lib.glam_pair_head_workspace_bytes(R, Cs, e_dim), out.device)
+        lib.glam_pair_head_fwd(*lead, ptr(ws), ws.numel(), ptr(out), stream())
     return out
 
 
@@ -1032,8 +1032,8 @@ def pair_head_classes(flat_a, flat_b, f, lin0, lin1, act="none", slope=0.0, clas
     (``F`` in 0..16, ``R * Cs < 2^31 - 1``, inference only, empty tables without a launch)."""
     who = "pair_head_classes"
     chosen = []
-    a, b, f, w0, b0, w1, b1, R, Cs, hid, F, e_dim, out_dim = _head_operands(
-        who, flat_a, flat_b, f, lin0, lin1, act, 2, HEAD_MAX_CLASSES, lambda n: chosen.extend(class_selection(classes, n, who)))
+    lead, _held, R, Cs, e_dim, out_dim = _head_operands(
+        who, flat_a, flat_b, f, lin0, lin1, act, slope, 2, HEAD_MAX_CLASSES, lambda n: chosen.extend(class_selection(classes, n, who)))
     dev = flat_a.device
     S = len(chosen)
     cls = torch.empty(R, Cs, dtype=torch.int32, device=dev)
@@ -1042,8 +1042,7 @@ def pair_head_classes(flat_a, flat_b, f, lin0, lin1, act="none", slope=0.0, clas
     table = torch.empty(R, Cs, out_dim, dtype=torch.float32, device=dev) if logits else None
     if R and Cs:
         lib = _lib.api()
-        ws = torch.empty(max(lib.glam_pair_head_classes_workspace_bytes(R, Cs, e_dim, out_dim), 16), dtype=torch.uint8, device=dev)
-        lib.glam_pair_head_classes_fwd(ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(f), R, Cs, hid, F, ptr(w0), w0.stride(0), ptr(b0), e_dim,
-                                       ptr(w1), ptr(b1), out_dim, _HEAD_ACTS[act], float(slope), (ctypes.c_int * max(S, 1))(*chosen), S,
-                                       ptr(ws), ws.numel(), ptr(cls), ptr(logp), ptr(sel) if S else None, ptr(table), stream())
+        ws = _workspace(lib.glam_pair_head_classes_workspace_bytes(R, Cs, e_dim, out_dim), dev)
+        lib.glam_pair_head_classes_fwd(*lead, (ctypes.c_int * max(S, 1))(*chosen), S, ptr(ws), ws.numel(), ptr(cls), ptr(logp),
+                                       ptr(sel) if S else None, ptr(table), stream())
     return ClassTable(cls, logp, sel, table)

@@ -1,6 +1,7 @@
 """CPU: the helpers the pair-fusion family shares (``glam_amd/ops_pair.py``, ``glam_amd/model.py``) — the host-vector validator at each of
-its three call sites, the one staged-copy holder, "P of whichever index is given", and the model guards built from slots against the
-methods that call them."""
+its three call sites, the one staged-copy holder, "P of whichever index is given", the model guards built from slots against the
+methods that call them, and what the table calls share: the plan cache, the listed head over a table, the fusion columns and the one
+launch site of the panel forward."""
 import numpy as np
 import pytest
 import torch
@@ -159,3 +160,172 @@ def test_model_guards_built_from_slots_agree_with_the_methods(cls, words, guard)
     with torch.no_grad():
         stale = _outcome(lambda: model._check_encoding(net, "call", object(), model.ProteinEncoding, None, "rows", words))
         assert stale.startswith("call: the encoding was made by another model") and f"{words['encode']}() on this one" in stale
+
+
+# ---- the table calls: one plan cache, one rows head, one panel launch ------------------------------------------------------------
+class _Sp:
+    B, N = 4, 87
+    ptr = torch.tensor([0, 5, 75, 78, 87], dtype=torch.int32)
+
+
+def _counting_sizes():
+    calls = []
+
+    def sizes():
+        calls.append(1)
+        return np.asarray([5, 70, 3, 9])
+    return sizes, calls
+
+
+@pytest.mark.parametrize("make_plan", [ops.panel_plan, ops.grid_plan])
+def test_plan_cache_keys_laziness_and_eviction(make_plan):
+    sizes, calls = _counting_sizes()
+    plans = {}
+    every = model._cached_plan(plans, make_plan, _Q, None, sizes, 16)
+    some = model._cached_plan(plans, make_plan, _Q, [2, 0, 2], sizes, 16)
+    assert list(plans) == [None, (2, 0, 2)] and plans[None] is every and plans[(2, 0, 2)] is some
+    assert every.sel.tolist() == [0, 1, 2, 3] and some.sel.tolist() == [2, 0, 2] and some.Q == _Q and some.N == 87
+    sizes, calls = _counting_sizes()
+    plans = {}
+    first = model._cached_plan(plans, make_plan, _Q, [2, 0, 2], sizes, 16)
+    assert model._cached_plan(plans, make_plan, _Q, np.asarray([2, 0, 2]), sizes, 16) is first and len(calls) == 1 and len(plans) == 1
+    # a selection that is refused: before the sizes are asked for, and nothing is kept
+    sizes, calls = _counting_sizes()
+    plans = {}
+    with pytest.raises(IndexError, match=r"must lie in \[0, 4\)"):
+        model._cached_plan(plans, make_plan, _Q, [1, 4], sizes, 16)
+    assert calls == [] and plans == {}
+    # first in, first out at the bound; no bound, no eviction
+    for bound, left in ((16, 16), (None, 17)):
+        plans = {}
+        for n in range(17):
+            model._cached_plan(plans, make_plan, _Q, [0] * (n + 1), sizes, bound)
+        assert len(plans) == left and ((0,) in plans) is (bound is None) and list(plans)[-1] == (0,) * 17
+    # a plan the caller calls stale is made again, under its key
+    old = plans[(0,)]
+    assert model._cached_plan(plans, make_plan, _Q, [0], sizes, None, stale=lambda p: False) is old
+    new = model._cached_plan(plans, make_plan, _Q, [0], sizes, None, stale=lambda p: p is old)
+    assert new is not old and plans[(0,)] is new and len(plans) == 17
+
+
+def test_the_three_plan_caches_go_through_the_helper(monkeypatch):
+    import types
+    dti, ddi = model.ArchitectureDTI(**_KW), model.ArchitectureDDI(**_KW)
+    penc = model.ProteinEncoding(dti, [None, None], _Sp(), None, dti._protein_stamp())
+    denc = model.DrugEncoding(ddi, [None, None], [None, None], _Sp(), None, None, ddi._drug_stamp())
+    penc.prosum, denc.sum1, denc.sum2 = [], [], []          # (filled: no segment sum on this machine)
+    data_pro = types.SimpleNamespace()
+    # for real: the keys, the one read-back per holder, the batch's unbounded dict and its re-validation
+    assert penc.panel([2, 0, 2]) is penc.plans[(2, 0, 2)] and penc.panel(None) is penc.plans[None] and list(penc.plans) == [(2, 0, 2), None]
+    assert denc.grid([1]) is denc.plans[(1,)] and denc.grid([1]).N == 87
+    assert penc.sizes_host.tolist() == denc.sizes_host.tolist() == [5, 70, 3, 9]
+    plan = dti._panel_plan(data_pro, _Sp(), [3, 3])
+    kept = data_pro.__dict__["_glam_panel_plans"]
+    assert kept["plans"] == {(3, 3): plan} and kept["sizes"].tolist() == [5, 70, 3, 9] and dti._panel_plan(data_pro, _Sp(), [3, 3]) is plan
+    other = _Sp()
+    other.ptr, other.N = torch.tensor([0, 5, 75, 78, 90], dtype=torch.int32), 90
+    again = dti._panel_plan(data_pro, other, [3, 3])
+    assert again is not plan and again.N == 90 and kept["plans"] == {(3, 3): again} and kept["sizes"].tolist() == [5, 70, 3, 12]
+    # ... and all three through the one function
+    seen = []
+
+    def spy(plans, make_plan, Q, selection, sizes, bound=None, stale=None):
+        seen.append((plans, make_plan, Q, selection, bound))
+        return "the plan"
+    monkeypatch.setattr(model, "_cached_plan", spy)
+    assert penc.panel([1]) == denc.grid([2]) == dti._panel_plan(data_pro, _Sp(), [0]) == "the plan"
+    assert seen[0] == (penc.plans, ops.panel_plan, 4, [1], 16) and seen[0][0] is penc.plans
+    assert seen[1] == (denc.plans, ops.grid_plan, 4, [2], 16) and seen[1][0] is denc.plans
+    assert seen[2] == (kept["plans"], ops.panel_plan, 4, [0], None) and seen[2][0] is kept["plans"]
+
+
+class _Block:
+    """What the rows head sees of a ``LinearBlock``: a call and ``.linear`` — here the bare ``torch.nn.Linear``, counted."""
+
+    def __init__(self, n_in, n_out, gen):
+        self.linear = torch.nn.Linear(n_in, n_out).double()
+        with torch.no_grad():
+            self.linear.weight.copy_(torch.randint(-3, 4, (n_out, n_in), generator=gen))
+            self.linear.bias.copy_(torch.randint(-3, 4, (n_out,), generator=gen))
+        self.outputs = []
+
+    def __call__(self, x):
+        self.outputs.append(self.linear(x))
+        return self.outputs[-1]
+
+
+def _integer_table(R, Cs, steps=2, hid=3, e_dim=5, out_dim=2):
+    """Integer-valued fp64 operands (every sum is exact, in any order) and the head entry by entry."""
+    gen = torch.Generator().manual_seed(R * 10 + Cs)
+    net = type("Head", (), {})()
+    net.lin_out0, net.lin_out1 = _Block(2 * hid + 2 * steps, e_dim, gen), _Block(e_dim, out_dim, gen)
+    a = torch.randint(-4, 5, (R, hid), generator=gen).double()
+    b = torch.randint(-4, 5, (Cs, hid), generator=gen).double()
+    fusion = [torch.randint(-4, 5, (R, Cs, 2), generator=gen).double() for _ in range(steps)]
+    want = torch.zeros(R, Cs, out_dim, dtype=torch.float64)
+    with torch.no_grad():
+        for i in range(R):
+            for j in range(Cs):
+                want[i, j] = net.lin_out1.linear(net.lin_out0.linear(torch.cat([a[i], b[j]] + [f[i, j] for f in fusion])))
+    return net, a, b, fusion, want
+
+
+@pytest.mark.parametrize("per_block", [1, 2, 5, 7, 0])          # 0: once per column
+def test_rows_head_over_a_table_entry_by_entry(per_block):
+    R, Cs = 5, 3
+    net, a, b, fusion, want = _integer_table(R, Cs)
+    with torch.no_grad():
+        out = model._table_head_rows(net, a, b, fusion, R, Cs, per_block)
+    assert out.shape == want.shape and out.dtype == want.dtype and torch.equal(out, want)
+    calls = Cs if per_block == 0 else -(-R // per_block)
+    assert len(net.lin_out0.outputs) == len(net.lin_out1.outputs) == calls
+    if per_block >= R:          # one block covers the table: what the head wrote, not a copy of it
+        assert out.untyped_storage().data_ptr() == net.lin_out1.outputs[0].untyped_storage().data_ptr()
+
+
+@pytest.mark.parametrize("R,Cs", [(0, 3), (5, 0), (0, 0)])
+@pytest.mark.parametrize("per_block", [0, 4])
+def test_rows_head_of_an_empty_table(R, Cs, per_block):
+    net, a, b, fusion, _ = _integer_table(R, Cs)
+    out = model._table_head_rows(net, a, b, fusion, R, Cs, per_block)
+    assert out.shape == (R, Cs, 2) and out.dtype == torch.float64 and not out.any()
+    assert net.lin_out0.outputs == [] and net.lin_out1.outputs == []
+
+
+def test_fusion_columns_side_by_side():
+    R, Cs, steps = 2, 3, 3
+    fusion = [torch.arange(R * Cs * 2, dtype=torch.float32).view(R, Cs, 2) + 100 * s for s in range(steps)]
+    cols = model._fusion_columns(fusion, R, Cs, fusion[0])
+    assert cols.shape == (R, Cs, 2 * steps)
+    for s in range(steps):
+        for i in range(R):
+            for j in range(Cs):
+                for c in range(2):
+                    assert cols[i, j, 2 * s + c] == fusion[s][i, j, c]
+    like = torch.zeros(1, dtype=torch.float64)
+    for r, c in ((0, 3), (2, 0)):
+        empty = model._fusion_columns([f[:r, :c] for f in fusion], r, c, like)
+        assert empty.shape == (r, c, 2 * steps) and empty.dtype == torch.float64
+    assert model._fusion_columns([], R, Cs, like) is None
+
+
+def test_panel_forward_has_one_launch_site(monkeypatch):
+    import inspect
+    assert inspect.getsource(ops_pair).count("glam_pair_pool_panel_fwd(") == 1
+    assert "glam_pair_pool_panel_fwd(" in inspect.getsource(ops_pair._panel_fwd)
+    seen = []
+
+    def spy(mol, pro, msp, psp, plan, molsum, prosum, slab, want_arg):
+        seen.append((slab, want_arg))
+        return torch.zeros(msp.B, plan.Qs, 2), torch.zeros(msp.B, plan.Qs, 2, dtype=torch.int32) if want_arg else None, None, None
+    monkeypatch.setattr(ops_pair, "_panel_fwd", spy)
+    monkeypatch.setattr(ops_pair, "_operands", lambda who, a, b, *rest: (a, b))       # (the refusal of a CPU matrix)
+    plan = ops.panel_plan([5, 70, 3, 9], [2, 0, 2])
+    for staged in (plan, plan.by_protein()):                                       # (a copy out of pinned memory needs a device)
+        staged._dev[torch.device("cpu")] = tuple(torch.from_numpy(p) for p in staged._parts)
+    msp = type("Msp", (), {"B": 2, "N": 6})()
+    mol, pro = torch.zeros(6, 15), torch.zeros(87, 15)
+    with torch.no_grad():
+        assert ops.pair_pool_panel(mol, pro, msp, _Sp(), plan, slab=3).shape == (2, 3, 2)
+        assert ops.pair_pool_panel_shared(mol, pro, msp, _Sp(), plan).shape == (2, 3, 2)
+    assert seen == [(3, False), (0, True)]

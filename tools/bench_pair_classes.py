@@ -125,14 +125,8 @@ def run_leg(name):
         act = model._class_head(net, "bench")
 
         def head_rows():
-            out = o1.new_empty(R, Cs, out_dim)
-            with ops.weight_scope():
-                for i0 in range(0, R, per_block):                # the loop of score_matrix(head="rows"); the panel: one piece
-                    i1 = min(R, i0 + per_block)
-                    block = ops.cat_cols([o1[i0:i1].repeat_interleave(Cs, 0), o2.repeat(i1 - i0, 1)]
-                                         + [f[i0:i1].reshape((i1 - i0) * Cs, 2) for f in fusion])
-                    out[i0:i1] = net.lin_out1(net.lin_out0(block)).view(i1 - i0, Cs, out_dim)
-            return from_logits(out)
+            with ops.weight_scope():             # the head of score_matrix(head="rows"); the panel: one piece
+                return from_logits(model._table_head_rows(net, o1, o2, fusion, R, Cs, per_block))
         heads = {"classes": lambda: model._table_head_classes(net, act, o1, o2, fusion, R, Cs, [1], False), "rows": head_rows}
         if out_dim <= ops.HEAD_MAX_OUT:
             heads["factored"] = lambda: from_logits(model._table_head_factored(net, act, o1, o2, fusion, R, Cs))

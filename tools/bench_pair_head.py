@@ -87,13 +87,8 @@ with torch.no_grad():
     act = model._factored_head(ddi, "bench")
 
     def head_rows():
-        out = o1.new_empty(Q, Q, 1)
         with ops.weight_scope():
-            for i0 in range(0, Q, per_block):                    # the loop of score_matrix(head="rows")
-                i1 = min(Q, i0 + per_block)
-                block = ops.cat_cols([o1[i0:i1].repeat_interleave(Q, 0), o2.repeat(i1 - i0, 1)] + [f[i0:i1].reshape((i1 - i0) * Q, 2) for f in fusion])
-                out[i0:i1] = ddi.lin_out1(ddi.lin_out0(block)).view(i1 - i0, Q, 1)
-        return out
+            return model._table_head_rows(ddi, o1, o2, fusion, Q, Q, per_block)          # the head of score_matrix(head="rows")
 
     def head_factored():
         return model._table_head_factored(ddi, act, o1, o2, fusion, Q, Q)

@@ -181,11 +181,17 @@ class GraphIndex:
             ws = torch.empty(lib.glam_csr_workspace_bytes(self.N, self.E), dtype=torch.uint8, device=self.device)
             ei = self._ei_ref()
             if ei is None:     # the caller dropped edge_index before the first backward: the by-target CSR holds the same edges
-                deg = (self.rowptr[1:] - self.rowptr[:-1]).long()
-                dst64 = torch.repeat_interleave(torch.arange(self.N, device=self.device), deg, output_size=self.E)
-                ei = torch.empty(2, self.E, dtype=torch.int64, device=self.device)
-                ei[0, self.eid.long()] = self.src.long()
-                ei[1, self.eid.long()] = dst64
+                # Only the first rowptr[N] entries of src / eid were written: edges with bad ids were dropped (VALIDATE = "deferred" /
+                # "off" lets such an index live).  Those entries go to a spare column and their edges come back as -1, which the build
+                # below drops again — no read of an unwritten entry, no host sync, and the same tables as from the tensor itself.
+                pos = torch.arange(self.E, device=self.device)
+                live = pos < self.rowptr[-1]
+                dst64 = torch.searchsorted(self.rowptr[1:].long(), pos, right=True)      # the segment that position pos lies in
+                slot = torch.where(live, self.eid.long(), self.E)
+                ei = torch.full((2, self.E + 1), -1, dtype=torch.int64, device=self.device)
+                ei[0, slot] = torch.where(live, self.src.long(), -1)
+                ei[1, slot] = torch.where(live, dst64, -1)
+                ei = ei[:, :self.E].contiguous()
             lib.glam_csr_build(ptr(ei), self.N, self.E, 1, ptr(colptr), ptr(dst), ptr(eid_t), ptr(self._err), ptr(ws), ws.numel(), stream())
             self._t = (colptr, dst, eid_t)
         return self._t

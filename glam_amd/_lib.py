@@ -230,6 +230,8 @@ SIGNATURES = {
     "glam_collate_padded": (_i32, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "glam_collate_padded_split": (_i32, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
                                          _vp]),
+    "glam_pair_list_supported": (_i32, [_i64, _i64]),
+    "glam_pair_list_load": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32] + [_vp] * 8),
 }
 
 # An ``int`` return is a status (0 = ok, < 0 = GLAM_E_*) that api() checks — the default, so that a new entry point is safe without

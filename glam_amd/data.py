@@ -278,14 +278,15 @@ def padded_capacity(ns, es, batch_size, ell, phantom_rows=None):
         K = need
 
 
-def padded_bucket(ns, es, y_rows, batch_size, capacity, ell, phantom_rows=None):
+def padded_bucket(ns, es, y_rows, batch_size, capacity, ell, phantom_rows=None, labels=True):
     """The checked ``(N_cap, E_cap, r)`` of ``DeviceDataset.padded``: ``capacity`` (or ``padded_capacity``) and the one constant count of
     ``y`` rows per graph.  ``ValueError`` for ``y`` rows that differ between graphs or are absent, and for a capacity that the dataset's
     largest graph does not fit with one phantom node beside it — with ``phantom_rows``, one node for each of the
-    ``phantom_graphs(ns, batch_size, N_cap, phantom_rows)`` phantom graphs."""
+    ``phantom_graphs(ns, batch_size, N_cap, phantom_rows)`` phantom graphs.  ``labels=False``: the graphs carry no ``y`` (the ligand side
+    of a resident pair batch, whose labels belong to the pairs): ``r = 0``."""
     y_rows = np.asarray(y_rows, dtype=np.int64)
-    r = int(y_rows[0]) if y_rows.size else 0
-    if r < 1 or bool((y_rows != r).any()):
+    r = int(y_rows[0]) if y_rows.size and labels else 0
+    if labels and (r < 1 or bool((y_rows != r).any())):
         raise ValueError("padded batches need the same number (>= 1) of y rows for every graph: the loss reads output[:B] against y[B * r]")
     n_cap, e_cap = padded_capacity(ns, es, batch_size, ell, phantom_rows) if capacity is None else (int(capacity[0]), int(capacity[1]))
     if phantom_rows is not None and not 1 <= int(batch_size) <= np.size(ns):
@@ -435,12 +436,15 @@ class PaddedBatch(Batch):
     each (``glam_collate_padded_split``), ``K`` fixed for the bucket, so ``num_graphs = B + K`` and the model's output has ``B + K`` rows.
     The kernels that give a graph to one wave or block then never meet a graph larger than ``m``.  ``None``: one phantom graph."""
 
-    def __init__(self, dataset, batch_size, capacity=None, phantom_rows=None):
+    def __init__(self, dataset, batch_size, capacity=None, phantom_rows=None, labels=True):
         from . import ops
         ds, B = dataset, int(batch_size)
         self.ell, self.ell_t = ds.ell_ok, ds.ell_t_ok
         has_y = ds.y is not None
-        N_cap, E_cap, r = padded_bucket(ds.ns, ds.es, ds.y_rows if has_y else np.zeros(0), B, capacity, self.ell or self.ell_t, phantom_rows)
+        if not labels and has_y:
+            raise ValueError("labels=False is the padded batch of graphs WITHOUT y (the ligands of a resident pair batch); this dataset has y")
+        N_cap, E_cap, r = padded_bucket(ds.ns, ds.es, ds.y_rows if has_y else np.zeros(0), B, capacity, self.ell or self.ell_t, phantom_rows,
+                                        labels)
         K = phantom_graphs(ds.ns, B, N_cap, phantom_rows)
         self.num_phantom_graphs, self.phantom_rows = K, None if phantom_rows is None else int(phantom_rows)
         dev = ds.device
@@ -556,6 +560,241 @@ class PaddedBatch(Batch):
         else:
             _lib.api().glam_collate_padded_split(self._ds._ds, self._out, _lib.ptr(self._table), B, self.num_phantom_graphs, N_cap, E_cap, r, Ed,
                                                  xrb, stride, earb, yrb, _lib.stream())
+
+
+# --------------------------------------------------------------------------------------
+# resident pair data: a dataset's pair table on the device, and batches of fixed capacity that one launch refills
+# --------------------------------------------------------------------------------------
+def pair_ids_table(ids, n_pairs, batch_size):
+    """The checked pair ids of one load of a resident pair batch (host, numpy) -> int32 ``[batch_size]``.  ``ops.host_ints``'s refusals —
+    a device tensor (``GlamHipError``), a non-integer dtype, another shape than a vector, an id outside ``[0, n_pairs)`` (``IndexError``) —
+    then ``ValueError`` for another count than ``batch_size``: before anything is enqueued; the kernel trusts the table."""
+    from . import ops
+    a = ops.host_ints(ids, "pair ids", "be a vector of pair ids", below=int(n_pairs))
+    if a.shape[0] != int(batch_size):
+        raise ValueError(f"this pair batch holds exactly {int(batch_size)} pairs, got {a.shape[0]} ids (run a shorter last batch eagerly on a "
+                         "host ops.pair_index, or drop it)")
+    return a.astype(np.int32)
+
+
+def dti_tables(pair_ids, first, ns, es, batch_size):
+    """The host side of one DTI load (O(B) numpy) -> ``(table, N, E)``: ``table`` int32 ``[4 * (B + 1) + B]`` — the ligand slot table of
+    ``resident_table`` over the ligands ``first[pair_ids]`` (ids, then the exclusive node / edge / y offsets: no y rows), then the pair ids
+    themselves — and the slots' node and edge totals for the capacity check.  Errors of ``pair_ids_table``."""
+    ids = pair_ids_table(pair_ids, first.shape[0], batch_size)
+    slots, N, E, _Y = resident_table(first[ids], ns, es, np.zeros(ns.shape[0], dtype=np.int64))
+    return np.concatenate([slots.reshape(-1), ids]), N, E
+
+
+def ddi_table(pair_ids, n_pairs, batch_size):
+    """The host side of one DDI load: the checked pair ids, int32 ``[B]`` (``pair_ids_table``)."""
+    return pair_ids_table(pair_ids, n_pairs, batch_size)
+
+
+def _pair_column(v, name):
+    from . import ops
+    return ops.host_ints(v, name, "be a vector with one segment id per pair", below=2 ** 31 - 1).astype(np.int32)
+
+
+class ResidentPairs:
+    """A dataset's pair table ON THE DEVICE: two int32 columns ``first`` / ``second`` ``[Np]`` — a graph id per pair and side (DTI: ligand,
+    protein; DDI: drug, drug) — and the labels ``y`` ``[Np, r]``.  Host copies of the columns (``first_host`` / ``second_host``, numpy) stay
+    for the O(B) table arithmetic of a load.  Validated once, here: integer columns of equal length with entries >= 0 (``IndexError`` /
+    ``ValueError``), one label row per pair whose bytes are a multiple of 4.  ``dti_batch`` / ``ddi_batch`` make the batch objects that one
+    launch refills from it per step."""
+
+    def __init__(self, first, second, y, device):
+        from . import ops
+        self.first_host, self.second_host = _pair_column(first, "first"), _pair_column(second, "second")
+        self.n = int(self.first_host.shape[0])
+        if self.second_host.shape[0] != self.n:
+            raise ValueError(f"ResidentPairs: the two columns disagree: {self.n} first ids, {self.second_host.shape[0]} second ids")
+        y = torch.as_tensor(y)
+        if y.dim() == 1:
+            y = y.unsqueeze(1)
+        if y.size(0) != self.n:
+            raise ValueError(f"ResidentPairs: {self.n} pairs but {y.size(0)} label rows")
+        rb = int(np.prod(y.shape[1:], dtype=np.int64)) * y.element_size()
+        if rb < 4 or rb % 4:
+            raise ValueError(f"ResidentPairs: label rows ({y.dtype} {tuple(y.shape[1:])}) are no positive multiple of 4 bytes")
+        self.device = device = torch.device(device)
+        if device.type != "cuda":
+            raise ops.GlamHipError(f"ResidentPairs lives on an MI355X HIP device (got {device}); the host path is ops.pair_index per step")
+        both = torch.from_numpy(np.concatenate([self.first_host, self.second_host])).to(device)        # (one copy)
+        self.first, self.second = both[:self.n], both[self.n:]
+        self.y = y.contiguous().to(device)
+
+    def __len__(self):
+        return self.n
+
+    def dti_batch(self, ligands, proteins, batch_size, phantom_rows=None, capacity=None):
+        """The refillable batch of ``batch_size`` (ligand, protein) pairs for ``ArchitectureDTI.forward_shared`` — ``first`` = ligand id in
+        the ``DeviceDataset`` ``ligands`` (which carries no ``y``), ``second`` = protein id in the ``Batch`` ``proteins``: see
+        ``ResidentDTIBatch``.  ``phantom_rows`` / ``capacity``: as ``DeviceDataset.padded``."""
+        return ResidentDTIBatch(self, ligands, proteins, batch_size, phantom_rows, capacity)
+
+    def ddi_batch(self, drugs1, drugs2=None, batch_size=32):
+        """The refillable batch of ``batch_size`` (drug, drug) pairs for ``ArchitectureDDI.forward_shared`` — ``first`` = drug id in the
+        ``Batch`` ``drugs1``, ``second`` = drug id in ``drugs2`` (``None``: ``drugs1`` serves both towers): see ``ResidentDDIBatch``."""
+        return ResidentDDIBatch(self, drugs1, drugs2, batch_size)
+
+
+class _ResidentPairBatch:
+    """What the two resident pair batches share: the fixed device table a load fills (one pinned, non-blocking copy), an epoch's tables
+    from one upload (``load_many`` / ``load(step=i)``), and the reload protocol of ``PaddedBatch`` — ``load(launch=False)`` uploads only
+    and ``glam_reload()`` enqueues the launches on the current stream, first in the step of a ``GraphedTrainStep``, so that a capture holds
+    them; outside a capture a ``load`` that has launched already is not repeated.  Subclasses give ``_host_table(ids)`` (the checked int32
+    table of one load, ``ValueError`` / ``IndexError`` before anything is enqueued) and ``_enqueue()`` (the launches)."""
+
+    def _init_table(self, words, device):
+        self._table = torch.zeros(words, dtype=torch.int32, device=device)
+        self._tables, self._launched = None, False
+
+    def load(self, ids=None, step=None, launch=True):
+        """Put the pairs ``ids`` — exactly ``B`` pair ids of the ``ResidentPairs`` table, host integers — into this batch; ``step=i``
+        instead: table ``i`` of the last ``load_many``, a device-to-device copy.  ``launch=False`` uploads the table only, for a batch
+        that a ``GraphedTrainStep`` runs next.  ``IndexError`` for ids outside the table, ``ValueError`` for another count than ``B`` (a
+        caller runs a shorter last batch eagerly on a host ``ops.pair_index``, or drops it) or slots beyond the capacity — before
+        anything is enqueued."""
+        if (ids is None) == (step is None):
+            raise ValueError(f"{type(self).__name__}.load takes either ids or step=")
+        if step is not None:
+            if self._tables is None or not 0 <= int(step) < self._tables.size(0):
+                raise IndexError(f"step {step}: load_many has uploaded {0 if self._tables is None else self._tables.size(0)} tables")
+            self._table.copy_(self._tables[int(step)])
+        else:
+            table = self._host_table(ids)
+            from . import _lib
+            _lib.require_device(self._table)
+            staged = torch.empty(table.shape, dtype=torch.int32, pin_memory=True)
+            staged.numpy()[...] = table
+            self._table.copy_(staged, non_blocking=True)
+        self._launched = False
+        if launch:
+            self.glam_reload()
+            self._launched = True
+        return self
+
+    def load_many(self, id_lists):
+        """The tables of ``len(id_lists)`` loads (an epoch's) from one numpy pass and ONE upload; ``load(step=i)`` then installs table
+        ``i``.  Same errors as ``load``, for every list, before anything is enqueued.  Returns the number of tables."""
+        tables = [self._host_table(ids) for ids in id_lists]
+        stacked = np.stack(tables) if tables else np.zeros((0, self._table.numel()), dtype=np.int32)
+        staged = torch.empty(stacked.shape, dtype=torch.int32, pin_memory=True)
+        staged.numpy()[...] = stacked
+        self._tables = staged.to(self._table.device, non_blocking=True)
+        return len(tables)
+
+    def glam_reload(self):
+        """The reload hook of ``GraphedTrainStep``: enqueue this batch's launches for the table now on the device, on the current stream."""
+        if self._launched and not torch.cuda.is_current_stream_capturing():
+            self._launched = False
+            return
+        self._enqueue()
+
+
+def _check_ids_below(col, n, what, things):
+    if col.size and int(col.max()) >= n:
+        raise IndexError(f"ResidentPairs: the {what} column names {things} up to {int(col.max())}, but only {n} are given")
+
+
+class ResidentDTIBatch(_ResidentPairBatch):
+    """One batch of FIXED CAPACITY of ``B`` (ligand, protein) pairs, refilled in place by ``load(pair_ids)`` — two launches behind one
+    small copy: the padded collate of the ligands (``glam_collate_padded``) and ``glam_pair_list_load`` for the pair -> protein lists and
+    the labels — so a ``GraphedTrainStep(SharedStep(model), ...)`` captures ONE graph and replays it for every batch of a shuffled epoch.
+
+    ``mol``: a ``PaddedBatch`` of ``num_graphs = B + K`` ligand graphs (``K`` phantom graphs, ``phantom_rows``); ``pro``: the ``Batch`` of the
+    ``Q`` distinct proteins, held once, on the device — EVERY step runs the protein tower over all of them, which fits a target set or a
+    panel of tens of proteins, not thousands of long ones; ``index``: ``ops.PairList(B + K, Q)`` whose phantom ligand slots point at protein
+    ``pad = 0`` (their output rows stay out of the loss: ``graphs.padded_loss``); ``y`` ``[B, r]``: the pairs' labels; ``num_real_graphs = B``.
+    Exactly ``B`` pair ids per load — a shorter last batch runs eagerly on a host ``ops.pair_index``, or is dropped."""
+
+    def __init__(self, pairs, ligands, proteins, batch_size, phantom_rows=None, capacity=None):
+        from . import ops
+        if not isinstance(ligands, DeviceDataset) or ligands.y is not None:
+            raise ValueError("dti_batch: ligands must be a DeviceDataset without y (the labels belong to the pairs: ResidentPairs.y)")
+        dev = pairs.device
+        if ligands.device != dev:
+            raise ValueError(f"dti_batch: the ligands live on {ligands.device}, the pair table on {dev}")
+        Q = int(getattr(proteins, "num_graphs", 0))
+        if Q < 1:
+            raise ValueError("dti_batch: proteins must be a collated Batch of the Q >= 1 distinct proteins")
+        _check_ids_below(pairs.first_host, ligands.n, "first", "ligands")
+        _check_ids_below(pairs.second_host, Q, "second", "proteins")
+        self.pairs, B = pairs, int(batch_size)
+        if B < 1:
+            raise ValueError(f"dti_batch: batch_size must be >= 1, got {batch_size}")
+        mol = PaddedBatch(ligands, B, capacity, phantom_rows, labels=False)
+        self.index = ops.PairList(mol.num_graphs, Q, dev, pad=0)          # (refuses a list beyond the kernel's bounds)
+        self.mol, self.pro = mol, proteins if proteins.x.device == dev else proteins.to(dev)
+        self.y = torch.empty((B,) + pairs.y.shape[1:], dtype=pairs.y.dtype, device=dev)
+        self.num_graphs, self.num_real_graphs = mol.num_graphs, B
+        self._init_table(4 * (B + 1) + B, dev)
+        mol._table = self._table[:4 * (B + 1)].view(4, B + 1)             # (the ligand slot table travels in this batch's one copy)
+        self._ids = self._table[4 * (B + 1):]
+
+    def _host_table(self, ids):
+        ds = self.mol._ds
+        table, N, E = dti_tables(ids, self.pairs.first_host, ds.ns, ds.es, self.num_real_graphs)
+        self.mol._fit(self.num_real_graphs, N, E)
+        return table
+
+    def _enqueue(self):
+        from . import ops
+        self.mol._launched = False
+        self.mol.glam_reload()
+        ops.pair_list_launch(self._ids, None, None, self.index, self.pairs.second, self.num_real_graphs, self.pairs.y, self.y)
+
+    def glam_admission(self, model):
+        """The admission check a ``GraphedTrainStep`` runs on its first step with this batch (``graphs.dti_admission``): ``padded_admission``'s
+        rules for the ligand tower and the head, the protein tower exempt.  ``model``: the ``SharedStep`` or the ``ArchitectureDTI``."""
+        from .graphs import dti_admission
+        return dti_admission(getattr(model, "model", model))
+
+
+class ResidentDDIBatch(_ResidentPairBatch):
+    """One batch of FIXED CAPACITY of ``B`` (drug, drug) pairs, refilled in place by ``load(pair_ids)`` — ONE launch behind one small copy
+    (``glam_pair_list_load``: both sides' lists and the labels) — so a ``GraphedTrainStep(SharedStep(model), ...)`` captures ONE graph and
+    replays it for every batch of a shuffled epoch.
+
+    ``mol1`` / ``mol2``: the ``Batch`` of the ``Q1`` / ``Q2`` distinct drugs of each side, held once, on the device (one ``Batch`` may serve
+    both) — EVERY step runs both towers over all of them (DrugBank's ~1.7 k drugs fit); ``first`` / ``second``: ``ops.PairList(B, Q1)`` /
+    ``(B, Q2)``; ``y`` ``[B, r]``; ``num_real_graphs = B``: no phantom.  Exactly ``B`` pair ids per load — a shorter last batch runs eagerly
+    on host ``ops.pair_index`` lists, or is dropped."""
+
+    def __init__(self, pairs, drugs1, drugs2=None, batch_size=32):
+        from . import ops
+        dev = pairs.device
+        drugs2 = drugs1 if drugs2 is None else drugs2
+        Q1, Q2 = int(getattr(drugs1, "num_graphs", 0)), int(getattr(drugs2, "num_graphs", 0))
+        if Q1 < 1 or Q2 < 1:
+            raise ValueError("ddi_batch: drugs1 / drugs2 must be collated Batches of the distinct drugs of each side")
+        _check_ids_below(pairs.first_host, Q1, "first", "drugs")
+        _check_ids_below(pairs.second_host, Q2, "second", "drugs")
+        self.pairs, B = pairs, int(batch_size)
+        if B < 1:
+            raise ValueError(f"ddi_batch: batch_size must be >= 1, got {batch_size}")
+        self.first = ops.PairList(B, Q1, dev, name="first", over="drugs")
+        self.second = ops.PairList(B, Q2, dev, name="second", over="drugs")
+        same = drugs2 is drugs1
+        self.mol1 = drugs1 if drugs1.x.device == dev else drugs1.to(dev)
+        self.mol2 = self.mol1 if same else (drugs2 if drugs2.x.device == dev else drugs2.to(dev))
+        self.y = torch.empty((B,) + pairs.y.shape[1:], dtype=pairs.y.dtype, device=dev)
+        self.num_graphs = self.num_real_graphs = B
+        self._init_table(B, dev)
+
+    def _host_table(self, ids):
+        return ddi_table(ids, self.pairs.n, self.num_real_graphs)
+
+    def _enqueue(self):
+        from . import ops
+        ops.pair_list_launch(self._table, self.first, self.pairs.first, self.second, self.pairs.second, self.num_real_graphs,
+                             self.pairs.y, self.y)
+
+    def glam_admission(self, model):
+        """No phantom: nothing to admit beyond ``forward_shared``'s own refusals (a no-op context)."""
+        import contextlib
+        return contextlib.nullcontext()
 
 
 class DataLoader:

@@ -25,6 +25,8 @@ A loop that SHUFFLES has no recurring batch objects; it gets one by construction
 capacity that every ``load(ids)`` refills in place.  The stepper calls its reload hook (``glam_reload``: the collate launch) first in
 every step, so the capture holds it and a replay is one table copy and one ``hipGraphLaunch`` per shuffled batch; ``padded_loss`` keeps the
 phantom graph's output row out of the loss, and ``padded_admission`` refuses models that would let it reach the real graphs.
+Pair training (``forward_shared``) has the same form: the resident pair batches of ``glam_amd.data.ResidentPairs`` refill their pair lists
+and labels through the same hook, under ``model.SharedStep``, and bring their own admission check (``glam_admission``).
 """
 from __future__ import annotations
 
@@ -114,7 +116,10 @@ class GraphedTrainStep:
         guard = contextlib.nullcontext()
         if reload is not None:
             if not self._admitted:
-                guard = padded_admission(self.model)      # (ValueError here for what the module tree shows; the rest at its call)
+                # (ValueError here for what the module tree shows; the rest at its call.  A batch that knows which parts of the model see
+                #  its phantom rows — the resident pair batches of glam_amd.data — brings its own check)
+                admission = getattr(batch, "glam_admission", None)
+                guard = padded_admission(self.model) if admission is None else admission(self.model)
             reload()
         self.optimizer.zero_grad(set_to_none=True)
         with no_graphed_call(), guard:    # the whole step is this class's graph: the model's own graphed-callable route stays out of it
@@ -211,12 +216,16 @@ class padded_admission:
     ``_PairNorm`` that is CALLED without its ``batch`` vector (``flat_norm`` / ``end_norm`` of the reference's models): statistics over all
     rows again.  Admitted: ``_TripletMessage``, ``_TripletMessageLight``, ``_NNConv``, the norms called per graph, every readout."""
 
-    def __init__(self, model):
+    def __init__(self, model, only=None):
+        """``only``: the names of the children of ``model`` the check walks (``None``: the whole tree) — for a batch whose phantom rows
+        reach a part of the model alone (``dti_admission``)."""
         from . import layer
         refused = (layer._BatchNorm, layer.BatchNorm, torch.nn.modules.batchnorm._BatchNorm, layer._GraphSizeNorm, layer.GraphSizeNorm,
                    layer._GCNConv, layer._GATConv, layer.GCNConv, layer.GATConv)
         self._norms, self._handles = [], []
         for name, m in model.named_modules():
+            if only is not None and name.split(".")[0] not in only:
+                continue
             if isinstance(m, refused):
                 raise ValueError(f"padded batches: {name or 'model'} ({type(m).__name__}) makes a graph's output depend on the rest of the "
                                  f"batch or on host caches derived from its content; it is not admitted (DESIGN.md §4.16)")
@@ -237,6 +246,26 @@ class padded_admission:
         for h in self._handles:
             h.remove()
         return False
+
+
+class dti_admission(padded_admission):
+    """The admission check of a resident DTI pair batch (``glam_amd.data.ResidentPairs.dti_batch``) for an ``ArchitectureDTI``: its ligand
+    side is a ``PaddedBatch`` and its pair list carries the phantom ligands' slots, so ``padded_admission``'s rules hold for what sees
+    phantom rows — the ligand tower (``mol_lin0``, ``mol_conv``, ``mol_readout``, ``mol_flat``) and the head (``lin_out0``, ``lin_out1``: its
+    input has one row per slot, phantom slots included; the head is not exempted).  A ``_LayerNorm`` / ``_PairNorm`` in ``mol_flat``,
+    ``lin_out0`` or ``lin_out1`` is refused here, from the module tree: those slots are called without a ``batch`` vector by construction.
+    The protein tower is exempt: it runs over a ``Batch`` that never changes (its default ``_GCNConv`` caches a self-loop list that stays
+    true), and keeps ``forward_shared``'s own refusals."""
+
+    PARTS = ("mol_lin0", "mol_conv", "mol_readout", "mol_flat", "lin_out0", "lin_out1")
+    BATCHLESS = ("mol_flat", "lin_out0", "lin_out1")
+
+    def __init__(self, model):
+        padded_admission.__init__(self, model, only=self.PARTS)
+        for name, m in self._norms:
+            if name.split(".")[0] in self.BATCHLESS and name.count(".") == 1:
+                raise ValueError(f"padded batches: {name} ({type(m).__name__}) is called without a batch vector: its statistics would run "
+                                 f"over the phantom ligands' rows too; it is not admitted (DESIGN.md §4.29)")
 
 
 class GraphedForward:

@@ -989,7 +989,8 @@ class ArchitectureDDI(torch.nn.Module):
         what = "matrix_top" if logp else "score_matrix"
         _table_guard(self, what, enc, head, classes=logp)
         R, Cs, index, sel = self._matrix_selection(enc, rows, cols)                              # host-side, before the first launch
-        ids = (index or ops.pair_index(None, R, R)).host                                         # (rows=None: every drug in order)
+        ids = ops.host_index(index or ops.pair_index(None, R, R), "matrix_top",                  # (rows=None: every drug in order)
+                             "rows as the host integers that were loaded into it")
         per_block = block_rows or max(1, min(R, self._TOP_BLOCK_PAIRS // max(Cs, 1)))
         top = hits.HitList(Cs, k, enc.flat1.device, largest)
         for i0 in range(0, R, per_block):
@@ -1039,3 +1040,21 @@ class ArchitectureDDI(torch.nn.Module):
             o1 = ops.pair_rows(t1.flat_out(), i1)
             o2 = ops.pair_rows(t2.flat_out(), i2)
             return self.lin_out1(self.lin_out0(ops.cat_cols([o1, o2] + fusion)))
+
+
+class SharedStep(torch.nn.Module):
+    """``forward(batch)`` = ``model.forward_shared`` on a resident pair batch (``glam_amd.data.ResidentPairs.dti_batch`` / ``ddi_batch``):
+    what a ``GraphedTrainStep`` calls as its model, so that an epoch of shuffled pairs is one captured step replayed — DTI:
+    ``forward_shared(batch.mol, batch.pro, batch.index)``, DDI: ``forward_shared(batch.mol1, batch.mol2, batch.first, batch.second)``.
+    ``model`` is a submodule: parameters and checkpoint keys sit under the one prefix ``model.``."""
+
+    def __init__(self, model):
+        super().__init__()
+        if not isinstance(model, (ArchitectureDTI, ArchitectureDDI)):
+            raise GlamHipError(f"SharedStep wraps a model with forward_shared (ArchitectureDTI / ArchitectureDDI), got {type(model).__name__}")
+        self.model = model
+
+    def forward(self, batch):
+        if isinstance(self.model, ArchitectureDTI):
+            return self.model.forward_shared(batch.mol, batch.pro, batch.index)
+        return self.model.forward_shared(batch.mol1, batch.mol2, batch.first, batch.second)

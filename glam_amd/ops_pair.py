@@ -300,6 +300,125 @@ class PairsByProtein(_Staged):
         _Staged.__init__(self, "the pair list by protein", self.order, self.ptr)
 
 
+# --------------------------------------------------------------------------------------
+# refillable pair lists: the index and its by-protein lists at fixed device addresses, refilled by one launch (csrc/pairlist.hip)
+# --------------------------------------------------------------------------------------
+def pair_list_bounds(P, Q, pad=0, name="pro_of_pair"):
+    """``(P, Q, pad)`` of a ``PairList`` as ints, or the refusal — host only, before any allocation or copy: ``P >= 1``, ``Q >= 1``, ``pad``
+    in ``[0, Q)`` (``ValueError``), and a build the kernel has (``glam_pair_list_supported``: ``P``, ``Q`` <= 65 536 and ``P * Q`` <= 2^26 —
+    its work is O(P * Q); ``GlamHipError``)."""
+    P, Q, pad = int(P), int(Q), int(pad)
+    if P < 1 or Q < 1 or not 0 <= pad < Q:
+        raise ValueError(f"a pair list of {name} needs P >= 1 pairs over Q >= 1 segments and its padding segment in [0, Q): got P = {P}, "
+                         f"Q = {Q}, pad = {pad}")
+    if _lib.load().glam_pair_list_supported(P, Q) != 0:          # (a status: the raw binding hands it back)
+        raise GlamHipError(f"a pair list of {P} pairs over {Q} segments is beyond what one launch builds (P, Q <= 65536 and P * Q <= 2^26: "
+                           f"the build compares every pair with every segment) — build the lists on the host: ops.pair_index")
+    return P, Q, pad
+
+
+def pair_list_launch(ids, a, col_a, b, col_b, B, y=None, y_out=None):
+    """ONE ``glam_pair_list_load`` on the current stream: the lists of ``a`` / ``b`` (``PairList`` or None) from the device columns ``col_a``
+    / ``col_b`` through the pair ids ``ids`` (device int32 ``[B]``, None = identity), and ``y_out[:B] = y[ids]``.  Trusted: callers validate
+    on the host first."""
+    side = lambda l, c: (None, 0, 0, None, None, None) if l is None else (ptr(c), l.Q, l.pad, ptr(l.idx), ptr(l.order), ptr(l.ptr))   # noqa: E731
+    ca, Qa, pa, *outs_a = side(a, col_a)
+    cb, Qb, pb, *outs_b = side(b, col_b)
+    P = (a if a is not None else b).P
+    rb = 0 if y is None else int(np.prod(y.shape[1:], dtype=np.int64)) * y.element_size()
+    _lib.api().glam_pair_list_load(ptr(ids), ca, cb, ptr(y), rb, int(B), P, Qa, Qb, pa, pb, *outs_a, *outs_b, ptr(y_out), stream())
+
+
+class _FixedLists:
+    """``by_protein()`` of a ``PairList``: ``on(device)`` -> its fixed ``(order, ptr)``."""
+
+    def __init__(self, owner):
+        self._owner = owner
+
+    def on(self, device):
+        self._owner.on(device)
+        return self._owner.order, self._owner.ptr
+
+
+class PairList(PairIndex):
+    """A ``PairIndex`` of FIXED CAPACITY that lives on the device: ``idx`` int32 ``[P]``, ``order`` int32 ``[P]`` and ``ptr`` int32 ``[Q + 1]``
+    are allocated once and hold whatever the last load put into them (``glam_pair_list_load``, csrc/pairlist.hip: bit for bit the lists
+    ``PairsByProtein`` builds on the host), so a training step captured on this object replays for every pair list of a shuffling loop
+    (DESIGN.md §4.29).  ``on(device)`` is ``idx``, ``by_protein().on(device)`` is ``(order, ptr)`` — the same tensors every time; another
+    device than its own is refused.  ``host`` is None: what builds host tables from an index (``ops.map_plan``, ``matrix_top``) refuses it.
+    ``pad``: the segment the slots behind a shorter load point at.  ``name`` / ``over``: as ``pair_index``.  Until the first ``load`` every
+    slot points at ``pad``."""
+
+    def __init__(self, P, Q, device, pad=0, name="pro_of_pair", over="proteins"):
+        self.P, self.Q, self.pad = pair_list_bounds(P, Q, pad, name)
+        self.host, self.name, self.over = None, name, over
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise GlamHipError(f"a PairList lives on an MI355X HIP device (got {self.device}); the host form is ops.pair_index")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        # one allocation, every tensor on a 16-byte boundary
+        sizes = [self.P, self.P, self.Q + 1, self.P]
+        starts = np.concatenate([[0], np.cumsum([(s + 3) & ~3 for s in sizes])])
+        self._arena = torch.zeros(int(starts[-1]), dtype=torch.int32, device=self.device)
+        self.idx, self.order, self.ptr, self._stage = [self._arena[a:a + s] for a, s in zip(starts[:-1].tolist(), sizes)]
+        self._lists = _FixedLists(self)
+        self._launched = False
+        self._stage.fill_(self.pad)
+        self.glam_reload()
+
+    def on(self, device):
+        device = torch.device(device)
+        if device.type != self.device.type or (device.index is not None and device.index != self.device.index):
+            raise GlamHipError(f"this PairList lives on {self.device}, the operands on {device}: a pair list is read where it was loaded")
+        return self.idx
+
+    def by_protein(self):
+        return self._lists
+
+    def check(self, index):
+        """``index`` as the int32 ``[P]`` host vector a load stages — at most ``P`` integers in ``[0, Q)`` (``host_ints``: ``IndexError``; a
+        device tensor: ``GlamHipError``), the slots behind them at ``pad`` — host only."""
+        a = host_ints(index, self.name, "have one entry per pair", below=self.Q)
+        if a.shape[0] > self.P:
+            raise IndexError(f"{self.name} must hold at most the {self.P} pairs of this PairList, got {a.shape[0]}")
+        full = np.full(self.P, self.pad, dtype=np.int32)
+        full[:a.shape[0]] = a
+        return full
+
+    def load(self, index, launch=True):
+        """Put the pair -> segment index ``index`` (host integers, ``B <= P`` of them, each in ``[0, Q)``) into this list: checked on the
+        host (``IndexError`` before anything is enqueued), ONE pinned, non-blocking upload into the fixed staging vector, one launch that
+        rewrites ``idx``, ``order`` and ``ptr`` whole.  ``launch=False`` uploads only — for a step that holds the launch itself
+        (``glam_reload()`` first in it, as ``GraphedTrainStep`` does for a batch: the ``PaddedBatch`` protocol)."""
+        full = self.check(index)
+        require_device(self.idx)
+        staged = torch.empty(self.P, dtype=torch.int32, pin_memory=True)
+        staged.numpy()[...] = full
+        self._stage.copy_(staged, non_blocking=True)
+        self._launched = False
+        if launch:
+            self.glam_reload()
+            self._launched = True
+        return self
+
+    def glam_reload(self):
+        """Enqueue the launch for the index now in the staging vector, on the current stream — inside a capture it becomes a node of the
+        graph.  Outside a capture a ``load`` that has launched already is not repeated."""
+        if self._launched and not torch.cuda.is_current_stream_capturing():
+            self._launched = False
+            return
+        pair_list_launch(None, self, self._stage, None, None, self.P)
+
+
+def host_index(index, who, instead):
+    """``index.host`` of a ``PairIndex``, or the refusal of a ``PairList`` (no host copy) in the words of ``who``; ``instead``: what to pass."""
+    if isinstance(index, PairList):
+        raise GlamHipError(f"{who} builds its tables on the host and a PairList keeps its index on the device only (reading it would be a "
+                           f"hidden read-back): pass {instead}")
+    return index.host
+
+
 def pair_index(pro_of_pair, P, Q, default="identity", name="pro_of_pair", over="proteins"):
     """``PairIndex`` of ``pro_of_pair`` for ``P`` pairs over ``Q`` proteins — host only, before anything is launched (the kernel trusts
     the index; the policy of ``data.resident_table``).  A host sequence, numpy array or CPU tensor of integers of length ``P``;
@@ -855,8 +974,9 @@ def map_plan(sizes1_host, sizes2_host, idx1=None, idx2=None):
     sizes = [_plan_sizes("map_plan", s, f"the sizes of side {k}") for k, s in ((1, sizes1_host), (2, sizes2_host))]
     Q1, Q2 = int(sizes[0].shape[0]), int(sizes[1].shape[0])
     P = pair_count(idx1, idx2, Q1)
-    a = pair_index(idx1, P, Q1, name="idx1", over="segments of x1").host.astype(np.int64)
-    b = pair_index(idx2, P, Q2, name="idx2", over="segments of x2").host.astype(np.int64)
+    instead = "the host integers that were loaded into it (or the ops.pair_index of them)"
+    a = host_index(pair_index(idx1, P, Q1, name="idx1", over="segments of x1"), "map_plan", instead).astype(np.int64)
+    b = host_index(pair_index(idx2, P, Q2, name="idx2", over="segments of x2"), "map_plan", instead).astype(np.int64)
     return MapPlan(sizes[0], sizes[1], a, b)
 
 

@@ -1284,6 +1284,31 @@ int glam_collate_padded_split(const void* const* ds_host, void* const* out_host,
                               int64_t E_cap, int64_t y_rows, int64_t Ed, int32_t x_row_bytes, int32_t x_out_stride_bytes,
                               int32_t ea_row_bytes, int32_t y_row_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Refillable pair lists (csrc/pairlist.hip): what glam_pair_pool_shared_fwd / _bwd, glam_pair_pool_gather_train_fwd / _bwd and
+ * glam_pair_rows_bwd read of a step's pairs, written into tensors of FIXED addresses by ONE launch — grid, sizes and every pointer the
+ * same for every step, so the launch can sit inside a captured hipGraph.  Replaces: nothing in the reference (its loaders collate one
+ * graph per pair and side); here it is what lets an epoch of SHUFFLED pairs replay one captured forward_shared step.
+ * Inputs, all on the device and trusted (the host validates before anything is enqueued): ids int32 [B], the step's pair ids, NULL =
+ * identity (ids[i] = i); col_a / col_b int32 [Np], the dataset's pair columns — a segment id per pair — either NULL = that side is
+ * absent; y [Np rows of y_row_bytes], the dataset's labels, or NULL.
+ * Outputs per present side s, over Q_s segments, capacity P >= B, padding segment pad_s in [0, Q_s):
+ *   idx_s   int32 [P]:       col_s[ids[i]] for i < B, pad_s for B <= i < P
+ *   order_s int32 [P]:       the STABLE argsort of idx_s (the slots of one segment in ascending i)
+ *   ptr_s   int32 [Q_s + 1]: the offsets of the segments' runs in order_s, ptr_s[Q_s] = P
+ * bit for bit np.argsort(idx, kind="stable") and [0] + cumsum(bincount(idx, minlength=Q)): the lists ops.PairsByProtein builds on the
+ * host, on whose order the backward kernels' run-to-run bit equality rests.  y_out [B rows] = y[ids[i]], bytewise (y_row_bytes a
+ * multiple of 4, both on a 4-byte boundary).  EVERY output word is written by every launch, by exactly one lane: a second, different
+ * load leaves no residue.  No workspace, no atomics, no LDS.
+ * The build is O(P * Q / 64) wave rounds per side: GLAM_E_UNSUPPORTED for P > 65 536, Q > 65 536 or P * Q > 2^26 on a present side —
+ * checked before the pointers are looked at; glam_pair_list_supported(P, Q) is that check alone and returns a STATUS.
+ * GLAM_E_INVALID for P < 1, B outside [0, P], nothing to load (no side, no y), a present side with Q < 1, pad outside [0, Q) or a
+ * null output, y without y_out (or the reverse), label rows that are no multiple of 4 bytes or misaligned. */
+int glam_pair_list_supported(int64_t P, int64_t Q);
+int glam_pair_list_load(const int32_t* ids, const int32_t* col_a, const int32_t* col_b, const void* y, int32_t y_row_bytes, int64_t B,
+                        int64_t P, int64_t Qa, int64_t Qb, int32_t pad_a, int32_t pad_b, int32_t* idx_a, int32_t* order_a,
+                        int32_t* ptr_a, int32_t* idx_b, int32_t* order_b, int32_t* ptr_b, void* y_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -232,6 +232,9 @@ SIGNATURES = {
                                          _vp]),
     "glam_pair_list_supported": (_i32, [_i64, _i64]),
     "glam_pair_list_load": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32] + [_vp] * 8),
+    "glam_gcn_scale": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "glam_gcn_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "glam_gcn_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
 }
 
 # An ``int`` return is a status (0 = ok, < 0 = GLAM_E_*) that api() checks — the default, so that a new entry point is safe without

@@ -586,6 +586,37 @@ def dti_tables(pair_ids, first, ns, es, batch_size):
     return np.concatenate([slots.reshape(-1), ids]), N, E
 
 
+def protein_slot_ids(second_of_pairs, ns, slots):
+    """The protein side of one refill load (host, O(B log B) numpy) -> ``(slot_ids, keys, U)``: ``u`` = the sorted distinct entries of
+    ``second_of_pairs`` (the proteins of the step's pairs), ``U = len(u)``; ``slot_ids`` int64 ``[slots]`` = ``u`` followed by ``slots - U``
+    FILLER proteins, the smallest by ``(ns, id)`` that are not in ``u`` — exactly ``slots`` distinct graphs, the case ``padded_capacity``
+    guarantees to fit; ``keys`` = ``searchsorted(u, second_of_pairs)``, the slot of every pair's protein.  ``ValueError`` for ``U > slots``
+    (the caller runs that step eagerly on ``proteins.collate(u)`` with ``ops.pair_index``) — before anything is enqueued."""
+    sec = np.asarray(second_of_pairs, dtype=np.int64)
+    ns = np.asarray(ns, dtype=np.int64)
+    u = np.unique(sec)
+    U, Q = int(u.size), int(slots)
+    if U > Q:
+        raise ValueError(f"this step's pairs name {U} distinct proteins, the batch holds protein_slots = {Q}: run the step eagerly on "
+                         f"proteins.collate(u) with ops.pair_index, or build the batch with more slots")
+    # (among the Q smallest at most U are in u: Q - U fillers are always found there)
+    smallest = np.lexsort((np.arange(ns.size), ns))[:Q]
+    fill = smallest[~np.isin(smallest, u)][:Q - U]
+    return np.concatenate([u, fill]).astype(np.int64), np.searchsorted(u, sec).astype(np.int32), U
+
+
+def dti_refill_tables(pair_ids, first, second, lig_ns, lig_es, pro_ns, pro_es, batch_size, slots, phantoms):
+    """The host side of one load of a ``ResidentDTIRefillBatch`` -> ``(table, (N, E), (Np, Ep))``: ``table`` int32 — the ligand slot table
+    and the pair ids as ``dti_tables`` lays them out, then the protein slot table ``[4 * (slots + 1)]`` of ``resident_table`` over
+    ``protein_slot_ids``' ids, then the ``batch_size + phantoms`` keys (the phantom ligand slots keep key 0) — and both sides' node / edge
+    totals for the capacity checks.  Errors of ``pair_ids_table`` and ``protein_slot_ids``."""
+    lig, N, E = dti_tables(pair_ids, first, lig_ns, lig_es, batch_size)
+    ids = lig[-int(batch_size):]
+    slot_ids, keys, _U = protein_slot_ids(second[ids], pro_ns, slots)
+    pro, Np, Ep, _Y = resident_table(slot_ids, pro_ns, pro_es, np.zeros(pro_ns.shape[0], dtype=np.int64))
+    return np.concatenate([lig, pro.reshape(-1), keys, np.zeros(int(phantoms), dtype=np.int32)]), (N, E), (Np, Ep)
+
+
 def ddi_table(pair_ids, n_pairs, batch_size):
     """The host side of one DDI load: the checked pair ids, int32 ``[B]`` (``pair_ids_table``)."""
     return pair_ids_table(pair_ids, n_pairs, batch_size)
@@ -627,10 +658,24 @@ class ResidentPairs:
     def __len__(self):
         return self.n
 
-    def dti_batch(self, ligands, proteins, batch_size, phantom_rows=None, capacity=None):
+    def dti_batch(self, ligands, proteins, batch_size, phantom_rows=None, capacity=None, protein_slots=None, protein_phantom_rows=None,
+                  protein_capacity=None):
         """The refillable batch of ``batch_size`` (ligand, protein) pairs for ``ArchitectureDTI.forward_shared`` — ``first`` = ligand id in
         the ``DeviceDataset`` ``ligands`` (which carries no ``y``), ``second`` = protein id in the ``Batch`` ``proteins``: see
-        ``ResidentDTIBatch``.  ``phantom_rows`` / ``capacity``: as ``DeviceDataset.padded``."""
+        ``ResidentDTIBatch``.  ``phantom_rows`` / ``capacity``: as ``DeviceDataset.padded``.
+
+        ``proteins`` a ``DeviceDataset`` (no ``y``) instead: ``second`` = protein id in that dataset, and the protein side is refilled per
+        load too — a padded batch of ``protein_slots`` protein graphs (``protein_phantom_rows`` / ``protein_capacity``: as
+        ``DeviceDataset.padded``), so a step runs the protein tower over the step's distinct proteins, not over the dataset's: see
+        ``ResidentDTIRefillBatch``."""
+        if isinstance(proteins, DeviceDataset):
+            if protein_slots is None:
+                raise ValueError("dti_batch: a DeviceDataset of proteins needs protein_slots = the protein graphs a step holds")
+            return ResidentDTIRefillBatch(self, ligands, proteins, batch_size, protein_slots, phantom_rows, capacity, protein_phantom_rows,
+                                          protein_capacity)
+        if protein_slots is not None or protein_phantom_rows is not None or protein_capacity is not None:
+            raise ValueError("dti_batch: protein_slots / protein_phantom_rows / protein_capacity go with a DeviceDataset of proteins; a "
+                             "Batch of proteins is held whole")
         return ResidentDTIBatch(self, ligands, proteins, batch_size, phantom_rows, capacity)
 
     def ddi_batch(self, drugs1, drugs2=None, batch_size=32):
@@ -750,6 +795,81 @@ class ResidentDTIBatch(_ResidentPairBatch):
         rules for the ligand tower and the head, the protein tower exempt.  ``model``: the ``SharedStep`` or the ``ArchitectureDTI``."""
         from .graphs import dti_admission
         return dti_admission(getattr(model, "model", model))
+
+
+class ResidentDTIRefillBatch(_ResidentPairBatch):
+    """``ResidentDTIBatch`` whose PROTEIN side is refilled too: a step runs the protein tower over the step's distinct
+    proteins — at most ``Qb = protein_slots`` of a ``DeviceDataset`` of hundreds or thousands — not over the whole dataset.  One small copy
+    and four launches per load: the ligand collate, the protein collate (``glam_collate_padded`` / ``_split``, unchanged), the pair lists
+    from the uploaded keys (``PairList``'s staged-keys launch) and the label gather (``glam_pair_list_load`` without a side).
+
+    ``mol``: as ``ResidentDTIBatch``; ``pro``: a ``PaddedBatch`` of ``Qb + Kp`` protein graphs whose ``edge_index`` carries the mark of
+    ``ops.mark_gcn_inline`` (``layer.GCNConv`` then reads self-loops and normalisation from the batch's own CSR, csrc/gcn.hip);
+    ``index``: ``ops.PairList(B + K, Qb + Kp, pad=0)``; ``y`` ``[B, r]``.  The slots of a load (``protein_slot_ids``): the sorted distinct
+    proteins ``u`` of its pairs, then ``Qb - U`` fillers — real proteins without a pair: an empty list, a zero gradient; ``slots`` / ``keys``
+    / ``distinct`` keep the last ``load(ids)``'s on the host.  Order contract: the real part of ``pro`` equals ``proteins.collate(slots)``
+    field by field, ``index`` the lists ``ops.pair_index(keys, B + K, Qb + Kp)`` builds on the host, bit for bit.  ``ValueError`` for a
+    load with more than ``Qb`` distinct proteins, before anything is enqueued."""
+
+    def __init__(self, pairs, ligands, proteins, batch_size, protein_slots, phantom_rows=None, capacity=None, protein_phantom_rows=None,
+                 protein_capacity=None):
+        from . import ops
+        if not isinstance(ligands, DeviceDataset) or ligands.y is not None:
+            raise ValueError("dti_batch: ligands must be a DeviceDataset without y (the labels belong to the pairs: ResidentPairs.y)")
+        if not isinstance(proteins, DeviceDataset) or proteins.y is not None:
+            raise ValueError("dti_batch: refilled proteins must be a DeviceDataset without y")
+        dev = pairs.device
+        for name, ds in (("ligands", ligands), ("proteins", proteins)):
+            if ds.device != dev:
+                raise ValueError(f"dti_batch: the {name} live on {ds.device}, the pair table on {dev}")
+        _check_ids_below(pairs.first_host, ligands.n, "first", "ligands")
+        _check_ids_below(pairs.second_host, proteins.n, "second", "proteins")
+        self.pairs, B, Qb = pairs, int(batch_size), int(protein_slots)
+        if B < 1:
+            raise ValueError(f"dti_batch: batch_size must be >= 1, got {batch_size}")
+        if not 1 <= Qb <= proteins.n:
+            raise ValueError(f"dti_batch: protein_slots must lie in 1 .. {proteins.n} (the dataset's proteins), got {protein_slots}")
+        mol = PaddedBatch(ligands, B, capacity, phantom_rows, labels=False)
+        pro = PaddedBatch(proteins, Qb, protein_capacity, protein_phantom_rows, labels=False)
+        ops.mark_gcn_inline(pro.edge_index)
+        self.index = ops.PairList(mol.num_graphs, pro.num_graphs, dev, pad=0)
+        self.mol, self.pro = mol, pro
+        self.y = torch.empty((B,) + pairs.y.shape[1:], dtype=pairs.y.dtype, device=dev)
+        self.num_graphs, self.num_real_graphs, self.protein_slots = mol.num_graphs, B, Qb
+        # one table, one copy: ligand slots | pair ids | protein slots | keys
+        cuts = np.cumsum([0, 4 * (B + 1), B, 4 * (Qb + 1), mol.num_graphs]).tolist()
+        self._init_table(cuts[-1], dev)
+        mol._table = self._table[cuts[0]:cuts[1]].view(4, B + 1)
+        self._ids = self._table[cuts[1]:cuts[2]]
+        pro._table = self._table[cuts[2]:cuts[3]].view(4, Qb + 1)
+        self.index._stage = self._table[cuts[3]:cuts[4]]              # (the list's launch reads the keys where this batch's copy lands)
+        self._cuts = cuts
+        self.slots = self.keys = self.distinct = None
+
+    def _host_table(self, ids):
+        lig, pro = self.mol._ds, self.pro._ds
+        B, Qb = self.num_real_graphs, self.protein_slots
+        table, (N, E), (Np, Ep) = dti_refill_tables(ids, self.pairs.first_host, self.pairs.second_host, lig.ns, lig.es, pro.ns, pro.es, B, Qb,
+                                                    self.mol.num_phantom_graphs)
+        self.mol._fit(B, N, E)
+        self.pro._fit(Qb, Np, Ep)
+        c = self._cuts
+        self.slots, self.keys = table[c[2]:c[2] + Qb].astype(np.int64), table[c[3]:c[3] + B].copy()
+        self.distinct = int(self.keys.max()) + 1
+        return table
+
+    def _enqueue(self):
+        from . import ops
+        for part in (self.mol, self.pro, self.index):
+            part._launched = False
+            part.glam_reload()
+        ops.pair_list_launch(self._ids, None, None, None, None, self.num_real_graphs, self.pairs.y, self.y)
+
+    def glam_admission(self, model):
+        """``graphs.dti_refill_admission``: ``dti_admission``'s rules, and ``padded_admission``'s for the protein tower with ``_GCNConv``
+        admitted.  ``model``: the ``SharedStep`` or the ``ArchitectureDTI``."""
+        from .graphs import dti_refill_admission
+        return dti_refill_admission(getattr(model, "model", model))
 
 
 class ResidentDDIBatch(_ResidentPairBatch):

@@ -26,7 +26,8 @@ capacity that every ``load(ids)`` refills in place.  The stepper calls its reloa
 every step, so the capture holds it and a replay is one table copy and one ``hipGraphLaunch`` per shuffled batch; ``padded_loss`` keeps the
 phantom graph's output row out of the loss, and ``padded_admission`` refuses models that would let it reach the real graphs.
 Pair training (``forward_shared``) has the same form: the resident pair batches of ``glam_amd.data.ResidentPairs`` refill their pair lists
-and labels through the same hook, under ``model.SharedStep``, and bring their own admission check (``glam_admission``).
+and labels through the same hook, under ``model.SharedStep``, and bring their own admission check (``glam_admission``; DESIGN.md §4.29);
+a DTI batch over a ``DeviceDataset`` of proteins refills its protein graphs the same way (``dti_refill_admission``).
 """
 from __future__ import annotations
 
@@ -266,6 +267,39 @@ class dti_admission(padded_admission):
             if name.split(".")[0] in self.BATCHLESS and name.count(".") == 1:
                 raise ValueError(f"padded batches: {name} ({type(m).__name__}) is called without a batch vector: its statistics would run "
                                  f"over the phantom ligands' rows too; it is not admitted (DESIGN.md §4.29)")
+
+
+class dti_refill_admission(dti_admission):
+    """The admission check of a resident DTI pair batch whose PROTEIN side is refilled too (``glam_amd.data.ResidentDTIRefillBatch``):
+    ``dti_admission``'s rules, and — the protein batch now is a ``PaddedBatch`` with phantom graphs and filler proteins whose content
+    changes per load — ``padded_admission``'s rules for the protein tower (``pro_lin0``, ``pro_conv``, ``pro_readout``, ``pro_flat``) with ONE
+    difference: ``_GCNConv`` is admitted there, because on that batch's marked ``edge_index`` it reads self-loops and normalisation from
+    the batch's own CSR (``ops.gcn_aggregate``) and caches nothing derived from the content.  Refused, naming the module, before anything
+    runs: a protein-side ``_GATConv`` (its self-loop list is still derived on the host), ``_BatchNorm`` and ``_GraphSizeNorm``, and a
+    ``_LayerNorm`` / ``_PairNorm`` in ``pro_flat``'s slot (called without a ``batch`` vector by construction)."""
+
+    PRO_PARTS = ("pro_lin0", "pro_conv", "pro_readout", "pro_flat")
+    PRO_BATCHLESS = ("pro_flat",)
+
+    def __init__(self, model):
+        from . import layer
+        dti_admission.__init__(self, model)
+        refused = (layer._BatchNorm, layer.BatchNorm, torch.nn.modules.batchnorm._BatchNorm, layer._GraphSizeNorm, layer.GraphSizeNorm,
+                   layer._GATConv, layer.GATConv)
+        for name, m in model.named_modules():
+            if name.split(".")[0] not in self.PRO_PARTS:
+                continue
+            if isinstance(m, refused):
+                why = ("derives its self-loop edge list on the host and caches it: stale on a protein batch that is refilled in place"
+                       if isinstance(m, (layer._GATConv, layer.GATConv)) else
+                       "makes a protein's output depend on the phantom and filler graphs of the batch")
+                raise ValueError(f"refilled protein batches: {name} ({type(m).__name__}) {why}; it is not admitted (DESIGN.md §4.30)")
+            if isinstance(m, (layer._LayerNorm, layer._PairNorm)):
+                if name.split(".")[0] in self.PRO_BATCHLESS and name.count(".") == 1:
+                    raise ValueError(f"refilled protein batches: {name} ({type(m).__name__}) is called without a batch vector: its "
+                                     f"statistics would run over the phantom and filler proteins' rows too; it is not admitted "
+                                     f"(DESIGN.md §4.30)")
+                self._norms.append((name, m))
 
 
 class GraphedForward:

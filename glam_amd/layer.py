@@ -538,6 +538,16 @@ class GCNConv(MessagePassing):
     def forward(self, x, edge_index, edge_weight=None, add_bias=True, with_identity=False):
         n = x.size(0)
         gi0 = ops.graph_index(edge_index, n)
+        if edge_weight is None and ops.gcn_inline(edge_index):
+            # an edge list that is rewritten in place (a refilled protein batch): self-loops and normalisation come out of its own CSR in
+            # every pass (csrc/gcn.hip) — no derived edge list, no second GraphIndex, no cached norm that would go stale
+            if with_identity:
+                xw, ident = ops.matmul_tall(x, self.weight, with_identity=True)
+            else:
+                xw, ident = ops.matmul_tall(x, self.weight), x
+            out = ops.gcn_aggregate(xw, gi0, owner=edge_index)
+            out = out if (self.bias is None or not add_bias) else out + self.bias
+            return (out, ident) if with_identity else out
         ei, gi, mask = _with_self_loops(gi0, edge_index, n, True)
         if edge_weight is None:        # the reference's call (layer.py:148): the normalisation is a function of the edge list
             cache = gi.__dict__.setdefault("_derived", {})

@@ -319,12 +319,12 @@ def pair_list_bounds(P, Q, pad=0, name="pro_of_pair"):
 
 def pair_list_launch(ids, a, col_a, b, col_b, B, y=None, y_out=None):
     """ONE ``glam_pair_list_load`` on the current stream: the lists of ``a`` / ``b`` (``PairList`` or None) from the device columns ``col_a``
-    / ``col_b`` through the pair ids ``ids`` (device int32 ``[B]``, None = identity), and ``y_out[:B] = y[ids]``.  Trusted: callers validate
-    on the host first."""
+    / ``col_b`` through the pair ids ``ids`` (device int32 ``[B]``, None = identity), and ``y_out[:B] = y[ids]``.  Neither list: the label
+    gather alone.  Trusted: callers validate on the host first."""
     side = lambda l, c: (None, 0, 0, None, None, None) if l is None else (ptr(c), l.Q, l.pad, ptr(l.idx), ptr(l.order), ptr(l.ptr))   # noqa: E731
     ca, Qa, pa, *outs_a = side(a, col_a)
     cb, Qb, pb, *outs_b = side(b, col_b)
-    P = (a if a is not None else b).P
+    P = int(B) if a is None and b is None else (a if a is not None else b).P
     rb = 0 if y is None else int(np.prod(y.shape[1:], dtype=np.int64)) * y.element_size()
     _lib.api().glam_pair_list_load(ptr(ids), ca, cb, ptr(y), rb, int(B), P, Qa, Qb, pa, pb, *outs_a, *outs_b, ptr(y_out), stream())
 

@@ -423,6 +423,73 @@ def self_slot_supported(K, D):
 
 
 # --------------------------------------------------------------------------------------
+# GCN aggregation from the batch's own CSR (csrc/gcn.hip): nothing derived from the edge list's CONTENT on the host
+# --------------------------------------------------------------------------------------
+_GCN_INLINE = "_glam_gcn_inline"
+
+
+def mark_gcn_inline(edge_index):
+    """Mark ``edge_index`` for ``layer.GCNConv``'s inline route (``gcn_aggregate``): its self-loop handling and normalisation are then
+    read from the edge list's own CSR in every pass, and nothing derived from its content is cached — the route of an edge list that a
+    kernel rewrites in place (``glam_amd.data.ResidentDTIRefillBatch``).  The mark lives on the tensor OBJECT, not on its ``GraphIndex``."""
+    setattr(edge_index, _GCN_INLINE, True)
+    return edge_index
+
+
+def gcn_inline(edge_index):
+    return getattr(edge_index, _GCN_INLINE, False) is True
+
+
+def gcn_scale(gi, owner=None):
+    """``dis[N]`` = ``deg^-1/2`` of ``gcn_aggregate`` for the index ``gi`` (one launch).  Kept in the weight scope of the running model
+    pass (``ops.weight_scope``) under ``owner`` — the edge_index tensor — so the applications of a block and both towers' passes compute
+    it once per edge list and PASS, and a later pass (another load of a refilled batch) computes it anew; never on the ``GraphIndex``."""
+    def build():
+        dis = torch.empty(gi.N, dtype=torch.float32, device=gi.device)
+        _lib.api().glam_gcn_scale(ptr(gi.rowptr), ptr(gi.src), gi.N, ptr(dis), stream())
+        return dis
+    owner = gi if owner is None else owner
+    return _o.scoped_weights(("gcn-dis", id(owner)), owner, build)
+
+
+class _GCNAggregate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xw, gi, dis):
+        require_device(xw, dis)
+        if xw.dtype != torch.float32 or xw.dim() != 2:
+            raise GlamHipError(f"gcn_aggregate: xw must be float32 [N, D], got {xw.dtype} {tuple(xw.shape)}")
+        if xw.stride(1) != 1 or xw.stride(0) < xw.size(1):      # (rows of a wider buffer pass as they are: ld = their stride)
+            xw = xw.contiguous()
+        N, D = xw.shape
+        if N != gi.N or dis.numel() != N:
+            raise GlamHipError("gcn_aggregate: xw / dis disagree with the edge list")
+        ld = xw.stride(0)
+        out = torch.empty(N, D, dtype=torch.float32, device=xw.device)
+        _lib.api().glam_gcn_fwd(ptr(xw), ld, ptr(dis), ptr(gi.rowptr), ptr(gi.src), N, D, ptr(out), stream())
+        ctx.save_for_backward(dis)
+        ctx.gi = gi
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (dis,) = ctx.saved_tensors
+        gi = ctx.gi
+        g = f32c(g, "d_out")
+        colptr, dst, _eid_t = gi.transpose()
+        d_xw = torch.empty_like(g)
+        _lib.api().glam_gcn_bwd(ptr(g), ptr(dis), ptr(colptr), ptr(dst), gi.N, g.size(1), ptr(d_xw), stream())
+        return d_xw, None, None
+
+
+def gcn_aggregate(xw, gi, owner=None):
+    """``out[i] = dis[i] * (dis[i] * xw[i] + sum_{e -> i, src_e != i} dis[src_e] * xw[src_e])`` with ``dis = (1 + in-degree without
+    self-loops)^-1/2`` -> ``[N, D]``, ``1 <= D <= 128``: PyG's ``GCNConv`` propagate behind ``add_remaining_self_loops`` + ``gcn_norm`` for
+    unit edge weights, from the CSR of ``gi`` alone (``glam_gcn_scale`` / ``glam_gcn_fwd`` / ``glam_gcn_bwd``).  ``owner``: see ``gcn_scale``."""
+    return _GCNAggregate.apply(xw, gi, gcn_scale(gi, owner))
+
+
+# --------------------------------------------------------------------------------------
 # NNConv over continuous edge features (csrc/nnconv_ec.hip): no per-edge weight tensor
 # --------------------------------------------------------------------------------------
 class _NNConvECStack(torch.autograd.Function):

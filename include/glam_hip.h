@@ -1309,6 +1309,28 @@ int glam_pair_list_load(const int32_t* ids, const int32_t* col_a, const int32_t*
                         int64_t P, int64_t Qa, int64_t Qb, int32_t pad_a, int32_t pad_b, int32_t* idx_a, int32_t* order_a,
                         int32_t* ptr_a, int32_t* idx_b, int32_t* order_b, int32_t* ptr_b, void* y_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * GCN aggregation from an edge list's own CSR (csrc/gcn.hip).  Replaces: PyG's GCNConv.propagate behind add_remaining_self_loops +
+ * gcn_norm with unit edge weights (torch_geometric/nn/conv/gcn_conv.py), as a closed form over the RAW edge list — no derived edge list,
+ * no per-edge norm vector — so it holds on a batch whose index a kernel rewrites in place:
+ *   deg[i] = 1 + #{e -> i : src_e != i}                 dis[i] = 1 / sqrt(deg[i])
+ *   out[i] = dis[i] * ( dis[i] * xw[i] + sum_{e -> i, src_e != i} dis[src_e] * xw[src_e] )
+ *   d_xw[j] = dis[j] * ( dis[j] * g[j] + sum_{e : j -> i, i != j} dis[i] * g[i] )
+ * Existing self-loops are skipped and every node gets one implicit loop; duplicates count as often as they occur; an isolated node
+ * returns xw[i].  Summation order: the own term first, then the row's edges in CSR order (one fmaf each), then the multiply by dis.
+ * glam_gcn_scale: rowptr int32 [N + 1] / src int32 [E], the CSR by target -> dis fp32 [N].
+ * glam_gcn_fwd:   xw fp32 [N rows, ld floats apart, D channels], the same CSR -> out fp32 [N, D] (contiguous).
+ * glam_gcn_bwd:   g fp32 [N, D], colptr int32 [N + 1] / dst int32 [E], the CSR by source -> d_xw fp32 [N, D].
+ * 1 <= D <= 128 (GLAM_E_UNSUPPORTED beyond); a 16-byte path when D % 4 == 0, ld % 4 == 0 and both row bases are 16-byte aligned, a
+ * scalar path otherwise.  Any degree, 0 included.  No atomics, no workspace, no read-back; every output word is written by exactly one
+ * lane, so two runs agree bit for bit.  Index entries outside [0, N) are skipped.  N == 0 launches nothing.
+ * GLAM_E_INVALID for N out of range, ld < D or a null pointer. */
+int glam_gcn_scale(const int32_t* rowptr, const int32_t* src, int64_t N, float* dis, void* stream);
+int glam_gcn_fwd(const float* xw, int64_t ld, const float* dis, const int32_t* rowptr, const int32_t* src, int64_t N, int32_t D, float* out,
+                 void* stream);
+int glam_gcn_bwd(const float* g, const float* dis, const int32_t* colptr, const int32_t* dst, int64_t N, int32_t D, float* d_xw,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
